@@ -24,6 +24,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 import unires_amd  # noqa: F401  (first: its import sets ROC_SIGNAL_POOL_SIZE before anything initialises the HIP runtime)
@@ -273,6 +274,34 @@ def cpu_baseline(wl, seconds_budget=25.0, device=None):
     return out
 
 
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much array data (64 MB in all with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_outputs(y, out_dir):
+    """Write what the timed step hands its caller - the reconstruction y of every channel - as
+    ``out_dir/y_c<c>.npy`` (float32).  A channel larger than its share of DUMP_BYTES is written as a fixed
+    sample: the values at sorted flat indices drawn without replacement by a CPU generator seeded with
+    DUMP_SEED, the same for every channel and every run of the same workload.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // (4 * len(y))
+    idx = None
+    written = {}
+    for c, yc in enumerate(y):
+        flat = yc.dat.detach().reshape(-1)
+        if flat.numel() <= cap:
+            arr = yc.dat.detach().cpu().numpy()
+        else:
+            if idx is None:
+                gen = torch.Generator().manual_seed(DUMP_SEED)
+                idx = torch.randperm(flat.numel(), generator=gen)[:cap].sort().values
+            arr = flat[idx.to(flat.device)].cpu().numpy()
+        name = 'y_c%d' % c
+        np.save(os.path.join(out_dir, name + '.npy'), arr.astype(np.float32, copy=False))
+        written[name] = list(arr.shape)
+    return written
+
+
 def time_steps(step, steps, warmup):
     for _ in range(warmup):
         step()
@@ -376,7 +405,12 @@ def main():
     ap.add_argument('--cpu-seconds', type=float, default=25.0)
     ap.add_argument('--admm-iters', type=int, default=50,
                     help='ADMM iterations of the subjects/sec leg (one subject = this many iterations)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (y of every channel, a fixed '
+                         'seeded sample where it is larger than 64 MB in all) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started as plain `python bench.py --gpus N`: re-launch as N ranks, one per GPU
@@ -432,6 +466,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(y, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     C = wl['C']
     iters_per_step = C * sett.cgs_max_iter
@@ -578,6 +613,8 @@ def main():
                                    'Infinity Cache holds (the round-2 method), _graph: those replayed as one hipGraph, '
                                    '_by_channel: cold, one channel at a time'},
         }
+        if dumped is not None:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'shapes': dumped}
         if world == 1 and not args.no_variants:
             out['variants'] = variants(args.workload, x, y, z, w, rho, tmp, sett, device)
         if not args.no_cpu_baseline and world == 1:

@@ -4,6 +4,10 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The CPU oracle's float32 matrix products run in MKL, whose default kernels differ by CPU vendor and instruction set:
+# the last bits of its results - and the vectors pinned in tests/golden/ref_*.npz - would depend on the host.  MKL's
+# compatible code path gives the same bits on every x86 CPU (read at MKL's first call, so set before any test runs).
+os.environ['MKL_CBWR'] = 'COMPATIBLE'
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 

@@ -76,11 +76,27 @@ def test_read_write_image_mirrors(tmp_path):
         nifti.read(str(tmp_path / 'bad.nii.gz'))
 
 
-def test_reads_the_reference_demo_volume_if_present():
-    """BASELINE configs[0] names data/t1_icbm_normal_1mm_pn0_rf0.nii.gz (BrainWeb T1, 1 mm)."""
-    p = '/root/reference/data/t1_icbm_normal_1mm_pn0_rf0.nii.gz'
-    if not os.path.exists(p):
-        pytest.skip('reference data not on this machine')
+def test_reads_a_volume_of_the_reference_demo_geometry(tmp_path):
+    """BASELINE configs[0] names data/t1_icbm_normal_1mm_pn0_rf0.nii.gz (BrainWeb T1, 1 mm): a gzipped file of
+    that geometry - 181 x 217 x 181 uint8 voxels of 1 mm, unscaled, sform into ICBM space next to a qform that
+    must lose - built byte by byte here rather than by nifti.write."""
+    shape = (181, 217, 181)
+    vals = (np.arange(np.prod(shape)) % 251).astype(np.uint8).reshape(shape, order='F')
+    hdr = bytearray(348)
+    struct.pack_into('<i', hdr, 0, 348)
+    struct.pack_into('<8h', hdr, 40, 3, *shape, 1, 1, 1, 1)
+    struct.pack_into('<2h', hdr, 70, 2, 8)
+    struct.pack_into('<8f', hdr, 76, 1.0, 1.0, 1.0, 1.0, 1, 1, 1, 1)
+    struct.pack_into('<f', hdr, 108, 352.0)  # (scl_slope 0: no scaling)
+    struct.pack_into('<2h', hdr, 252, 1, 1)
+    struct.pack_into('<6f', hdr, 256, 0.0, 0.0, 1.0, 5.0, 6.0, 7.0)
+    struct.pack_into('<12f', hdr, 280, 1, 0, 0, -90, 0, 1, 0, -126, 0, 0, 1, -72)
+    hdr[344:348] = b'n+1\0'
+    p = str(tmp_path / 't1_icbm_normal_1mm_pn0_rf0.nii.gz')
+    with gzip.open(p, 'wb') as f:
+        f.write(bytes(hdr) + b'\0\0\0\0' + vals.tobytes(order='F'))
     dat, dim, mat, *_ = _read_image(p)
     assert dim == (181, 217, 181)
     assert torch.allclose((mat[:3, :3] ** 2).sum(0).sqrt(), torch.ones(3, dtype=torch.float64))
+    assert torch.equal(mat[:3, 3], torch.tensor([-90.0, -126.0, -72.0], dtype=torch.float64))
+    assert dat.dtype == torch.float32 and torch.equal(dat, torch.from_numpy(vals.astype(np.float32)))
