@@ -86,6 +86,20 @@ int unires_abi_version(void);
 int unires_pull3d_affine(const float *src, const int32_t sdim[3], const float M[12], float *dst,
                          const int32_t gdim[3], float fov_tol, void *stream);
 
+/* The reference's _warp_label(label, affine_grid(M, gdim)) (unires/_core.py:419-436): for every
+ * distinct value u of label, ascending, p_u = the pull above of the indicator (label == u), and
+ * dst = u wherever p_u > the best so far (which starts at 0).  One gather per output voxel:
+ * ties go to the smallest value, a best of 0 gives 0, p_u has the bits of the pull's product
+ * form.  label holds any float32 values (the caller checks there are at most 255). */
+int unires_warp_label(const float *label, const int32_t ldim[3], const float M[12], float *dst,
+                      const int32_t gdim[3], float fov_tol, void *stream);
+
+/* nitorch grid_pull(src, affine_grid(M, gdim), 0, bound='zero', extrapolate=False)
+ * (unires/_core.py:484): src at the voxel rint(M g) (half-way cases to even) when that voxel is
+ * inside the volume and M g inside the FOV, else 0. */
+int unires_pull3d_nearest(const float *src, const int32_t sdim[3], const float M[12], float *dst,
+                          const int32_t gdim[3], float fov_tol, void *stream);
+
 /* nitorch grid_grad(src, affine_grid(M, gdim), 'linear', bound='zero', extrapolate=False)
  * (_update.py:508, the rigid Gauss-Newton's spatial derivatives): gradient of the trilinear
  * sample w.r.t. the voxel coordinate; dst3 is (gdim, 3), component fastest. */

@@ -92,6 +92,29 @@ def pull_affine(src, M, gdim, fov_tol=FOV_TOL):
 
 
 @on_device
+def pull_nearest(src, M, gdim, fov_tol=FOV_TOL):
+    """grid_pull(src, affine_grid(M, gdim), interpolation=0) - nearest neighbour (half-way cases to
+    even), zero bound, extrapolate=False."""
+    s, lead = _vol(src, 'src')
+    out = torch.empty(tuple(gdim), dtype=torch.float32, device=s.device)
+    check(_lib.load().unires_pull3d_nearest(_ptr(s), i3(s.shape), f12(M), _ptr(out), i3(gdim),
+                                            fov_tol, _stream()))
+    return out.reshape(lead + tuple(gdim))
+
+
+@on_device
+def warp_label(label, M, gdim, fov_tol=FOV_TOL):
+    """The reference's label vote in one pass: per output voxel, the value u of ``label`` whose
+    indicator (label == u) has the highest linear pull; ties go to the smallest value, a best of 0
+    gives 0.  ``label`` is float32 (the caller bounds the number of values)."""
+    s, lead = _vol(label, 'label')
+    out = torch.empty(tuple(gdim), dtype=torch.float32, device=s.device)
+    check(_lib.load().unires_warp_label(_ptr(s), i3(s.shape), f12(M), _ptr(out), i3(gdim),
+                                        fov_tol, _stream()))
+    return out.reshape(lead + tuple(gdim))
+
+
+@on_device
 def pull_grad_affine(src, M, gdim, fov_tol=FOV_TOL):
     """grid_grad(src, affine_grid(M, gdim)) -> (gdim, 3): spatial gradient of the trilinear sample."""
     s, lead = _vol(src, 'src')

@@ -1,4 +1,4 @@
-"""Image I/O of the drop-in: ``_read_image`` / ``_write_image`` with the contract of
+"""Image I/O of the drop-in: ``_read_image`` / ``_read_label`` / ``_write_image`` with the contract of
 unires/_util.py:134-226 (same arguments, same 8-tuple, same errors), on the package's own NIfTI-1
 codec (``nifti.py``) instead of nitorch.io."""
 import os
@@ -35,6 +35,17 @@ def _read_image(data, device='cpu', is_ct=False):
     if dat.dim() != 3:
         raise ValueError("Input image dimension required to be 3D, recieved {:}D!".format(dat.dim()))
     return dat, tuple(dat.shape), mat, fname, direc, nam, header, bool(is_ct)
+
+
+def _read_label(x, pth, sett):
+    """Reads a label volume for the observation ``x`` (unires/_util.py:200-212): float32 voxels on
+    ``sett.device``, shape checked against ``x.dim``; sets ``x.label = [dat, header]``."""
+    voxels, _, header = nifti.read(pth)
+    dat = torch.as_tensor(voxels).to(device=sett.device, dtype=torch.float32)
+    if tuple(dat.shape) != tuple(x.dim):
+        raise ValueError('Incorrect label dimensions.')
+    x.label = [dat, header]
+    return x
 
 
 def _bids_name(fname):

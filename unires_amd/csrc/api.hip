@@ -158,6 +158,29 @@ extern "C" int unires_pull3d_affine(const float *src, const int32_t sdim[3], con
   return UNIRES_OK;
 }
 
+extern "C" int unires_warp_label(const float *label, const int32_t ldim[3], const float M[12],
+                                 float *dst, const int32_t gdim[3], float fov_tol, void *stream) {
+  if (!label || !dst || !ldim || !gdim || !M) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(ldim) || !dims_ok(gdim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  Affine A;
+  memcpy(A.m, M, sizeof(A.m));
+  launch_warp_label(label, mk(ldim), A, dst, mk(gdim), fov_tol, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_pull3d_nearest(const float *src, const int32_t sdim[3], const float M[12],
+                                     float *dst, const int32_t gdim[3], float fov_tol,
+                                     void *stream) {
+  if (!src || !dst || !sdim || !gdim || !M) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(sdim) || !dims_ok(gdim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  Affine A;
+  memcpy(A.m, M, sizeof(A.m));
+  launch_pull_nearest(src, mk(sdim), A, dst, mk(gdim), fov_tol, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 extern "C" int unires_pull_grad3d_affine(const float *src, const int32_t sdim[3], const float M[12],
                                          float *dst3, const int32_t gdim[3], float fov_tol,
                                          void *stream) {

@@ -82,10 +82,12 @@ def _mat_shape(mat_or_grid, shape):
 
 
 def grid_pull(input, mat, shape=None, interpolation='linear', bound='zero', extrapolate=False):
-    """nitorch grid_pull(input, affine_grid(mat, shape), ...); ``mat`` may be that grid itself."""
-    _only_linear_zero(interpolation, bound, extrapolate)
+    """nitorch grid_pull(input, affine_grid(mat, shape), ...); ``mat`` may be that grid itself.
+    ``interpolation`` 0 / 'nearest' takes the nearest-neighbour pull (unires/_core.py:484)."""
+    nearest = _is_nearest(interpolation)
+    _only_linear_zero(1 if nearest else interpolation, bound, extrapolate)  # (bound / extrapolate as for order 1)
     m, shp = _mat_shape(mat, shape)
-    return _ops.pull_affine(input, _m12(m), shp)
+    return (_ops.pull_nearest if nearest else _ops.pull_affine)(input, _m12(m), shp)
 
 
 def grid_grad(input, mat, shape=None, interpolation='linear', bound='zero', extrapolate=False):
@@ -116,6 +118,10 @@ def im_gradient(dat, vx=None, which='forward', bound='zero'):
 def im_divergence(dat, vx=None, which='forward', bound='zero'):
     _only_forward_zero(which, bound)
     return _ops.div_fwd_zero(dat, vx)
+
+
+def _is_nearest(interpolation):
+    return not isinstance(interpolation, bool) and interpolation in (0, 'nearest')
 
 
 def _only_linear_zero(interpolation, bound, extrapolate):

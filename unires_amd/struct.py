@@ -18,6 +18,7 @@ class _input:
         self.mu = 1.0
         self.sd = 1.0
         self.rigid_q = None
+        self.label = None   # [dat, header] of a manual label volume (_util._read_label)
 
 
 class _output:
@@ -29,6 +30,7 @@ class _output:
         self.mat = mat
         self.lam = lam
         self.lam0 = lam
+        self.label = None   # labels warped into the output space (_core._init_y_label)
 
 
 class _proj_op:
@@ -102,3 +104,9 @@ class settings:
         self.host_pace = 2
         # build-side knob: keep sum_n tau_n At x_n across ADMM iterations (recomputed on change)
         self.cache_atx = True
+        # manual labels of one observation, (path, (channel, repeat)) (unires/struct.py:86)
+        self.label = None
+        # resample observations to voxels no smaller than vx before fitting (_core._resample_inplane)
+        self.force_inplane_res = False
+        # reconstruction voxel size: a scalar or one per axis (unires/struct.py:109)
+        self.vx = 1.0
