@@ -114,7 +114,7 @@ __device__ __forceinline__ unsigned s2_rowcode(const S2BuildArgs &B, int ui, int
 }
 
 // One wave per tile.  MODE 0: counts[t] = {entries, instructions}; MODE 1: counts holds the exclusive prefix
-// sums and the entries / masks are written where they belong (the two-pass build of rounds 2-4, kept as the
+// sums (of the instruction counts padded to whole batches) and the entries / masks / batch words are written where they belong (the two-pass build of rounds 2-4, kept as the
 // fallback); MODE 2 (round 5): ONE pass - counts[t] as in MODE 0 AND the tile's entries / masks into its staging
 // slot (kS2StageE entries, 64 masks per tile: entries, ext and masks point at the staging arrays), from where
 // k_splat2_compact moves them once the host has fixed the processing order.  A tile with more entries than a slot
@@ -124,7 +124,7 @@ template <int MODE>
 __global__ void __launch_bounds__(kWave)
     k_splat2_build(S2BuildArgs B, uint2 *__restrict__ counts, const int *__restrict__ geom,
                    S2Entry *__restrict__ entries, S2Ext *__restrict__ ext, ulonglong2 *__restrict__ masks,
-                   int *__restrict__ err, unsigned long long *__restrict__ stats) {
+                   unsigned *__restrict__ bwords, int *__restrict__ err, unsigned long long *__restrict__ stats) {
   using T = S2Tile;
   constexpr int L = T::L, kSegs = 384;
   __shared__ S2Seg segs[kSegs];
@@ -377,6 +377,26 @@ __global__ void __launch_bounds__(kWave)
     }
   }
   const uint2 base = MODE == 1 ? counts[slot] : make_uint2((unsigned)slot * (unsigned)kS2StageE, (unsigned)slot * 64u);
+  // The batch words (splat2.hpp): the ring slot of every instruction's first entry, and where the stream's segment ring
+  // moves on - the rule the stream used to apply at run time: before batch b it advances by one chunk if the batch
+  // reaches past the two chunks it holds.  Instructions past the tile's last (the padding) start at its end.
+  {
+    const int nb = (nbins + kS2Batch - 1) / kS2Batch;
+    const int fe = lane < nbins ? incl - nent : total_ent;
+    unsigned adv = 0u;
+    int chunk_lo = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int nx = kS2Batch * (b + 1);
+      const int need = nx < nbins ? __shfl(fe, nx, kWave) : total_ent;
+      if (need > 32 * (chunk_lo + 2)) adv |= 1u << b, ++chunk_lo;
+    }
+    unsigned w = 0u;
+#pragma unroll
+    for (int u = 0; u < kS2Batch; ++u) w |= ((unsigned)__shfl(fe, min(kS2Batch * lane + u, kWave - 1), kWave) & 63u) << (6 * u);
+    if (lane < nb) bwords[base.y / kS2Batch + lane] = w | (((adv >> lane) & 1u) ? kS2BatchAdv : 0u);
+    // padding: empty instructions
+    if (lane >= nbins && lane < kS2Batch * nb) masks[base.y + lane] = make_ulonglong2(0ull, 0ull);
+  }
   unsigned long long pts = 0;
   if (lane < nbins) {
     S2Entry *out = entries + base.x + (incl - nent);
@@ -433,8 +453,9 @@ __global__ void __launch_bounds__(kWave)
 __global__ void __launch_bounds__(kWave)
     k_splat2_compact(const uint2 *__restrict__ stage_cnt, const S2Entry *__restrict__ stage_e,
                      const S2Ext *__restrict__ stage_x, const ulonglong2 *__restrict__ stage_m,
-                     const int *__restrict__ geom, const uint2 *__restrict__ tile_off, S2Entry *__restrict__ entries,
-                     S2Ext *__restrict__ ext, ulonglong2 *__restrict__ masks) {
+                     const unsigned *__restrict__ stage_b, const int *__restrict__ geom, const uint2 *__restrict__ tile_off,
+                     S2Entry *__restrict__ entries, S2Ext *__restrict__ ext, ulonglong2 *__restrict__ masks,
+                     unsigned *__restrict__ bwords) {
   const int u = blockIdx.x, lane = threadIdx.x;
   const int t = geom[u];
   const uint2 c = stage_cnt[t], o = tile_off[u];
@@ -446,7 +467,9 @@ __global__ void __launch_bounds__(kWave)
     uint4 *dx = reinterpret_cast<uint4 *>(ext) + 2 * (size_t)o.x;
     for (unsigned i = lane; i < 2u * c.x; i += kWave) dx[i] = sx[i];
   }
-  if ((unsigned)lane < (c.y & 0xffu)) masks[o.y + lane] = stage_m[(size_t)t * 64 + lane];  // (.y: instructions | table base << 8)
+  const unsigned nb = ((c.y & 0xffu) + kS2Batch - 1) / kS2Batch;  // (.y: instructions | table base << 8)
+  if ((unsigned)lane < kS2Batch * nb) masks[o.y + lane] = stage_m[(size_t)t * 64 + lane];
+  if ((unsigned)lane < nb) bwords[o.y / kS2Batch + lane] = stage_b[(size_t)t * (64 / kS2Batch) + lane];
 }
 
 // Staging arrays of the single-pass build: one set per device, grown on demand, shared by every schedule built on it
@@ -456,6 +479,7 @@ struct S2Stage {
   S2Entry *e = nullptr;
   S2Ext *x = nullptr;
   ulonglong2 *m = nullptr;
+  unsigned *b = nullptr;  // 64 / kS2Batch batch words per tile
   size_t tiles = 0, tiles_x = 0;
 };
 static std::mutex g_stage_mu;
@@ -464,7 +488,8 @@ static std::map<int, S2Stage> g_stage;
 static S2Stage *s2_stage(int nt, bool want_ext) {  // (call with g_stage_mu held) nullptr: use the two-pass build
   static const bool two_pass = getenv("UNIRES_S2_BUILD_2PASS") != nullptr;
   if (two_pass) return nullptr;
-  const size_t bytes = (size_t)nt * (kS2StageE * (sizeof(S2Entry) + (want_ext ? sizeof(S2Ext) : 0)) + 64 * sizeof(ulonglong2));
+  const size_t bytes = (size_t)nt * (kS2StageE * (sizeof(S2Entry) + (want_ext ? sizeof(S2Ext) : 0)) + 64 * sizeof(ulonglong2) +
+                                     (64 / kS2Batch) * sizeof(unsigned));
   if (bytes > (512ull << 20)) return nullptr;  // (a 1 000^3 volume: two passes rather than half a gigabyte of staging)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -473,16 +498,19 @@ static S2Stage *s2_stage(int nt, bool want_ext) {  // (call with g_stage_mu held
     if (G.cnt) (void)hipFree(G.cnt);
     if (G.e) (void)hipFree(G.e);
     if (G.m) (void)hipFree(G.m);
-    G.cnt = nullptr, G.e = nullptr, G.m = nullptr, G.tiles = 0;
+    if (G.b) (void)hipFree(G.b);
+    G.cnt = nullptr, G.e = nullptr, G.m = nullptr, G.b = nullptr, G.tiles = 0;
     const size_t n = (size_t)nt + nt / 8;
     if (hipMalloc((void **)&G.cnt, n * sizeof(uint2)) != hipSuccess ||
         hipMalloc((void **)&G.e, n * kS2StageE * sizeof(S2Entry)) != hipSuccess ||
-        hipMalloc((void **)&G.m, n * 64 * sizeof(ulonglong2)) != hipSuccess) {
+        hipMalloc((void **)&G.m, n * 64 * sizeof(ulonglong2)) != hipSuccess ||
+        hipMalloc((void **)&G.b, n * (64 / kS2Batch) * sizeof(unsigned)) != hipSuccess) {
       (void)hipGetLastError();
       if (G.cnt) (void)hipFree(G.cnt);
       if (G.e) (void)hipFree(G.e);
       if (G.m) (void)hipFree(G.m);
-      G.cnt = nullptr, G.e = nullptr, G.m = nullptr;
+      if (G.b) (void)hipFree(G.b);
+      G.cnt = nullptr, G.e = nullptr, G.m = nullptr, G.b = nullptr;
       return nullptr;
     }
     G.tiles = n;
@@ -509,6 +537,7 @@ void splat2_free(SplatSched &S) {
   if (S.entries) (void)hipFree(S.entries);
   if (S.ext) (void)hipFree(S.ext);
   if (S.masks) (void)hipFree(S.masks);
+  if (S.bwords) (void)hipFree(S.bwords);
   if (S.tile_off) (void)hipFree(S.tile_off);
   if (S.tile_geom) (void)hipFree(S.tile_geom);
   if (S.recs) (void)hipFree(S.recs);
@@ -561,7 +590,7 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
   std::vector<uint2> cnt((size_t)nt), h((size_t)nt + 1);
   if (stage) {
     hipLaunchKernelGGL(k_splat2_build<2>, dim3(nt), dim3(kWave), 0, 0, B, stage->cnt, (const int *)nullptr, stage->e,
-                       axis == 3 ? stage->x : (S2Ext *)nullptr, stage->m, err_dev, stats_dev);
+                       axis == 3 ? stage->x : (S2Ext *)nullptr, stage->m, stage->b, err_dev, stats_dev);
     int e0 = 0;
     if (hipMemcpy(cnt.data(), stage->cnt, (size_t)nt * sizeof(uint2), hipMemcpyDeviceToHost) != hipSuccess) return 1;
     if (hipMemcpy(&e0, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
@@ -572,7 +601,7 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
     }
   } else {
     hipLaunchKernelGGL(k_splat2_build<0>, dim3(nt), dim3(kWave), 0, 0, B, S.tile_off, (const int *)nullptr,
-                       (S2Entry *)nullptr, (S2Ext *)nullptr, (ulonglong2 *)nullptr, err_dev,
+                       (S2Entry *)nullptr, (S2Ext *)nullptr, (ulonglong2 *)nullptr, (unsigned *)nullptr, err_dev,
                        (unsigned long long *)nullptr);
     if (hipMemcpy(cnt.data(), S.tile_off, (size_t)nt * sizeof(uint2), hipMemcpyDeviceToHost) != hipSuccess)
       return 1;
@@ -676,10 +705,11 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
       if (g < 0) continue;
       const uint2 cg = cnt[g];
       const unsigned tzi = (unsigned)(g % ntz), tyi = (unsigned)((g / ntz) % nty), txi = (unsigned)(g / (ntz * nty));
+      const unsigned npad = (cg.y + kS2Batch - 1) / kS2Batch * kS2Batch;  // (whole batches: empty instructions)
       recs[pp] = make_uint4(txi | (tyi << 10) | (tzi << 20), re, ri, cg.y | ((unsigned)kbv[g] << 8));
       geom[u] = g;
       h[u] = make_uint2(re, ri);
-      re += cg.x, ri += cg.y;
+      re += cg.x, ri += npad;
       ++u;
     }
     if (u != nt) return 1;  // (every tile exactly once)
@@ -707,6 +737,13 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
     if (hipMalloc((void **)&S.masks, cap * sizeof(ulonglong2)) != hipSuccess) return 1;
     S.cap_instr = cap;
   }
+  if ((size_t)ri / kS2Batch + 8 > S.cap_batches) {
+    if (S.bwords) (void)hipFree(S.bwords);
+    S.bwords = nullptr;
+    const size_t cap = (size_t)ri / kS2Batch + ri / (8 * kS2Batch) + 8;
+    if (hipMalloc((void **)&S.bwords, cap * sizeof(unsigned)) != hipSuccess) return 1;
+    S.cap_batches = cap;
+  }
   if (hipMemcpy(S.tile_off, h.data(), ((size_t)nt + 1) * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)
     return 1;
   if (hipMemcpy(S.tile_geom, geom.data(), ((size_t)nt + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
@@ -721,13 +758,15 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
   if (hipMemcpy(S.recs, recs.data(), recs.size() * sizeof(uint4), hipMemcpyHostToDevice) != hipSuccess) return 1;
   (void)hipMemset(S.entries + re, 0xff, kPad * sizeof(S2Entry));
   (void)hipMemset(S.masks + ri, 0, 8 * sizeof(ulonglong2));
+  (void)hipMemset(S.bwords + ri / kS2Batch, 0, 8 * sizeof(unsigned));
   if (stage)
     hipLaunchKernelGGL(k_splat2_compact, dim3(nt), dim3(kWave), 0, 0, (const uint2 *)stage->cnt, (const S2Entry *)stage->e,
                        axis == 3 ? (const S2Ext *)stage->x : (const S2Ext *)nullptr, (const ulonglong2 *)stage->m,
-                       (const int *)S.tile_geom, (const uint2 *)S.tile_off, S.entries, S.ext, S.masks);
+                       (const unsigned *)stage->b, (const int *)S.tile_geom, (const uint2 *)S.tile_off, S.entries, S.ext,
+                       S.masks, S.bwords);
   else
     hipLaunchKernelGGL(k_splat2_build<1>, dim3(nt), dim3(kWave), 0, 0, B, S.tile_off, (const int *)S.tile_geom,
-                       S.entries, S.ext, S.masks, err_dev, stats_dev);
+                       S.entries, S.ext, S.masks, S.bwords, err_dev, stats_dev);
   int herr = 0;
   unsigned long long hs[2] = {0, 0};
   if (hipMemcpy(&herr, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
@@ -784,6 +823,7 @@ struct S2Args {
   const S2Ext *ext;      // AXIS 3
   unsigned xs_sy4, xs_sx4;  // AXIS 3: bytes between x-space rows / slabs
   const ulonglong2 *masks;  // per instruction: {segment starts, active lanes}
+  const unsigned *bwords;   // per batch of kS2Batch instructions: ring slots, ring advance (splat2.hpp)
   const uint4 *recs;     // per position of the walk: {tile, entry offset, instruction offset, instructions | table base << 8}
   int ntiles;
   Affine A;
@@ -909,16 +949,19 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
   // the slice - no register carried through the epilogue); the masks' load is issued AFTER them, so that the wait
   // the compiler puts in front of the masks' first use covers both (loads return in order).
   ulonglong2 h_mk = make_ulonglong2(0ull, 0ull);
+  unsigned h_bw = 0u;
   struct Hdr {  // what a header request wants of the kernel arguments
     const S2Entry *entries;
     size_t ent_bytes;
     const float4 *tab;
     int gn;
     const ulonglong2 *masks;
+    const unsigned *bwords;
   };
-  auto load_hdr = [&](KArgs K) { return Hdr{K->entries, K->ent_bytes, K->tab, K->gn, K->masks}; };
+  auto load_hdr = [&](KArgs K) { return Hdr{K->entries, K->ent_bytes, K->tab, K->gn, K->masks, K->bwords}; };
   auto issue_header = [&](const Hdr &H, const u4v &rc, int ln) {
     const int ni = (int)(rc.w & 0xffu);
+    const int np = AXIS == 2 ? (ni + kS2Batch - 1) / kS2Batch * kS2Batch : ni;  // (AXIS 2 streams the padding too)
     const int gn = H.gn;
     const __amdgpu_buffer_rsrc_t rs_ent = make_rsrc(H.entries, H.ent_bytes);
     S2_FENCE();
@@ -932,8 +975,8 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     S2_FENCE();
     // (every lane loads - lanes past the tile's last instruction read the zero padding or a later tile's masks, never
     // used: an unconditional load is always issued, and the wait on it is what orders the DMA above)
-    h_mk = H.masks[rc.z + (unsigned)min(ln, max(ni - 1, 0))];
-    (void)ni;
+    h_mk = H.masks[rc.z + (unsigned)min(ln, max(np - 1, 0))];
+    if (AXIS == 2) h_bw = H.bwords[rc.z / (unsigned)kS2Batch + (unsigned)min(ln, max(np / kS2Batch - 1, 0))];
   };
   if (rec.x != 0xffffffffu) issue_header(load_hdr(kargs()), rec, lane);
   for (; rec.x != 0xffffffffu; ++round) {
@@ -947,20 +990,25 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     }
     const int x0 = (int)(rec.x & 1023u) * TX, y0 = (int)((rec.x >> 10) & 1023u) * TY, z0 = (int)(rec.x >> 20) * T::TZ;
     const int ex = min(TX, dd.x - x0), ey = min(TY, dd.y - y0), ez = min(T::TZ, dd.z - z0);
-    const int ninstr = (int)(rec.w & 0xffu);
+    // (AXIS 2: whole batches, the build's empty instructions included)
+    const int ninstr = AXIS == 2 ? ((int)(rec.w & 0xffu) + kS2Batch - 1) / kS2Batch * kS2Batch : (int)(rec.w & 0xffu);
     const int tab_base = (int)(rec.w >> 8);
     const unsigned ent0 = rec.y;
     const uint4 *E = reinterpret_cast<const uint4 *>(P.entries) + ent0;  // (used through the stream: stays in registers)
     const int t_next = t + slots;
     const u4v rec_next = t_next < t_hi ? recs[t_next] : rec_none;
-    // lane l keeps the segment-start mask of instruction l (a tile has at most 64 of them)
+    // lane l keeps the masks of instruction l (a tile has at most 64 of them) and the word of batch l
     int lp = lane;  // (laundered per tile, as in the epilogue: the prologue's addresses are not held through the stream)
     asm volatile("" : "+v"(lp));
     const ulonglong2 mymask = h_mk;
     const int mlo_v = (int)(unsigned)mymask.x, mhi_v = (int)(unsigned)(mymask.x >> 32);
     const int alo_v = (int)(unsigned)mymask.y, ahi_v = (int)(unsigned)(mymask.y >> 32);
-    // the masks are here => so are the ring's chunks 0 and 1 and the table slice (issued before them)
-    asm volatile("" ::"v"(mlo_v), "v"(mhi_v), "v"(alo_v), "v"(ahi_v) : "memory");
+    const int bw_v = (int)h_bw;
+    // the batch words (AXIS 2) / the masks are here => so are the ring's chunks 0 and 1 and the table slice (issued before them)
+    if (AXIS == 2)
+      asm volatile("" ::"v"(mlo_v), "v"(mhi_v), "v"(alo_v), "v"(ahi_v), "v"(bw_v) : "memory");
+    else
+      asm volatile("" ::"v"(mlo_v), "v"(mhi_v), "v"(alo_v), "v"(ahi_v) : "memory");
     // segment ring: chunk 2 in flight in registers
     uint4 pre = make_uint4(0u, 0u, 0u, 0u);
     if (lp < 32) pre = E[64 + lp];
@@ -1001,38 +1049,24 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     unsigned acc_addr = (unsigned)(__UINTPTR_TYPE__)(LdsF1)(void *)acc - 4u * (unsigned)(((x0 - 1) * SY + (y0 - 1)) * SZ + (z0 - 1));
     asm volatile("" : "+s"(acc_addr));
     int chunk_lo = 0;  // the ring holds chunks chunk_lo and chunk_lo + 1 (32 entries each)
-    int eb = 0;        // first entry of the next instruction, relative to the tile
+    int eb = 0;        // (running decode, AXIS != 2) first entry of the next instruction, relative to the tile
     S2_FENCE();
-    constexpr int kU = 4;
+    constexpr int kU = kS2Batch;
     // (Tried and dropped: a schedule whose groups of 2 / 4 consecutive instructions are mutually
     // conflict-free, so that their LDS updates run as two rounds with all reads of a round in
     // flight - the extra packing constraint costs lane fill (0.75 -> 0.65 / 0.40) and the round form
     // 20-30 more VGPRs (occupancy 4 -> 3 waves per SIMD): 155 us instead of 88 us.)
-    // A batch = kU instructions.  fetch(): segment-start masks -> mbcnt -> segment entry (LDS ring)
-    // -> conv_up table -> ONE source load per lane and instruction, all issued back to back;
-    // splat(): coordinates, weights and the two LDS update groups.  Two batches are in flight: the
-    // source loads of batch b + 1 travel while batch b is splatted.
+    // A batch = kU instructions (the build pads a tile to whole batches with empty instructions).  Its word (splat2.hpp)
+    // says where each instruction's entries start in the ring and whether the ring moves on first: advance(), then
+    // fetch(): segment-start masks -> mbcnt -> segment entry (LDS ring) -> conv_up table -> ONE source load per lane and
+    // instruction, all issued back to back; splat(): coordinates, weights and the two LDS update groups.  Two batches
+    // are in flight: the source loads of batch b + 1 travel while batch b is splatted.
     struct Batch {
       float w0[kU], w1[kU], s0[kU], s1[kU], gx[kU], gy[kU], gz[kU];  // (coordinates, not their four ingredients: a register less per slot)
       unsigned long long amask[kU];
     };
-    auto fetch = [&](Batch &Bt, int p0) {
-      unsigned mlo[kU], mhi[kU];
-      int ebu[kU];
-      int need = eb;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        // (a batch slot past the tile's last instruction replays that instruction, switched off)
-        const int pi = min(p0 + u, ninstr - 1);
-        mlo[u] = (unsigned)__builtin_amdgcn_readlane(mlo_v, pi);
-        mhi[u] = (unsigned)__builtin_amdgcn_readlane(mhi_v, pi);
-        Bt.amask[u] = p0 + u < ninstr ? ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(ahi_v, pi) << 32) |
-                                            (unsigned)__builtin_amdgcn_readlane(alo_v, pi)
-                                      : 0ull;
-        ebu[u] = (p0 + u < ninstr || u == 0) ? need : ebu[u > 0 ? u - 1 : 0];
-        if (p0 + u < ninstr) need += __popc(mlo[u]) + __popc(mhi[u]) + 1;
-      }
-      if (need > 32 * (chunk_lo + 2)) {  // advance the ring by one chunk (the oldest one is dead)
+    auto advance = [&](unsigned bw) {
+      if (bw & kS2BatchAdv) {  // advance the ring by one chunk (the oldest one is dead)
         S2_FENCE();
         if (lane < 32) ring[(chunk_lo & 1) * 32 + lane] = pre;
         if (AXIS == 3) ring2[(chunk_lo & 1) * 64 + lane] = pre2;
@@ -1043,11 +1077,11 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
         if (AXIS == 3) pre2 = X[64 * (chunk_lo + 2) + lane];
         S2_FENCE();
       }
-      eb = need;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int sl = (int)__builtin_amdgcn_mbcnt_hi(mhi[u], __builtin_amdgcn_mbcnt_lo(mlo[u], 0u));
-        const u4r e = *(LdsU4)(__UINTPTR_TYPE__)((((unsigned)(ebu[u] + sl) << 4) & m3f0) | ring_b);
+    };
+    // slot u of a batch from ring slot `sl` (mod 64) of the lane's segment entry: entry -> conv_up table -> source load
+    auto load = [&](Batch &Bt, int u, int sl) {
+      {
+        const u4r e = *(LdsU4)(__UINTPTR_TYPE__)((((unsigned)sl << 4) & m3f0) | ring_b);
         const float rx = __uint_as_float(e.x), ry = __uint_as_float(e.y), rz = __uint_as_float(e.z);
         float kf;
         const unsigned code = e.w & kS2RowIdle;
@@ -1060,7 +1094,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
         if (S2_ABL(8)) {
         } else if (AXIS == 3) {
           // conv_up along x, y and z: 2 x 2 x-space columns (per segment) x the z pair (per lane)
-          const uint4 xa = ring2[2 * ((ebu[u] + sl) & 63)], xb = ring2[2 * ((ebu[u] + sl) & 63) + 1];
+          const uint4 xa = ring2[2 * (sl & 63)], xb = ring2[2 * (sl & 63) + 1];
           const f4r tb = *(LdsF4)(__UINTPTR_TYPE__)((((unsigned)k << 4) & m3f0) | tabs_b);
           const unsigned a = xa.x + (unsigned)__float_as_int(tb.y);
           const uint2 p00 = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, a, 0, 0));
@@ -1109,10 +1143,46 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
         Bt.gz[u] = fmaf(c2, kf, rz) + t2;
       }
     };
+    // AXIS 2: the batch word's ring slots
+    auto fetch = [&](Batch &Bt, int p0, unsigned bw) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int pi = p0 + u;
+        const unsigned mlo = (unsigned)__builtin_amdgcn_readlane(mlo_v, pi), mhi = (unsigned)__builtin_amdgcn_readlane(mhi_v, pi);
+        Bt.amask[u] = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(ahi_v, pi) << 32) |
+                      (unsigned)__builtin_amdgcn_readlane(alo_v, pi);
+        // ring slot of the lane's entry: the instruction's first slot (the batch word) + segments started below the lane
+        // (added after mbcnt, not as its accumulator: a second scalar operand of one VOP3 costs a move on gfx9)
+        load(Bt, u, (int)((bw >> (6 * u)) & 63u) + (int)__builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u)));
+      }
+    };
+    // the other forms: a running count of the segments, slots past the tile's last instruction replay it switched off
+    auto fetch_run = [&](Batch &Bt, int p0) {
+      unsigned mlo[kU], mhi[kU];
+      int ebu[kU];
+      int need = eb;
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int pi = min(p0 + u, ninstr - 1);
+        mlo[u] = (unsigned)__builtin_amdgcn_readlane(mlo_v, pi);
+        mhi[u] = (unsigned)__builtin_amdgcn_readlane(mhi_v, pi);
+        Bt.amask[u] = p0 + u < ninstr ? ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(ahi_v, pi) << 32) |
+                                            (unsigned)__builtin_amdgcn_readlane(alo_v, pi)
+                                      : 0ull;
+        ebu[u] = (p0 + u < ninstr || u == 0) ? need : ebu[u > 0 ? u - 1 : 0];
+        if (p0 + u < ninstr) need += __popc(mlo[u]) + __popc(mhi[u]) + 1;
+      }
+      advance(need > 32 * (chunk_lo + 2) ? kS2BatchAdv : 0u);
+      eb = need;
+#pragma unroll
+      for (int u = 0; u < kU; ++u)
+        load(Bt, u, ebu[u] + (int)__builtin_amdgcn_mbcnt_hi(mhi[u], __builtin_amdgcn_mbcnt_lo(mlo[u], 0u)));
+    };
     // (Tried and dropped: the four weight products and the eight accumulate FMAs as v_pk_mul_f32 /
     // v_pk_fma_f32 on the (y, y + 1) pairs the ds_read2 / ds_write2 carry - 6 VALU instructions less
     // per splat instruction, 129 VGPRs (128 when forced), and 79-83 us where this form has 76-83.)
-    auto splat = [&](const Batch &Bt) {
+    auto splat = [&](const Batch &Bt, auto second_tag) {
+      constexpr bool SECOND = decltype(second_tag)::value;  // bb, the second batch of the loop
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const float gx = Bt.gx[u], gy = Bt.gy[u], gz = Bt.gz[u];
@@ -1138,7 +1208,17 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
         // cell index in float (exact: integers below 2^24), one conversion
         const float cf = fmaf(fx, (float)XS, fmaf(fy, (float)YS, fz));
         const int cell = (int)cf;
-        const float v = Bt.w0[u] * Bt.s0[u] + Bt.w1[u] * Bt.s1[u];
+        // (AXIS 0 / 1 / 2: the contraction spelled out, as the previous form of this kernel was compiled - slot 0 of the
+        // first batch and every slot of the second one fma(w1, s1, w0 s0), slots 1 - 3 of the first fma(w0, s0, w1 s1) -
+        // so that results stay bit-identical; left to itself the compiler picks per slot, and picked differently.  For
+        // AXIS -1 / 3 one of the two products is 0 x 0 and the order does not matter.)
+        float v;
+        if (AXIS < 0 || AXIS == 3)
+          v = Bt.w0[u] * Bt.s0[u] + Bt.w1[u] * Bt.s1[u];
+        else if (!SECOND && u > 0)
+          v = fmaf(Bt.w0[u], Bt.s0[u], Bt.w1[u] * Bt.s1[u]);
+        else
+          v = fmaf(Bt.w1[u], Bt.s1[u], Bt.w0[u] * Bt.s0[u]);
         const v2f vx = (v2f){v, v} * wx;                 // {vx0, vx1}
         const v2f a0 = (v2f){vx.x, vx.x} * wy, a1 = (v2f){vx.y, vx.y} * wy;  // {a00, a01}, {a10, a11}
         S2_FENCE();
@@ -1200,14 +1280,23 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
       // order: ends bunch up, 64 .. 80 us, but the ticket in front of the epilogue's loads costs each
       // epilogue 1 us), a staggered start of half the waves and a prefetch of the next tile's schedule.)
       Batch ba, bb;
-      fetch(ba, 0);
+      auto step = [&](Batch &Bt, int p0) {
+        if (AXIS == 2) {
+          const unsigned bw = (unsigned)__builtin_amdgcn_readlane(bw_v, p0 / kU);
+          advance(bw);
+          fetch(Bt, p0, bw);
+        } else {
+          fetch_run(Bt, p0);
+        }
+      };
+      step(ba, 0);
       for (int p0 = 0; p0 < ninstr; p0 += 2 * kU) {
         const bool more = p0 + kU < ninstr;
-        if (more) fetch(bb, p0 + kU);
-        splat(ba);
+        if (more) step(bb, p0 + kU);
+        splat(ba, std::false_type{});
         if (more) {
-          if (p0 + 2 * kU < ninstr) fetch(ba, p0 + 2 * kU);
-          splat(bb);
+          if (p0 + 2 * kU < ninstr) step(ba, p0 + 2 * kU);
+          splat(bb, std::true_type{});
         }
       }
     }
@@ -1226,7 +1315,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     const float *objb = OBJK ? K->objb : nullptr;
     const int accumulate = K->accumulate;
     const float kcx = K->cx, kcy = K->cy, kcz = K->cz, ka0 = K->a0;
-    asm volatile("" ::"s"(H.entries), "s"(H.ent_bytes), "s"(H.tab), "s"(H.gn), "s"(H.masks), "s"(pin), "s"(dst), "s"(objb),
+    asm volatile("" ::"s"(H.entries), "s"(H.ent_bytes), "s"(H.tab), "s"(H.gn), "s"(H.masks), "s"(H.bwords), "s"(pin), "s"(dst), "s"(objb),
                  "s"(accumulate), "s"(kcx), "s"(kcy), "s"(kcz), "s"(ka0));
     {
       // (the ring's chunk in flight may never have been used: let it land NOW, or the compiler waits for everything -
@@ -1414,7 +1503,7 @@ int launch_splat2(const SplatSched &S, const float *src, size_t src_numel, const
                   unsigned row_stride, unsigned tab_step, unsigned xs_sy, unsigned xs_sx, const Affine &A,
                   float alpha,
                   const PushEpilogue &ep, float *dst, Dim3i dd, const int *done, hipStream_t st) {
-  if (!S.valid || S.ntiles != s2_ntiles(dd) || !S.recs) return 1;
+  if (!S.valid || S.ntiles != s2_ntiles(dd) || !S.recs || !S.bwords) return 1;
   if (S.axis >= 0 && (!tab_dev || gn < 1)) return 1;
   if (S.axis == 3 && !S.ext) return 1;
   if (src_numel >= (1ull << 30)) return 1;  // 32-bit byte offsets into the source
@@ -1424,7 +1513,7 @@ int launch_splat2(const SplatSched &S, const float *src, size_t src_numel, const
   P.src_bytes = src_numel * sizeof(float);  // buffer range check: idle lanes may point anywhere
   P.tab = tab_dev, P.gn = gn;
   P.row_stride4 = 4u * row_stride, P.tab_step4 = 4u * tab_step;
-  P.entries = S.entries, P.ent_bytes = S.cap_entries * sizeof(S2Entry), P.ext = S.ext, P.xs_sy4 = 4u * xs_sy, P.xs_sx4 = 4u * xs_sx, P.masks = S.masks, P.recs = S.recs, P.ntiles = S.ntiles;
+  P.entries = S.entries, P.ent_bytes = S.cap_entries * sizeof(S2Entry), P.ext = S.ext, P.xs_sy4 = 4u * xs_sy, P.xs_sx4 = 4u * xs_sx, P.masks = S.masks, P.bwords = S.bwords, P.recs = S.recs, P.ntiles = S.ntiles;
   P.A = A, P.alpha = alpha;
   P.p = ep.p, P.a0 = ep.a0, P.cx = ep.cx, P.cy = ep.cy, P.cz = ep.cz;
   P.dst = dst, P.dd = dd, P.accumulate = ep.accumulate, P.partials = ep.partials, P.objb = ep.objb;

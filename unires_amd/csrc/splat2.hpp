@@ -19,6 +19,12 @@
 namespace unires {
 
 constexpr unsigned kS2RowBits = 19, kS2RowIdle = (1u << kS2RowBits) - 1u;
+// The stream runs a tile's instructions in batches of kS2Batch; the build pads every tile's instruction count to a
+// multiple of it with empty instructions (no segment starts, no active lane).  One 32-bit word per batch: bits
+// [6 u, 6 u + 6) = the ring slot (first entry mod 64) of instruction u of the batch, kS2BatchAdv = the segment ring
+// advances by one chunk before the batch.
+constexpr int kS2Batch = 4;
+constexpr unsigned kS2BatchAdv = 1u << 24;
 
 struct S2Entry {     // one segment of an instruction (16 bytes)
   float rx, ry, rz;  // affine_row(A, ui, uj): the row part of the coordinate arithmetic
@@ -35,16 +41,17 @@ struct SplatSched {
   S2Entry *entries = nullptr;            // device
   S2Ext *ext = nullptr;                  // device, axis 3 only (same indexing as entries)
   ulonglong2 *masks = nullptr;           // device, per instruction: {bit l-1 set <=> a segment starts at lane l, active lanes}
+  unsigned *bwords = nullptr;            // device, per batch of kS2Batch instructions (instruction offset / kS2Batch)
   uint2 *tile_off = nullptr;             // device, ntiles + 1 {entry offset, instruction offset}, in PROCESSING order (build kernels)
   int *tile_geom = nullptr;              // device, ntiles: the output tile of processing slot u (build kernels)
   // device, one 16-byte record per position of the walk (splat2_build (4)): {tile index x | y << 10 | z << 20,
-  // entry offset, instruction offset, instructions | conv_up table base << 8}
+  // entry offset, instruction offset (tiles padded to whole batches), instructions | conv_up table base << 8}
   uint4 *recs = nullptr;
   size_t cap_recs = 0;
   int pos_lo[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // position range of each partition (XCD): contiguous tiles of equal COST
   int nwg = 0;                            // workgroups the layout was made for (the launch must use as many)
   unsigned long long *scratch = nullptr; // device: {error flag, points, instructions} of a build
-  size_t cap_entries = 0, cap_instr = 0, cap_tiles = 0;
+  size_t cap_entries = 0, cap_instr = 0, cap_tiles = 0, cap_batches = 0;
   int ntiles = 0;
   bool valid = false;
   int axis = -1;      // -1 direct source; 0..2 conv_up along that axis; 3 along all three
