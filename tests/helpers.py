@@ -70,7 +70,7 @@ def fov_margin(po, method):
 
 def make_problem(dim_y=(16, 14, 12), n_channels=1, thick=3, seed=0, scl=0.0, regime='sr',
                  n_repeats=1, vx_y=1.0, rot=0.05, trans=0.7, noise_sd=20.0, prof_tp=0,
-                 prof_ip=0, thick_axes=None, aniso=None, iso=False, orient=None):
+                 prof_ip=0, thick_axes=None, aniso=None, iso=False, orient=None, angles=None, shift=None):
     """A synthetic multi-channel y-update problem.
 
     regime 'sr': thick-slice observations (ratio ``thick`` along a per-channel axis),
@@ -78,6 +78,8 @@ def make_problem(dim_y=(16, 14, 12), n_channels=1, thick=3, seed=0, scl=0.0, reg
     'id': do_proj False (A = I).
     ``orient``: per (channel, repeat) index c * n_repeats + n (cycled), a (perm, flip) pair: the
     observation is stored with its voxel axes permuted / reversed (``orient_axes``).
+    ``angles``: the rigid's rotations about x, y, z (rad) instead of random ones (the translation stays random);
+    ``shift``: a rigid that is exactly this translation (mm), no rotation.
     """
     def stored(c, n, dim, mat):
         if orient is None:
@@ -97,7 +99,10 @@ def make_problem(dim_y=(16, 14, 12), n_channels=1, thick=3, seed=0, scl=0.0, reg
         for n in range(n_repeats):
             for _attempt in range(20):
                 u = torch.rand(6, generator=gen) * 2 - 1
-                rigid = rigid_matrix((u[:3] * trans).tolist(), (u[3:] * rot).tolist())
+                r_ = list(angles) if angles is not None else (u[3:] * rot).tolist()
+                rigid = rigid_matrix((u[:3] * trans).tolist(), r_)
+                if shift is not None:
+                    rigid = rigid_matrix(list(shift), (0.0, 0.0, 0.0))
                 if regime == 'id':
                     break
                 if regime == 'sr':
@@ -265,17 +270,29 @@ def fov_tie_voxels(wl, P, eps=1e-4, reach=2):
     reference's mask is discontinuous there: which side a float32 coordinate falls on depends on
     the last-ulp rounding of the coordinate arithmetic (torch-CPU matmul vs FMA chain), so the
     matvec legitimately differs by one grid point's worth in these voxels."""
-    from oracle import nitorch_restated as N
-    from oracle import unires_restated as O
     regime = wl.get('regime', 'sr')
     method = 'super-resolution' if regime == 'sr' else 'denoising'
-    mat, dim = O.proj_matrix(P['po'], method)
+    return fov_tie_mask(P['po'], method, tuple(P['b'].shape), eps=eps, reach=reach)
+
+
+def fov_near_points(po, method, dim_y, eps):
+    """(grid, near): the reference's float32 grid and the grid points whose coordinate lies within ``eps`` of one
+    of the +-5e-2 in-FOV thresholds of ``dim_y``.  ``eps`` is a parameter: the coordinate rounding it has to cover
+    grows with the coordinates' magnitude (tests/ref64.py passes twice its largest per-point coordinate bound)."""
+    from oracle import nitorch_restated as N
+    mat, dim = O.proj_matrix(po, method)
     g = N.affine_grid(mat.float(), dim)
-    dim_y = tuple(P['b'].shape)
     near = torch.zeros(g.shape[:3], dtype=torch.bool)
     for d, n in enumerate(dim_y):
         for thr in (-5e-2, n - 1 + 5e-2):
             near |= (g[..., d] - thr).abs() < eps
+    return g, near
+
+
+def fov_tie_mask(po, method, dim_y, eps=1e-4, reach=2):
+    """(mask over ``dim_y``, number of near grid points): the output voxels a grid point within ``eps`` of an
+    in-FOV threshold can reach (``reach`` voxels on either side of its floor)."""
+    g, near = fov_near_points(po, method, dim_y, eps)
     pts = g[near]
     bad = torch.zeros(dim_y, dtype=torch.bool)
     for pt in pts:

@@ -1,0 +1,432 @@
+"""Every operator form the plan can select, per voxel, against the float64 reference of tests/ref64.py.
+
+For each case a fresh child process (env switches are read once per process) builds the case's plan, reports the
+form through ``plan.repeat_info`` (and, with UNIRES_SPLAT2_VERBOSE=1, which schedule build ran), and writes A p,
+At v, AtA p, the matvec q with its float64 dot epilogue, and A / At / AtA of impulse combs to an .npz file.  The
+parent checks every voxel against |out - ref| <= u c_M M + G + D (ref64) away from FOV ties, the float64 adjoint
+identity and the dot against the same tolerances, and that the case ran on its form.  One child at a time, each
+under a timeout; the first child that fails or dies ends the test; no retries.
+
+Impulse combs put deltas (random values) at the volume's corners, at the first and last voxel of each axis' last,
+partial tile (k_splat2 / k_ata1 tiles: 8 x 4 x 30) and of its first tile, and in the middle - in two combs, so
+that the deltas of one comb lie further apart than the operator's footprint (2 (3 r + 4) + 1 voxels along an axis
+of ratio r in y space, 8 voxels in x space) and each column / row is seen on its own.  In y space they give the
+columns of A and AtA, in x space (the x volume's corners, ends and middle) the rows of A, through At.  They are
+compared against the reference built with the taps the plan uses (``trimmed=True``), so D = 0 and a forward and an
+adjoint that disagree on a tap or on the footprint show.
+
+Case table (repeat_info: pull2 / splat2_axis / shift / fused / separable).  Where repeat_info cannot tell forms
+apart, the kernels the env switch selects are named; the case then checks that the switch took effect where
+repeat_info can show it, and relies on the switch otherwise:
+
+| case               | geometry                                        | env                | form                                |
+|--------------------|-------------------------------------------------|--------------------|-------------------------------------|
+| z_thick            | 97x90x121, thick 6 along z, rot 0.12, scl 0.1   |                    | pull2 + splat2 AXIS 2               |
+| z_thick_conc3      | the same, after plan.set_concurrency(3)         |                    | pull2 + splat2 AXIS 2               |
+| x_thick, y_thick   | 41x38x61, thick 4 along x / y                   |                    | pull2 + AXIS 0 / AXIS 1             |
+| iso2_rect          | 42x38x61 (x-space z 30), ratio 2, scl 0.1       |                    | hybrid: pull2 + AXIS 2, not sep.    |
+| iso2_rect_z4       | 42x38x64 (x-space z 32, a multiple of 4)        |                    | hybrid: pull2 + AXIS 2, not sep.    |
+| iso2_rect_nohyb    | 42x38x61, scl 0 (AXIS 3 scales along z only)    | UNIRES_NO_HYBRID=1 | splat2 AXIS 3                       |
+| iso2_gauss         | 34x30x36, ratio 2, Gaussian in-plane            |                    | separable passes; dropped taps      |
+| denoise            | 41x38x61, rot 0.1                               |                    | k_ata1 (fused)                      |
+| denoise_noata1     | the same                                        | UNIRES_NO_ATA1=1   | pull2 + splat2 AXIS -1              |
+| translate          | 41x38x60, thick 6 along z, fractional shift     |                    | shift kernel (matvec)               |
+| translate_noshift  | the same                                        | UNIRES_NO_SHIFT=1  | two-kernel matvec                   |
+| int_shift          | 41x38x61, thick 6 along z, shift (2, -1, 3)     |                    | k_ata_aligned* (matvec; the shift   |
+|                    |                                                 |                    | kernel declines: z not 4k)          |
+| int_shift_noalign  | the same                                        | UNIRES_NO_ALIGNED=1| two-kernel matvec                   |
+| identity           | 37x41x53 (not a multiple of the 2048 chunk)     |                    | k_dtd_flat (regime id)              |
+| identity_noflat    | the same                                        | UNIRES_NO_FLAT=1   | the line stencil kernel             |
+| orient_9 / _22     | 41x38x61, thick 4, stored as SIGNED_PERMS 9/22  |                    | canonicalised, pull2 + splat2       |
+| z_nosplat2         | 41x38x61, thick 6 along z, rot 0.1, scl 0.1     | UNIRES_NO_SPLAT2=1 | k_splat (no schedule)               |
+| z_pushtile         | the same                                        | UNIRES_PUSH=tile   | k_push_tile (the schedule is built, |
+|                    |                                                 |                    | the switch bypasses it: not visible)|
+| z_nopull2          | the same                                        | UNIRES_NO_PULL2=1  | k_pull_conv on R.Af / R.Tf          |
+| dn_nopull2         | denoise                                         | NO_PULL2, NO_ATA1  | k_pull + splat2 AXIS -1             |
+| ctab_1266 / _1272  | 24x20x1266 / 1272, thick 6 along z: conv table  |                    | AXIS 2 / no schedule                |
+|                    | of 1267 / 1273 entries (limit gn + 128 <= 1400) |                    |                                     |
+| rowcode_724 / _725 | 724x724x12 / 725x724x12, thick 6 along z:       |                    | AXIS 2 / no schedule                |
+|                    | gd.x rows_y = 524176 / 524900 against 2^19 - 1  |                    |                                     |
+| ax0_gdy511 / _512  | 24x511x20 / 24x512x20, thick 4 along x          |                    | AXIS 0 / no schedule (gd.y <= 511)  |
+| ax1_gdy509 / _513  | 24x508x20 / 24x512x20, thick 4 along y: gd.y    |                    | AXIS 1 / no schedule                |
+|                    | 509 / 513 (4 n + 1: 511 and 512 are not grids)  |                    |                                     |
+| sweep_*            | z-thick (thick 6, 41x38x61) and denoise, at     |                    | SWEEP_FORMS: two-pass schedule      |
+|                    | 0.3 / 0.5 / 0.7 / 0.78 rad about x and about y  |                    | build (staging-slot overflow) at    |
+|                    |                                                 |                    | 0.3 / 0.5; no splat2 / k_ata1 at    |
+|                    |                                                 |                    | 0.7; no pull2 at 0.78 about x       |
+
+The conv-table pair: a rect profile at ratio r has r + 1 taps, so the table has r n_x + 1 entries: 1272 itself is
+no table length at ratio 6, and 1267 / 1273 are the two lengths either side of the limit.
+
+The last-resort forward (api.hip: ata_forward / unires_proj_apply, launch_pull + conv_down on the untrimmed R.A /
+R.T / R.dim_g) runs only when launch_pull_conv fails.  launch_pull_conv (fused.hip) halves its output tile
+(pick_out_tile) down to one voxel until the pulled tile fits 24 KB of LDS, so it fails (over 64 KB) only when the
+product of the taps exceeds ~16k.  Such profiles are separable (R.sep: more than 64 taps in all) and run the
+separable passes on R.Af / R.Tf; the hybrid form, which resets sep, is kept only where the window plan of pull2
+exists (build_repeat_kernels) and its forward is hybrid_forward.  So that path is not reached, and its untrimmed taps
+never meet the trimmed push.  z_nopull2 runs k_pull_conv, on the trimmed R.Af / R.Tf.
+
+Observed on an MI355X (largest err / tol over every check of the case; voxels excluded as FOV ties): z_thick 0.350
+/ 300, z_thick_conc3 0.350 / 300, x_thick 0.288 / 0, y_thick 0.296 / 0, iso2_rect 0.394 / 0, iso2_rect_z4 0.335 / 0,
+iso2_rect_nohyb 0.394 / 0, iso2_gauss 1.000 / 0 (voxels only the dropped taps reach: the kernel returns 0, err = D),
+denoise 0.400 / 0, denoise_noata1 0.400 / 0, translate 0.038 / 0, translate_noshift 0.035 / 0, int_shift 0.025 / 0,
+int_shift_noalign 0.025 / 0, identity 0.151 / 0, identity_noflat 0.156 / 0, orient_9 0.141 / 0, orient_22 0.158 / 0,
+z_nosplat2, z_pushtile, z_nopull2 0.257 / 0, dn_nopull2 0.400 / 0, ctab_1266 0.403 / 2144, ctab_1272 0.229 / 3187,
+rowcode_724 0.284 / 22442 (of 6.3M), rowcode_725 0.271 / 24686, ax0_gdy511 0.237 / 662, ax0_gdy512 0.247 / 602,
+ax1_gdy509 0.237 / 386, ax1_gdy513 0.374 / 657, the sweep 0.111 - 0.376 / 0; the 256^3 matvec 0.156 / 3302.  The
+most instructions in one tile: 23 - 26 below 0.3 rad, 33 - 48 in the two-pass sweep cases.  No case failed: the
+suite found no kernel bug.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILE = (8, 4, 30)
+
+
+def _c(kw, env=None, conc=1, expect=None, light=False):
+    return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light)
+
+
+_Z = dict(dim_y=(41, 38, 61), thick=6, thick_axes=[2], rot=0.1, trans=2.0, scl=0.1)
+_DN = dict(dim_y=(41, 38, 61), regime='dn', rot=0.1, trans=2.0)
+_MID = dict(dim_y=(97, 90, 121), thick=6, thick_axes=[2], rot=0.12, trans=2.0, scl=0.1)
+_ISO = dict(dim_y=(42, 38, 61), thick=2, iso=(2, 2, 2), rot=0.1, trans=1.0, scl=0.1)
+_oriented = lambda i: i['perm'] != (0, 1, 2) or any(i['flip'])
+
+CASES = {
+    'z_thick': _c(_MID, expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable']),
+    'z_thick_conc3': _c(_MID, conc=3, expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable']),
+    'x_thick': _c(dict(_Z, thick=4, thick_axes=[0]), expect=lambda i: i['pull2'] and i['splat2_axis'] == 0),
+    'y_thick': _c(dict(_Z, thick=4, thick_axes=[1]), expect=lambda i: i['pull2'] and i['splat2_axis'] == 1),
+    'iso2_rect': _c(_ISO, expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable']),
+    'iso2_rect_z4': _c(dict(_ISO, dim_y=(42, 38, 64)),
+                       expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable']),
+    # (AXIS 3 carries the slice scaling along z only; with all ratios equal the thick axis is x: scl 0 here)
+    'iso2_rect_nohyb': _c(dict(_ISO, scl=0.0), {'UNIRES_NO_HYBRID': '1'}, expect=lambda i: i['splat2_axis'] == 3),
+    'iso2_gauss': _c(dict(dim_y=(34, 30, 36), thick=2, iso=(2, 2, 2), prof_ip=2, rot=0.1, trans=1.0),
+                     expect=lambda i: i['separable']),
+    'denoise': _c(_DN, expect=lambda i: i['fused']),
+    'denoise_noata1': _c(_DN, {'UNIRES_NO_ATA1': '1'},
+                         expect=lambda i: not i['fused'] and i['pull2'] and i['splat2_axis'] == -1),
+    # (the shift kernel's domain: identity rotation, z profile only, dim_y.z a multiple of 4 in [8, 256])
+    'translate': _c(dict(_Z, dim_y=(41, 38, 60), rot=0.0), expect=lambda i: i['shift']),
+    'translate_noshift': _c(dict(_Z, dim_y=(41, 38, 60), rot=0.0), {'UNIRES_NO_SHIFT': '1'},
+                            expect=lambda i: not i['shift']),
+    'int_shift': _c(dict(_Z, shift=(2.0, -1.0, 3.0)), expect=lambda i: not i['shift'] and i['splat2_axis'] == 2),
+    'int_shift_noalign': _c(dict(_Z, shift=(2.0, -1.0, 3.0)), {'UNIRES_NO_ALIGNED': '1'},
+                            expect=lambda i: not i['shift']),
+    'identity': _c(dict(dim_y=(37, 41, 53), regime='id'), expect=lambda i: i['regime'] == 'identity'),
+    'identity_noflat': _c(dict(dim_y=(37, 41, 53), regime='id'), {'UNIRES_NO_FLAT': '1'},
+                          expect=lambda i: i['regime'] == 'identity'),
+    'orient_9': _c(dict(_Z, thick=4, scl=0.0, orient=9),
+                   expect=lambda i: _oriented(i) and i['pull2'] and i['splat2_axis'] is not None),
+    'orient_22': _c(dict(_Z, thick=4, scl=0.0, orient=22),
+                    expect=lambda i: _oriented(i) and i['pull2'] and i['splat2_axis'] is not None),
+    'z_nosplat2': _c(_Z, {'UNIRES_NO_SPLAT2': '1'}, expect=lambda i: i['splat2_axis'] is None),
+    'z_pushtile': _c(_Z, {'UNIRES_PUSH': 'tile'}, expect=lambda i: i['splat2_axis'] == 2),
+    'z_nopull2': _c(_Z, {'UNIRES_NO_PULL2': '1'}, expect=lambda i: not i['pull2']),
+    'dn_nopull2': _c(_DN, {'UNIRES_NO_PULL2': '1', 'UNIRES_NO_ATA1': '1'},
+                     expect=lambda i: not i['pull2'] and not i['fused'] and i['splat2_axis'] == -1),
+    'ctab_1266': _c(dict(dim_y=(24, 20, 1266), thick=6, thick_axes=[2], rot=0.02, trans=1.0),
+                    expect=lambda i: i['splat2_axis'] == 2),
+    'ctab_1272': _c(dict(dim_y=(24, 20, 1272), thick=6, thick_axes=[2], rot=0.02, trans=1.0),
+                    expect=lambda i: i['splat2_axis'] is None),
+    'rowcode_724': _c(dict(dim_y=(724, 724, 12), thick=6, thick_axes=[2], rot=0.02, trans=1.0), light=True,
+                      expect=lambda i: i['splat2_axis'] == 2),
+    'rowcode_725': _c(dict(dim_y=(725, 724, 12), thick=6, thick_axes=[2], rot=0.02, trans=1.0), light=True,
+                      expect=lambda i: i['splat2_axis'] is None),
+    'ax0_gdy511': _c(dict(dim_y=(24, 511, 20), thick=4, thick_axes=[0], rot=0.02, trans=1.0),
+                     expect=lambda i: i['splat2_axis'] == 0),
+    'ax0_gdy512': _c(dict(dim_y=(24, 512, 20), thick=4, thick_axes=[0], rot=0.02, trans=1.0),
+                     expect=lambda i: i['splat2_axis'] is None),
+    'ax1_gdy509': _c(dict(dim_y=(24, 508, 20), thick=4, thick_axes=[1], rot=0.02, trans=1.0),
+                     expect=lambda i: i['splat2_axis'] == 1),
+    'ax1_gdy513': _c(dict(dim_y=(24, 512, 20), thick=4, thick_axes=[1], rot=0.02, trans=1.0),
+                     expect=lambda i: i['splat2_axis'] is None),
+}
+
+# The rotation sweep: the form each geometry runs at each angle, as observed on an MI355X: (pull2, splat2 axis,
+# k_ata1, schedule build).  Without any env switch: from 0.3 rad on, a tile overflows its 128-entry staging slot
+# and the schedule takes the two-pass build (up to 48 instructions per tile); at 0.7 rad a tile needs more than
+# 64 instructions and splat2 (and k_ata1) leave their domain; at 0.78 rad about x the pull window leaves pull2's.
+SWEEP_ANGLES = (0.3, 0.5, 0.7, 0.78)
+_T, _F = True, False
+SWEEP_FORMS = {
+    'sweep_z_x0.30': (_T, 2, _F, 'two-pass'), 'sweep_z_x0.50': (_T, 2, _F, 'two-pass'),
+    'sweep_z_x0.70': (_T, None, _F, None), 'sweep_z_x0.78': (_F, None, _F, None),
+    'sweep_z_y0.30': (_T, 2, _F, 'two-pass'), 'sweep_z_y0.50': (_T, 2, _F, 'two-pass'),
+    'sweep_z_y0.70': (_T, None, _F, None), 'sweep_z_y0.78': (_T, None, _F, None),
+    'sweep_dn_x0.30': (_T, -1, _T, 'two-pass'), 'sweep_dn_x0.50': (_T, -1, _T, 'two-pass'),
+    'sweep_dn_x0.70': (_T, None, _F, None), 'sweep_dn_x0.78': (_F, None, _F, None),
+    'sweep_dn_y0.30': (_T, -1, _T, 'two-pass'), 'sweep_dn_y0.50': (_T, -1, _T, 'two-pass'),
+    'sweep_dn_y0.70': (_T, None, _F, None), 'sweep_dn_y0.78': (_T, None, _F, None),
+}
+for _g, _kw in (('z', dict(_Z, scl=0.0)), ('dn', _DN)):
+    for _ax in ('x', 'y'):
+        for _a in SWEEP_ANGLES:
+            _ang = (_a, 0.0, 0.0) if _ax == 'x' else (0.0, _a, 0.0)
+            CASES['sweep_%s_%s%.2f' % (_g, _ax, _a)] = _c(dict(_kw, angles=_ang))
+# every case below 0.3 rad builds its schedule in one pass: the staging slot holds its tiles
+for _n in CASES:
+    if not _n.startswith('sweep_'):
+        CASES[_n]['one_pass'] = True
+
+_CHILD = r'''
+import json, sys
+import numpy as np, torch
+sys.path.insert(0, %(root)r)
+from tests.helpers import SIGNED_PERMS, make_problem, gpu_structs
+from tests.test_gpu_voxelwise import comb, inputs, spacings
+from oracle import nitorch_restated as N
+from unires_amd._project import _channel_plan
+kw, conc, light, out = %(kw)r, %(conc)r, %(light)r, sys.argv[1]
+if 'orient' in kw:
+    kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
+prob = make_problem(seed=11, **kw)
+xg, yg, sett = gpu_structs(prob, 'cuda:0')
+vx = N.voxel_size(prob['mat_y']).float()
+plan = _channel_plan(xg[0], yg[0], prob['method'], prob['do_proj'], vx)
+plan.set_concurrency(conc)
+info = plan.repeat_info(0)
+info['regime'] = 'identity' if not prob['do_proj'] else prob['method']
+p, v = inputs(prob['dim_y'], plan.dims_x[0])
+res = dict(info=json.dumps(info))
+d = lambda t: t.to('cuda:0')
+if prob['do_proj']:
+    sy, sx = spacings(kw)
+    res['Ap'] = plan.proj_apply(0, 'A', d(p)).cpu().numpy()
+    res['AtAp'] = plan.proj_apply(0, 'AtA', d(p)).cpu().numpy()
+    if not light:
+        res['Atv'] = plan.proj_apply(0, 'At', d(v)).cpu().numpy()
+    for ph in (0, 1):
+        pc = comb(prob['dim_y'], TILE_Y, sy, ph)
+        res['AtA_comb%%d' %% ph] = plan.proj_apply(0, 'AtA', d(pc)).cpu().numpy()
+        if not light:
+            res['A_comb%%d' %% ph] = plan.proj_apply(0, 'A', d(pc)).cpu().numpy()
+            vc = comb(plan.dims_x[0], None, sx, ph)
+            res['At_comb%%d' %% ph] = plan.proj_apply(0, 'At', d(vc)).cpu().numpy()
+dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
+res['q'] = plan.matvec(d(p), prob['rho'], yg[0].lam, dot=dot).cpu().numpy()
+torch.cuda.synchronize()
+res['dot'] = np.array(dot.item())
+np.savez(out, **res)
+'''.replace('TILE_Y', repr(TILE))
+
+
+def inputs(dim_y, dim_x):
+    gen = torch.Generator().manual_seed(7)
+    p = (torch.rand(tuple(dim_y), generator=gen) * 10 - 2).float()
+    v = (torch.rand(tuple(dim_x), generator=gen) * 10 - 2).float()
+    return p, v
+
+
+def spacings(kw):
+    """Comb spacing per axis, wider than the operator's footprint: y space 2 (3 r + 4) + 1 (A^T A reaches the
+    conv taps (r + 3 at most for the rect profile, r + 3 + r for the Gaussian at ratio 2) plus a corner either
+    side, twice), x space 8 (rows of A whose y footprints overlap)."""
+    r = [1, 1, 1]
+    if kw.get('regime', 'sr') == 'sr':
+        if kw.get('iso'):
+            r = list(kw['iso'])
+        else:
+            r[kw['thick_axes'][0]] = kw['thick']
+    return tuple(2 * (3 * ri + 4) + 1 for ri in r), (8, 8, 8)
+
+
+def comb(dim, tile, spacing, phase):
+    """Deltas (random values) on the product of per-axis positions: the ends, the first / last voxel of the first
+    and last (partial) tile and the middle, kept greedily in a phase-dependent order where at least ``spacing``
+    from those already kept (phase 0 and 1 together cover both voxels of each adjacent pair)."""
+    gen = torch.Generator().manual_seed(13 + phase)
+    pos = []
+    for a, n in enumerate(dim):
+        t = tile[a] if tile is not None else max(1, n // 3)
+        last = (n - 1) // t * t
+        pri = ([0, last, t, n // 2, n - 1, last - 1, t - 1, 1] if phase == 0 else
+               [n - 1, last - 1, t - 1, 1, n // 2, 0, last, t])
+        keep = []
+        for i in pri:
+            if 0 <= i < n and all(abs(i - k) >= spacing[a] for k in keep):
+                keep.append(i)
+        pos.append(sorted(keep))
+    out = torch.zeros(tuple(dim))
+    for i in pos[0]:
+        for j in pos[1]:
+            for k in pos[2]:
+                out[i, j, k] = float(torch.rand((), generator=gen)) * 4 + 1
+    return out
+
+
+def _run_child(tmp_path, name, case):
+    path = str(tmp_path / ('%s.npz' % name))
+    env = dict(os.environ)
+    env.update(case['env'])
+    env['UNIRES_SPLAT2_VERBOSE'] = '1'
+    r = subprocess.run([sys.executable, '-c', _CHILD % dict(root=ROOT, kw=case['kw'], conc=case['conc'],
+                                                            light=case['light']), path],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])
+    res = dict(np.load(path))
+    builds = re.findall(r'\[splat2\].*build (\S+), max instructions per tile (\d+)', r.stderr)
+    return res, (builds[-1] if builds else None)
+
+
+def _check(name, case, res):
+    from oracle import nitorch_restated as N
+    from oracle import unires_restated as O
+    from tests import ref64
+    from tests.helpers import SIGNED_PERMS, make_problem, oracle_structs
+    kw = case['kw']
+    if 'orient' in kw:
+        kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
+    prob = make_problem(seed=11, **kw)
+    xs, ys = oracle_structs(prob)
+    xc, yc = xs[0], ys[0]
+    info = json.loads(str(res['info']))
+    vx = N.voxel_size(prob['mat_y']).float()
+    rho = torch.tensor(prob['rho'], dtype=torch.float32)
+    p, v = inputs(prob['dim_y'], xc[0].po.dim_x if prob['do_proj'] else prob['dim_y'])
+    p64 = p.double()
+    q = torch.from_numpy(res['q'])
+    rep = {}
+
+    def dot_ok(refq, tolq, ex):
+        err_q = (q.double() - refq).abs()
+        slack = float((p64.abs() * err_q)[ex].sum()) if ex is not None else 0.0
+        return abs(float(res['dot']) - float((p64 * refq).sum())) <= float((p64.abs() * tolq).sum()) + slack
+
+    if not prob['do_proj']:  # A = I: q = tau p + rho lam^2 DtD p
+        tau = float(torch.tensor(float(xc[0].tau), dtype=torch.float32))
+        lam = float(torch.tensor(float(yc.lam), dtype=torch.float32))
+        c = float(rho) * lam * lam
+        refq = tau * p64 + c * O.DtD(p64, vx)
+        tolq = (ref64.U + ref64.U64) * (ref64.C_DTD + 2) * (tau * p64.abs() + c * ref64.dtd_abs(p64.abs(), vx))
+        r = ref64.compare(q, refq, tolq)
+        assert r['ok'], (name, 'matvec', r)
+        assert dot_ok(refq, tolq, None), (name, 'dot')
+        rep['matvec'] = r['max_ratio']
+        return rep, 0, 0.0
+    # the bound's orientation (it widens the coordinate error) is restated, and must be the plan's
+    mat, _ = O.proj_matrix(xc[0].po, prob['method'])
+    perm, flip, oriented = ref64.orientation_of(mat.float().double())
+    assert (tuple(info['perm']), tuple(info['flip'])) == (perm, flip), (name, info, perm, flip)
+    op = ref64.Operator64(xc[0].po, prob['method'], oriented=oriented)
+    mx, my, myy, n_near = op.tie_masks(xc[0].po)
+    assert int(myy.sum()) < 0.01 * p.numel(), (name, int(myy.sum()))
+    refA, tolA = op.bound_A(p)
+    r = ref64.compare(torch.from_numpy(res['Ap']), refA, tolA, mx)
+    assert r['ok'], (name, 'A', r)
+    rep['A'] = r['max_ratio']
+    ref, tol = op.bound_AtA(p)
+    r = ref64.compare(torch.from_numpy(res['AtAp']), ref, tol, myy)
+    assert r['ok'], (name, 'AtA', r)
+    rep['AtA'] = r['max_ratio']
+    del ref, tol
+    refq, tolq = op.bound_matvec(p, xc[0].tau, rho, yc.lam, vx)
+    r = ref64.compare(q, refq, tolq, myy)
+    assert r['ok'], (name, 'matvec', r)
+    rep['matvec'] = r['max_ratio']
+    # the float64 dot epilogue: <p, q> within sum |p| tol_q (+ the actual error in tied voxels)
+    assert dot_ok(refq, tolq, myy), (name, 'dot')
+    del refq, tolq
+    if not case['light']:
+        refAt, tolAt = op.bound_At(v)
+        r = ref64.compare(torch.from_numpy(res['Atv']), refAt, tolAt, my)
+        assert r['ok'], (name, 'At', r)
+        rep['At'] = r['max_ratio']
+        # the float64 adjoint identity on the kernels' A and At
+        Ap, Atv, v64 = torch.from_numpy(res['Ap']).double(), torch.from_numpy(res['Atv']).double(), v.double()
+        lhs = abs(float((Ap * v64).sum()) - float((p64 * Atv).sum()))
+        slack = float(((Ap - refA).abs() * v64.abs())[mx].sum() + ((Atv - refAt).abs() * p64.abs())[my].sum())
+        assert lhs <= float((tolA * v64.abs()).sum() + (tolAt * p64.abs()).sum()) + slack, (name, 'adjoint')
+    # impulse combs against the plan's own taps (D = 0): columns of A and AtA, rows of A via At
+    opt = ref64.Operator64(xc[0].po, prob['method'], trimmed=True, oriented=oriented)
+    sy, sx = spacings(case['kw'])
+    for ph in (0, 1):
+        pc = comb(prob['dim_y'], TILE, sy, ph)
+        checks = [('AtA_comb%d' % ph, lambda: opt.bound_AtA(pc), myy)]
+        if not case['light']:
+            vc = comb(tuple(xc[0].po.dim_x), None, sx, ph)
+            checks += [('A_comb%d' % ph, lambda: opt.bound_A(pc), mx), ('At_comb%d' % ph, lambda: opt.bound_At(vc), my)]
+        for key, bound, ex in checks:
+            refc, tolc = bound()
+            r = ref64.compare(torch.from_numpy(res[key]), refc, tolc, ex)
+            assert r['ok'], (name, key, r)
+            rep[key] = r['max_ratio']
+    return rep, int(myy.sum()), op.R
+
+
+def test_every_form_per_voxel_against_float64(tmp_path):
+    drift = []
+    for name, case in CASES.items():
+        res, build = _run_child(tmp_path, name, case)
+        info = json.loads(str(res['info']))
+        info['perm'], info['flip'] = tuple(info['perm']), tuple(info['flip'])
+        form = (info['pull2'], info['splat2_axis'], info['fused'], build[0] if build else None)
+        if case['expect'] is not None and not case['expect'](info):
+            drift.append((name, info))  # (checked after the table: every case's form is reported)
+        if case.get('one_pass') and build is not None and build[0] != 'one-pass':
+            drift.append((name, build))
+        if name in SWEEP_FORMS and SWEEP_FORMS[name] != form:
+            drift.append((name, form, SWEEP_FORMS[name]))
+        rep, excluded, R = _check(name, case, res)
+        print('%-20s %s build %s max err/tol %.3f excluded %d R %.0f'
+              % (name, info, build, max(rep.values()), excluded, R), flush=True)
+    assert not drift, drift
+
+
+@pytest.mark.slow
+def test_full_size_matvec_per_voxel(tmp_path):
+    """One channel of cfg3_256c3_thick6z at 256^3 (helpers.oracle_channel), the matvec with its dot, per voxel."""
+    import workloads
+    from tests import helpers as H
+    from tests import ref64
+    child = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+import workloads
+from tests import helpers as H
+import unires_amd as U
+from unires_amd._project import _channel_plan
+wl = dict(workloads.WORKLOADS['cfg3_256c3_thick6z'])
+P = H.oracle_channel(wl, (256, 256, 256), seed=0)
+po = U._proj_info((256, 256, 256), P['mat_y'], P['dim_x'], P['mat_x'], rigid=P['rigid'], prof_ip=0, prof_tp=0,
+                  device='cuda:0')
+xg = [U._input(P['dat_x'].to('cuda:0'), P['mat_x'], P['tau'], po)]
+yg = U._output(torch.zeros((256, 256, 256), device='cuda:0'), P['mat_y'], P['lam'])
+plan = _channel_plan(xg, yg, 'super-resolution', True)
+info = plan.repeat_info(0)
+assert info['pull2'] and info['splat2_axis'] == 2, info
+dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
+q = plan.matvec(P['b'].to('cuda:0'), 0.9, P['lam'], dot=dot).cpu().numpy()
+torch.cuda.synchronize()
+np.savez(sys.argv[1], q=q, dot=np.array(dot.item()))
+''' % ROOT
+    path = str(tmp_path / 'full.npz')
+    r = subprocess.run([sys.executable, '-c', child, path], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = dict(np.load(path))
+    wl = dict(workloads.WORKLOADS['cfg3_256c3_thick6z'])
+    P = H.oracle_channel(wl, (256, 256, 256), seed=0)
+    from oracle import nitorch_restated as N
+    vx = N.voxel_size(P['mat_y']).float()
+    op = ref64.Operator64(P['po'], 'super-resolution')
+    _, _, myy, _ = op.tie_masks(P['po'])
+    assert int(myy.sum()) < 0.01 * P['b'].numel()
+    refq, tolq = op.bound_matvec(P['b'], P['tau'], torch.tensor(0.9), P['lam'], vx)
+    q = torch.from_numpy(res['q'])
+    rr = ref64.compare(q, refq, tolq, myy)
+    print('full size: max err/tol %.3f, excluded %d, R %.0f' % (rr['max_ratio'], rr['excluded'], op.R), flush=True)
+    assert rr['ok'], rr
+    p64 = P['b'].double()
+    slack = float((p64.abs() * (q.double() - refq).abs())[myy].sum())
+    assert abs(float(res['dot']) - float((p64 * refq).sum())) <= float((p64.abs() * tolq).sum()) + slack

@@ -779,10 +779,17 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
   S.axis = axis;
   S.fill = hs[1] ? (double)hs[0] / (64.0 * (double)hs[1]) : 0.0;
   S.valid = true;
-  if (verbose)
+  if (verbose) {
+    // (also: which build ran - one pass through the staging slots or, a tile overflowing its slot, two - the most
+    // instructions in one tile, and how many tiles end at each residue mod 4 of their instruction count)
+    unsigned imax = 0, res4[4] = {0, 0, 0, 0};
+    for (int i = 0; i < nt; ++i) imax = std::max(imax, cnt[i].y), ++res4[cnt[i].y & 3u];
     fprintf(stderr, "[splat2] %d tiles, %llu instructions, %u segments, %llu points (%.2f per output voxel), "
-            "lane fill %.3f, schedule %.1f MB, row_sep %d\n", nt, hs[1], re, hs[0],
-            (double)hs[0] / (double)dd.numel(), S.fill, (re * sizeof(S2Entry) + ri * 16.0) / 1e6, safe.row_sep);
+            "lane fill %.3f, schedule %.1f MB, row_sep %d, build %s, max instructions per tile %u, "
+            "tiles by instructions mod 4 %u %u %u %u\n", nt, hs[1], re, hs[0],
+            (double)hs[0] / (double)dd.numel(), S.fill, (re * sizeof(S2Entry) + ri * 16.0) / 1e6, safe.row_sep,
+            stage ? "one-pass" : "two-pass", imax, res4[0], res4[1], res4[2], res4[3]);
+  }
   return 0;
 }
 
