@@ -205,6 +205,13 @@ int unires_plan_time_matvecs(unires_plan_t *plan, int32_t on);
 /* Waits for the recorded events; returns how many applications were recorded since the last call and
  * the sum of their durations (microseconds), and forgets them. */
 int unires_plan_matvec_time(unires_plan_t *plan, int32_t *launches, double *total_us);
+/* Deferred iterate update of tol == 0 solves (no FFT preconditioner): x += alpha_k p_k is applied for K iterations
+ * at once, in iteration order, with the same roundings (the same bits); the last K directions are kept in a ring of
+ * plan buffers.  k > 0 asks for K = min(k, 8) for this plan's next solves (1: the iterate updated every iteration;
+ * default: UNIRES_CG_RING, else 8); the ring is allocated at the plan's first such solve and never grown, so K is
+ * capped by what was allocated then.  k == 0 changes nothing.  *last (nullable) gets the K the plan's last solve ran
+ * with (1 for solves outside the scope and for a plan that has not solved yet). */
+int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last);
 
 /* _proj_apply(operator, ., po_n)  (_project.py:99-190) for repeat n, WITHOUT tau.
  * in/out sizes follow the operator (A: dim_y -> dim_x; At: dim_x -> dim_y; AtA: dim_y -> dim_y). */

@@ -121,6 +121,13 @@ class ChannelPlan:
         the operator applications as production runs them)."""
         check(self.lib.unires_plan_time_matvecs(self._h, 2 if on == 2 else (1 if on else 0)))
 
+    def cg_ring(self, k=0):
+        """Deferred iterate update of tol = 0 solves (``unires_plan_cg_ring``): ``k > 0`` asks for a ring of k
+        directions (1: x updated every iteration); returns the ring size the plan's last solve ran with."""
+        last = C.c_int32(0)
+        check(self.lib.unires_plan_cg_ring(self._h, int(k), C.byref(last)))
+        return int(last.value)
+
     @on_device
     def matvec_time(self):
         """(launches, total microseconds) recorded since the last call; waits for them."""

@@ -363,10 +363,11 @@ struct unires_plan {
     float *x = nullptr;
     float rho = 0.f, lam = 0.f;
     int max_iter = -1, stop = -1, pre = -1;
+    int ring = 1;  // direction buffers of the deferred iterate update (a captured solve has the ring baked in)
     double tol = -1.0;
     bool operator==(const CgKey &o) const {
       return b == o.b && x == o.x && rho == o.rho && lam == o.lam && max_iter == o.max_iter &&
-             stop == o.stop && pre == o.pre && tol == o.tol;
+             stop == o.stop && pre == o.pre && ring == o.ring && tol == o.tol;
     }
   } cg_key;
   hipGraphExec_t cg_exec = nullptr;
@@ -376,6 +377,13 @@ struct unires_plan {
   unsigned long long *progress = nullptr, *progress_dev = nullptr;
   unsigned cg_gen = 0;
   float *precM = nullptr;  // Jacobi diagonal (own allocation, made by unires_precond_build)
+  // deferred iterate update of tol = 0 solves (cg_ring_prepare): ring slot 0 is `p`, slots 1 .. ring_slots live in
+  // `ring` (own allocation, made at the first such solve, freed with the plan only: a graph may have it baked in)
+  float *ring = nullptr;
+  int ring_slots = 0;
+  bool ring_tried = false;  // the allocation was decided (made, refused by the budget, or failed)
+  int ring_req = 0;         // unires_plan_cg_ring: K asked for (0: UNIRES_CG_RING or the default)
+  int last_ring = 1;        // K of the plan's last solve (1: the iterate updated every iteration)
   FftPre fft;              // FFT-diagonal preconditioner (plans + buffers, made on demand)
   float prec_rho = 0.f, prec_lam = 0.f;
   int prec_mode = UNIRES_PRECOND_IDENTITY;
@@ -819,6 +827,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (!plan) return UNIRES_OK;
   if (plan->ws) (void)hipFree(plan->ws);
   if (plan->precM) (void)hipFree(plan->precM);
+  if (plan->ring) (void)hipFree(plan->ring);
   if (plan->cg_exec) (void)hipGraphExecDestroy(plan->cg_exec);
   if (plan->cg_start_exec) (void)hipGraphExecDestroy(plan->cg_start_exec);
   if (plan->cg_chunk_exec) (void)hipGraphExecDestroy(plan->cg_chunk_exec);
@@ -838,6 +847,18 @@ extern "C" int unires_plan_time_matvecs(unires_plan_t *plan, int32_t on) {
   plan->twice = twice;
   plan->timing = on == 1;
   if (!plan->timing) drop_timing(plan);
+  return UNIRES_OK;
+}
+
+extern "C" int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
+  if (k < 0) return fail(UNIRES_ERR_ARG, "ring size must be >= 0");
+  if (k > 0) {
+    const int v = std::min<int>(k, kMaxRing);
+    if (v != plan->ring_req) drop_cg_graph(plan);  // (a captured solve has its ring baked in)
+    plan->ring_req = v;
+  }
+  if (last) *last = plan->last_ring;
   return UNIRES_OK;
 }
 
@@ -1448,20 +1469,38 @@ static int cg_enqueue_start(unires_plan *pl, float rho, float lam, const float *
   return UNIRES_OK;
 }
 
+// UNIRES_CG_FOLD=1: alpha / beta in the prologues of the vector kernels instead of one-block kernels of their own
+static bool cg_fold_on() {
+  static const bool on = getenv("UNIRES_CG_FOLD") && getenv("UNIRES_CG_FOLD")[0] == '1';
+  return on;
+}
+
+// slot j of the plan's direction ring (slot 0: the buffer the start writes p into)
+static float *ring_slot(unires_plan *pl, int j) {
+  return j == 0 ? pl->p : pl->ring + (size_t)(j - 1) * (align_up(pl->dy.numel() * 4) / 4);
+}
+
+// `ring` > 1 (tol = 0 solves enqueued whole, cg_ring_prepare): the iterate update is deferred - iteration k's
+// direction is slot (k - k_first) mod ring, and x takes the window's alpha p terms at every ring-th iteration and at
+// the last (k_update_p_flush, cg.hip).
 static int cg_enqueue_iters(unires_plan *pl, float rho, float lam, const float *b, float *x, int k_first,
                             int count, double tol, int stop_mode, const float *M, bool fft, bool dev_k,
-                            unsigned long long *hostw, hipStream_t st) {
+                            unsigned long long *hostw, hipStream_t st, int ring = 1) {
   const size_t ny = pl->dy.numel();
   const bool check = tol != 0.0;
   CgState *S = pl->state;
   const int *done = &S->done;
   const int gv = vec_num_blocks(ny);
-  // UNIRES_CG_FOLD=1: alpha / beta in the prologues of the vector kernels instead of one-block
-  // kernels of their own
-  static const bool fold_on = getenv("UNIRES_CG_FOLD") && getenv("UNIRES_CG_FOLD")[0] == '1';
+  const bool fold_on = cg_fold_on();
   const int gf = vec_num_blocks_fold(ny);
+  if (ring > 1 && (check || fft || dev_k || fold_on || ring > kMaxRing || ring - 1 > pl->ring_slots))
+    return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
+  RingPtrs rp = {};
+  for (int j = 0; j < ring && ring > 1; ++j) rp.p[j] = ring_slot(pl, j);
   for (int k = k_first; k < k_first + count; ++k) {
     const int kk = dev_k ? -1 : k;
+    const int slot = ring > 1 ? (k - k_first) % ring : 0;
+    float *p = ring > 1 ? ring_slot(pl, slot) : pl->p;  // this iteration's direction
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (pl->timing && hipEventCreate(&ev0) == hipSuccess) {
       if (hipEventCreate(&ev1) == hipSuccess) {
@@ -1471,8 +1510,8 @@ static int cg_enqueue_iters(unires_plan *pl, float rho, float lam, const float *
         ev0 = nullptr;
       }
     }
-    if (pl->twice) (void)matvec(pl, rho, lam, pl->p, pl->ap, pl->part0, done, st);  // (measurement: see the header)
-    const int g = matvec(pl, rho, lam, pl->p, pl->ap, pl->part0, done, st);
+    if (pl->twice) (void)matvec(pl, rho, lam, p, pl->ap, pl->part0, done, st);  // (measurement: see the header)
+    const int g = matvec(pl, rho, lam, p, pl->ap, pl->part0, done, st);
     if (ev0 && ev1) {
       (void)hipEventRecord(ev1, st);
       if (pl->tev.size() >= 65536) {  // a caller that never collects: forget the oldest pair
@@ -1495,7 +1534,7 @@ static int cg_enqueue_iters(unires_plan *pl, float rho, float lam, const float *
       launch_update_px_fold(S, pl->part1, gf, k, pl->r, pl->p, x, ny, M, st);
     } else {
       launch_sc_alpha(S, pl->part0, g, st);
-      launch_update_xr(S, pl->p, pl->ap, lazy_x ? nullptr : x, pl->r, b, ny, pl->part0,
+      launch_update_xr(S, p, pl->ap, lazy_x ? nullptr : x, pl->r, b, ny, pl->part0,
                        recur ? pl->part1 : nullptr, M, st);
       if (fft) {  // (the transforms also run after convergence: hipFFT has no device-side skip)
         if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
@@ -1505,7 +1544,12 @@ static int cg_enqueue_iters(unires_plan *pl, float rho, float lam, const float *
         launch_sc_beta_guarded(S, pl->part0, pl->part1, gv, kk, tol, hostw, st);
       else
         launch_sc_beta(S, pl->part0, pl->part1, gv, kk, obj_kind, tol, obj_kind ? hostw : nullptr, st);
-      launch_update_p(S, fft ? pl->fft.z : pl->r, pl->p, ny, M, lazy_x ? x : nullptr, st);
+      if (ring > 1 && (slot == ring - 1 || k == k_first + count - 1))
+        launch_update_p_flush(S, pl->r, rp, slot + 1, ring_slot(pl, (slot + 1) % ring), ny, M, x, st);
+      else if (ring > 1)
+        launch_update_p_ring(S, pl->r, p, ring_slot(pl, slot + 1), slot, ny, M, st);
+      else
+        launch_update_p(S, fft ? pl->fft.z : pl->r, pl->p, ny, M, lazy_x ? x : nullptr, st);
     }
     if (check && stop_mode == UNIRES_STOP_MAXGAIN) {
       // objective sum x (Ax - 2b) folded into the matvec epilogue: A(x) is never stored
@@ -1523,10 +1567,50 @@ static int cg_enqueue_iters(unires_plan *pl, float rho, float lam, const float *
 
 // Enqueues the whole solve (every kernel of nitorch's cg()) on `st`.
 static int cg_enqueue(unires_plan *pl, float rho, float lam, const float *b, float *x, int max_iter,
-                      double tol, int stop_mode, const float *M, bool fft, hipStream_t st) {
+                      double tol, int stop_mode, const float *M, bool fft, hipStream_t st, int ring) {
   const int rc = cg_enqueue_start(pl, rho, lam, b, x, tol, stop_mode, M, fft, nullptr, st);
   if (rc) return rc;
-  return cg_enqueue_iters(pl, rho, lam, b, x, 1, max_iter, tol, stop_mode, M, fft, false, nullptr, st);
+  return cg_enqueue_iters(pl, rho, lam, b, x, 1, max_iter, tol, stop_mode, M, fft, false, nullptr, st, ring);
+}
+
+// K of the deferred iterate update for a solve that nothing reads x of before it ends (tol = 0, no FFT
+// preconditioner, not the folded measurement path; the caller checks that): unires_plan_cg_ring's request, else
+// UNIRES_CG_RING, else 8, clamped to 1 .. kMaxRing.  The K - 1 extra direction buffers are allocated at the plan's
+// first such solve, within a budget (UNIRES_CG_RING_MB, default an eighth of the free device memory); the ring is
+// never grown or freed after that (a graph - ours or a caller's capture - may have its buffers baked in), so later
+// requests get at most what was allocated then.  No room, a failed allocation, or a stream under capture at that
+// first solve: K = 1, the iterate updated every iteration.
+static bool stream_capturing(hipStream_t st);
+static int cg_ring_prepare(unires_plan *pl, hipStream_t st) {
+  static const int env_k = [] {
+    const char *e = getenv("UNIRES_CG_RING");
+    return e ? atoi(e) : 8;
+  }();
+  int want = pl->ring_req > 0 ? pl->ring_req : env_k;
+  want = std::max(1, std::min(want, kMaxRing));
+  if (want <= 1) return 1;
+  if (!pl->ring_tried) {
+    if (stream_capturing(st)) return 1;  // (no allocation inside a capture: decided at the next plain solve)
+    pl->ring_tried = true;
+    const size_t slot = align_up(pl->dy.numel() * 4);
+    size_t budget = 0;
+    if (const char *e = getenv("UNIRES_CG_RING_MB")) {
+      budget = (size_t)std::max(0.0, atof(e) * 1048576.0);
+    } else {
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = free_b / 8;
+      (void)hipGetLastError();
+    }
+    const int n = (int)std::min<size_t>((size_t)(want - 1), budget / slot);
+    if (n < 1) return 1;
+    if (hipMalloc((void **)&pl->ring, (size_t)n * slot) != hipSuccess) {
+      (void)hipGetLastError();
+      pl->ring = nullptr;
+      return 1;
+    }
+    pl->ring_slots = n;
+  }
+  return std::min(want, pl->ring_slots + 1);
 }
 
 // --------------------------------------------------------------------------
@@ -1811,6 +1895,7 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
     return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
                                 "(it is fed to the device chunk by chunk, following its progress)");
   if (cg_chunked(tol, max_iter) && !(stream_capturing(st) && max_iter <= kMaxCgIter)) {
+    pl->last_ring = 1;
     std::vector<CgRun> runs(1, cg_make_run(pl, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode, st));
     if ((rc = cg_run_start(runs[0]))) return rc;
     if ((rc = cg_runs_drive(runs))) return rc;
@@ -1819,19 +1904,22 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
     return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
   }
   ++pl->cg_gen;  // (k_sc_init counts every solve)
+  // deferred iterate update: only where nothing reads x before the solve ends
+  const int ring = tol == 0.0 && !fft && !cg_fold_on() && max_iter > 0 ? cg_ring_prepare(pl, st) : 1;
+  pl->last_ring = ring;
 
   // hipGraph replay (UNIRES_CG_GRAPH=0 disables): the ~8 launches per iteration of a solve are
   // captured once and re-launched as one graph while the arguments stay the same
   unires_plan::CgKey key;
   key.b = b, key.x = x, key.rho = rho, key.lam = lam, key.max_iter = max_iter, key.stop = stop_mode;
-  key.pre = precond_mode, key.tol = tol;
+  key.pre = precond_mode, key.tol = tol, key.ring = ring;
   const bool graphable = cg_graphs_on() && !fft && max_iter > 0 && !pl->timing;  // (events go with plain launches)
   if (graphable && pl->cg_exec && pl->cg_key == key) {
     HIP_TRY(hipGraphLaunch(pl->cg_exec, st));
   } else {
     if (graphable && pl->cg_exec) drop_cg_graph(pl);
     rc = graphable ? capture_graph(st, &pl->cg_exec, [&] {
-      return cg_enqueue(pl, rho, lam, b, x, max_iter, tol, stop_mode, M, fft, st);
+      return cg_enqueue(pl, rho, lam, b, x, max_iter, tol, stop_mode, M, fft, st, ring);
     }) : -1;
     if (rc > 0) {
       cg_resync_gen(pl);
@@ -1843,7 +1931,7 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
         cg_resync_gen(pl);
         return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
       }
-    } else if ((rc = cg_enqueue(pl, rho, lam, b, x, max_iter, tol, stop_mode, M, fft, st))) {
+    } else if ((rc = cg_enqueue(pl, rho, lam, b, x, max_iter, tol, stop_mode, M, fft, st, ring))) {
       cg_resync_gen(pl);
       return rc;
     }
@@ -1881,6 +1969,7 @@ extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, cons
     }
   } else {
     std::vector<CgRun> runs;
+    for (int c = 0; c < n; ++c) plans[c]->last_ring = 1;
     for (int c = 0; c < n; ++c)
       runs.push_back(cg_make_run(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode,
                                  (hipStream_t)streams[c]));

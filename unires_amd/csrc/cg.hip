@@ -218,6 +218,105 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---- deferred iterate update (tol = 0 solves: nothing reads x before the solve ends) ------------------------------
+// x += alpha_k p_k is applied for up to K iterations at once, per element, in iteration order and with the same
+// roundings as k_update_p<true> (x = fl(x + fl(alpha_k p_k)), alpha rounded to float32 at use): the same bits.  The
+// directions stay in a ring of K buffers instead of being overwritten in place.  Plain iterations read r and p_k and
+// write p_{k+1} (3 volume passes instead of 5); every K-th iteration and the solve's last one flush: they read x and
+// the window's m directions, write x and p_{k+1} (m + 4 passes).  With K = 8: 4.125 passes per iteration on average.
+
+// Every read of a direction here is its last one for a while (the flush reads it again K iterations on, long after the
+// Infinity Cache has turned over): streaming loads.  With p written in place this did not matter; with a ring, p_k's
+// lines allocating next to the fresh p_{k+1}, r and A p (4 x 67 MB at 256^3 against 256 MB) pushed p_{k+1} out before
+// the matvec read it: k_splat2 59.5 -> 66.1 us, the pull 35.9 -> 37.5 (config 3, serial fixed-iteration run).  With
+// these loads streaming: 60.9 / 36.2 (p_k is still resident from the matvec's own reads; experiments/E14).
+//
+// p_out = beta p_in + z.  Workgroup 0 records this iteration's alpha and whether it was committed: k_update_p returns
+// at entry on a done state, so x must not take that iteration's term (the flush reads the record).
+__global__ void __launch_bounds__(kBlock)
+    k_update_p_ring(CgState *__restrict__ st, const float *__restrict__ r, const float *__restrict__ p_in,
+                    float *__restrict__ p_out, int slot, size_t n, const float *__restrict__ M) {
+  const int done = st->done;
+  if (blockIdx.x == 0 && threadIdx.x == 0) st->ahist[slot] = st->alpha, st->committed[slot] = done ? 0 : 1;
+  if (done) return;
+  const float beta = (float)st->beta;
+  GRID_STRIDE_VEC4(n);
+  for (size_t i = tid0; i < n4; i += stride) {
+    const float4 vz = zval4(ld4(r, i), M, i);
+    float4 vp = ld4_stream(p_in, i);  // (see below)
+    vp.x = __fadd_rn(__fmul_rn(beta, vp.x), vz.x);
+    vp.y = __fadd_rn(__fmul_rn(beta, vp.y), vz.y);
+    vp.z = __fadd_rn(__fmul_rn(beta, vp.z), vz.z);
+    vp.w = __fadd_rn(__fmul_rn(beta, vp.w), vz.w);
+    st4(p_out, i, vp);
+  }
+  for (size_t i = n4 * 4 + tid0; i < n; i += stride)
+    p_out[i] = __fadd_rn(__fmul_rn(beta, p_in[i]), zval1(r[i], M, i));
+}
+
+// The flush: slots 0 .. m - 2 hold the earlier iterations of the window (their alpha and commit flag recorded by
+// k_update_p_ring), slot m - 1 this iteration's direction, committed unless the state is done now.  Whatever `done`
+// says, the earlier committed terms are applied; this iteration's term and p update only when it is not done.
+// p_out is slot 0 when the window is full (m = K): element i of slot 0 is read and then overwritten by the same thread
+// in the same loop trip, and no other thread touches element i, so the in-place write is safe (the pointers carry no
+// __restrict__, which keeps the compiler from moving the load below the store).
+__global__ void __launch_bounds__(kBlock)
+    k_update_p_flush(CgState *__restrict__ st, const float *__restrict__ r, RingPtrs ring, int m, float *p_out,
+                     size_t n, const float *__restrict__ M, float *__restrict__ x) {
+  const int done = st->done;
+  const float beta = (float)st->beta;
+  float a[kMaxRing];
+  bool c[kMaxRing];
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < kMaxRing; ++j) {
+    c[j] = false, a[j] = 0.f;
+    if (j < m - 1) c[j] = st->committed[j] != 0, a[j] = (float)st->ahist[j];
+    if (j == m - 1) c[j] = !done, a[j] = (float)st->alpha;
+    any = any || c[j];
+  }
+  if (!any) return;
+  GRID_STRIDE_VEC4(n);
+  for (size_t i = tid0; i < n4; i += stride) {
+    float4 vz = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!done) vz = zval4(ld4(r, i), M, i);
+    float4 vx = ld4_stream(x, i);
+    float4 vp[kMaxRing];
+#pragma unroll
+    for (int j = 0; j < kMaxRing; ++j)
+      if (c[j]) vp[j] = ld4_stream(ring.p[j], i);
+#pragma unroll
+    for (int j = 0; j < kMaxRing; ++j) {
+      if (!c[j]) continue;
+      vx.x = __fadd_rn(vx.x, __fmul_rn(a[j], vp[j].x));
+      vx.y = __fadd_rn(vx.y, __fmul_rn(a[j], vp[j].y));
+      vx.z = __fadd_rn(vx.z, __fmul_rn(a[j], vp[j].z));
+      vx.w = __fadd_rn(vx.w, __fmul_rn(a[j], vp[j].w));
+      if (j == m - 1) {  // (c[m - 1] = !done)
+        float4 b = vp[j];
+        b.x = __fadd_rn(__fmul_rn(beta, b.x), vz.x);
+        b.y = __fadd_rn(__fmul_rn(beta, b.y), vz.y);
+        b.z = __fadd_rn(__fmul_rn(beta, b.z), vz.z);
+        b.w = __fadd_rn(__fmul_rn(beta, b.w), vz.w);
+        st4(p_out, i, b);
+      }
+    }
+    st4_stream(x, i, vx);
+  }
+  for (size_t i = n4 * 4 + tid0; i < n; i += stride) {  // tail
+    float vx = x[i], own = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMaxRing; ++j) {
+      if (!c[j]) continue;
+      const float pj = ring.p[j][i];
+      vx = __fadd_rn(vx, __fmul_rn(a[j], pj));
+      if (j == m - 1) own = pj;
+    }
+    x[i] = vx;
+    if (!done) p_out[i] = __fadd_rn(__fmul_rn(beta, own), zval1(r[i], M, i));
+  }
+}
+
 // y = a*x + y (generic axpy; used by the identity regime's RHS)
 __global__ void __launch_bounds__(kBlock)
     k_axpy(float a, const float *__restrict__ x, float *__restrict__ y, size_t n) {
@@ -629,6 +728,14 @@ void launch_update_p(const CgState *s, const float *r, float *p, size_t n, const
     hipLaunchKernelGGL(k_update_p<true>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, p, n, M, x);
   else
     hipLaunchKernelGGL(k_update_p<false>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, p, n, M, x);
+}
+void launch_update_p_ring(CgState *s, const float *r, const float *p_in, float *p_out, int slot, size_t n,
+                          const float *M, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_p_ring, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, p_in, p_out, slot, n, M);
+}
+void launch_update_p_flush(CgState *s, const float *r, const RingPtrs &ring, int m, float *p_out, size_t n,
+                           const float *M, float *x, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_p_flush, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
 }
 // y = a*y + c  (preconditioner diagonal: tau * AtA(1) + const)
 __global__ void __launch_bounds__(kBlock) k_scale_shift(float a, float c, float *__restrict__ y, size_t n) {

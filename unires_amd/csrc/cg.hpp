@@ -5,6 +5,7 @@
 namespace unires {
 
 constexpr int kMaxCgIter = 4096;
+constexpr int kMaxRing = 8;  // most direction buffers a deferred-iterate solve keeps (api.hip: cg_ring_prepare)
 
 struct CgState {  // lives in device memory, owned by the plan
   double rz, pAp, alpha, beta, obj_max, obj_min;
@@ -17,6 +18,13 @@ struct CgState {  // lives in device memory, owned by the plan
   int skip_fresh;        // 1: this iteration's fresh objective (a second A(x)) is not needed - its kernels return at entry
   int fresh_prev_ok;     // fresh_prev holds the FRESH objective of the previous iteration
   double rec_prev, fresh_prev, gain_rec;  // recurred objective of the previous iteration; this iteration's recurred gain
+  // deferred iterate update (launch_update_p_ring / _flush): alpha of the iteration whose direction is in ring slot j,
+  // and whether that iteration's "x += alpha p" was committed (its p update ran, i.e. the solve was not done)
+  double ahist[kMaxRing];
+  int committed[kMaxRing];
+};
+struct RingPtrs {  // the ring's direction buffers, slot j = the j-th iteration since the last flush (by value: kernarg)
+  const float *p[kMaxRing];
 };
 
 // Progress word of a solve, published by its scalar kernels to host-mapped memory (chunked solves,
@@ -38,6 +46,16 @@ void launch_update_xr(const CgState *s, const float *p, const float *ap, float *
 // pass less per iteration (only valid when nothing stops the solve between the two launches)
 void launch_update_p(const CgState *s, const float *r, float *p, size_t n, const float *M, float *x,
                      hipStream_t st);
+// Deferred iterate update (tol = 0 solves, api.hip): the directions of up to kMaxRing iterations stay in a ring and
+// x takes their alpha p terms at once, in iteration order, with the same roundings.
+// ring: p_out = beta p_in + z for the iteration whose direction is ring slot `slot`; records its alpha and whether it
+// was committed (the state not done).
+void launch_update_p_ring(CgState *s, const float *r, const float *p_in, float *p_out, int slot, size_t n,
+                          const float *M, hipStream_t st);
+// flush: the same p update for slot m - 1 (p_out may be slot 0: see k_update_p_flush), then
+// x = fl(x + fl(alpha_j p_j)) for the committed slots j = 0 .. m - 1 in ascending order
+void launch_update_p_flush(CgState *s, const float *r, const RingPtrs &ring, int m, float *p_out, size_t n,
+                           const float *M, float *x, hipStream_t st);
 // M = nullptr: identity preconditioner; else z = r / M (Jacobi)
 void launch_scale_shift(float a, float c, float *y, size_t n, hipStream_t st);
 void launch_fill(float v, float *y, size_t n, hipStream_t st);
