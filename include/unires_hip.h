@@ -100,6 +100,25 @@ int unires_warp_label(const float *label, const int32_t ldim[3], const float M[1
 int unires_pull3d_nearest(const float *src, const int32_t sdim[3], const float M[12], float *dst,
                           const int32_t gdim[3], float fov_tol, void *stream);
 
+/* Noise / intensity hyper-parameters (the reference's _estimate_hyperpar -> nitorch estimate_noise,
+ * unires/_core.py:96-142; DESIGN 8.1 states the estimator).  Step 1: the masked range and 1024-bin
+ * histogram of n_obs observations in one pass.  ptrs / sizes / ct: HOST arrays of n_obs device
+ * pointers to float32 voxels, their counts (1 .. 2^32 - 1) and CT flags.  Voxels taken: finite,
+ * non-zero, and >= 0 unless ct[o].  counts: (n_obs, 1024) uint32 device, overwritten;
+ * range: (n_obs, 2) float32 device = (min, max) of the voxels taken (+inf, -inf when none).
+ * Bin of v: floor((v - min) * 1024 / (max - min)) in float64, clamped to 1023. */
+int unires_noise_hist(int32_t n_obs, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
+                      uint32_t *counts, float *range, void *stream);
+
+/* Step 2: a two-class float64 EM fit of every histogram in one launch - Rice when range min >= 0,
+ * Gaussian otherwise - stopped when the log-likelihood gains less than 1e-8 x the voxel count, or
+ * after max_iter M-steps.  out: (n_obs, 16) float64 device: mg0 mg1, nu|mu 0 1, sigma 0 1, class
+ * mean 0 1, final ll, M-steps, sd (sigma of the class with the smaller mean), |mean_fg - mean_bg|,
+ * model (0 Rice, 1 Gaussian, -1 = no voxels or min == max: only [12..15] are meaningful), sum of
+ * counts, min, max. */
+int unires_noise_fit(int32_t n_obs, const uint32_t *counts, const float *range, int32_t max_iter,
+                     double *out, void *stream);
+
 /* nitorch grid_grad(src, affine_grid(M, gdim), 'linear', bound='zero', extrapolate=False)
  * (_update.py:508, the rigid Gauss-Newton's spatial derivatives): gradient of the trilinear
  * sample w.r.t. the voxel coordinate; dst3 is (gdim, 3), component fastest. */

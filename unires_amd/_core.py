@@ -1,11 +1,14 @@
 """Initial guess of the reconstruction - counterparts of ``_init_y_dat``
 (unires/_core.py:371-399), of the label path ``_init_y_label`` /
-``_warp_label`` (:402-436) and of ``_resample_inplane`` (:457-492).  Everything else in the
-reference's ``_core.py`` (I/O, hyper-parameter estimation, coregistration, mean-space
+``_warp_label`` (:402-436), of ``_resample_inplane`` (:457-492), and of the hyper-parameter step
+``_estimate_hyperpar`` (:96-142) with the regularisation half of ``_format_y``, ``_init_lam``
+(:273-281).  Everything else in the reference's ``_core.py`` (I/O, coregistration, mean-space
 construction) is out of scope."""
+import math
+
 import torch
 
-from . import _ops
+from . import _ops, stats
 from .spatial import _mat_shape, _m12, voxel_size
 
 MAX_LABELS = 255  # the reference's limit (unires/_core.py:425)
@@ -100,3 +103,44 @@ def _resample_inplane(x, sett):
             xn.mat = torch.as_tensor(xn.mat).matmul(D.to(torch.as_tensor(xn.mat)))
             xn.dim = dim_x
     return x
+
+
+@_ops.on_device
+def _estimate_hyperpar(x, sett):
+    """Noise precision and mean foreground intensity of every observation (unires/_core.py:96-142):
+    ``x[c][n].sd``, ``.tau = 1 / sd**2`` and ``.mu = |mean_fg - mean_bg|`` from a two-class mixture
+    fit to the intensity histogram (``stats.estimate_noise``).  A non-CT observation
+    keeps its voxels >= 0.  One histogram launch and one fit launch for all observations, one read
+    back.  The values are float32 CPU scalars, with the reference's ``.float()`` arithmetic."""
+    obs = [(c, n) for c in range(len(x)) for n in range(len(x[c]))]
+    if not obs:
+        return x
+    counts, rng = stats.noise_hist([x[c][n].dat for c, n in obs], [bool(x[c][n].ct) for c, n in obs])
+    rows = stats.noise_fit(counts, rng).cpu()
+    for (c, n), row in zip(obs, rows):
+        if row[stats.MODEL] < 0:
+            raise ValueError('_estimate_hyperpar: channel %d, repeat %d has no usable voxels '
+                             '(finite, non-zero%s) or all of them are equal'
+                             % (c, n, '' if x[c][n].ct else ', >= 0'))
+        prm_noise, prm_not_noise = stats._noise_params(row)
+        sd_bg = prm_noise['sd'].float()
+        x[c][n].sd = sd_bg
+        x[c][n].tau = 1 / sd_bg ** 2
+        x[c][n].mu = torch.abs(prm_not_noise['mean'].float() - prm_noise['mean'].float())
+    return x
+
+
+def _init_lam(x, y, sett):
+    """Regularisation of every channel from the estimated intensities (the lambda half of
+    ``_format_y``, unires/_core.py:273-281): ``y[c].lam0 = y[c].lam = sqrt(1/C) / mean_n(mu)``, a CT
+    observation's ``mu`` divided by 4 in super-resolution.  Host arithmetic in float32."""
+    C = len(x)
+    for c in range(C):
+        mu_c = torch.zeros(len(x[c]), dtype=torch.float32)
+        for n in range(len(x[c])):
+            mu_c[n] = float(x[c][n].mu)
+            if x[c][n].ct and sett.method == 'super-resolution':
+                mu_c[n] /= 4
+        y[c].lam0 = math.sqrt(1 / C) / torch.mean(mu_c)
+        y[c].lam = math.sqrt(1 / C) / torch.mean(mu_c)
+    return y

@@ -22,6 +22,7 @@
 #include "cg.hpp"
 #include "fftpre.hpp"
 #include "fused.hpp"
+#include "noise.hpp"
 #include "ops.hpp"
 #include "orient.hpp"
 #include "pull2.hpp"
@@ -177,6 +178,50 @@ extern "C" int unires_pull3d_nearest(const float *src, const int32_t sdim[3], co
   Affine A;
   memcpy(A.m, M, sizeof(A.m));
   launch_pull_nearest(src, mk(sdim), A, dst, mk(gdim), fov_tol, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+// UNIRES_NOISE_HIST_FORM: 0 plain LDS atomics, 1 wave pre-aggregation (default; profiles/noise_time.json),
+// read at every call (tools/noise_time.py measures both in one process)
+static int noise_hist_form() {
+  const char *e = getenv("UNIRES_NOISE_HIST_FORM");
+  return e && *e ? (atoi(e) ? 1 : 0) : 1;
+}
+
+static int reduce_scratch(hipStream_t st, size_t ndoubles, double **out);
+
+extern "C" int unires_noise_hist(int32_t n_obs, const float *const *ptrs, const int64_t *sizes,
+                                 const int32_t *ct, uint32_t *counts, float *range, void *stream) {
+  if (!ptrs || !sizes || !ct || !counts || !range) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
+  size_t blocks = 0;
+  for (int32_t o = 0; o < n_obs; ++o) {
+    if (!ptrs[o]) return fail(UNIRES_ERR_NULL, "null observation pointer");
+    if (sizes[o] < 1 || sizes[o] > (int64_t)UINT32_MAX) return fail(UNIRES_ERR_DIM, "observation size out of range");
+    blocks += (size_t)noise_hist_blocks(sizes[o]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;  // one (min, max) float pair per workgroup
+  if (int rc = reduce_scratch(st, blocks, &part)) return rc;
+  HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_obs * kNoiseBins * sizeof(uint32_t), st));
+  for (int32_t o = 0; o < n_obs; o += kNoiseMaxObs) {
+    const int n = std::min<int32_t>(kNoiseMaxObs, n_obs - o);
+    size_t off = 0;  // a group's partials after the previous group's (one scratch, stream-ordered anyway)
+    for (int32_t q = 0; q < o; ++q) off += (size_t)noise_hist_blocks(sizes[q]);
+    launch_noise_hist(n, ptrs + o, sizes + o, ct + o, reinterpret_cast<float *>(part + off),
+                      counts + (size_t)o * kNoiseBins, range + 2 * (size_t)o, noise_hist_form(), st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
+extern "C" int unires_noise_fit(int32_t n_obs, const uint32_t *counts, const float *range,
+                                int32_t max_iter, double *out, void *stream) {
+  if (!counts || !range || !out) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
+  if (max_iter < 0) return fail(UNIRES_ERR_ARG, "max_iter must be >= 0");
+  launch_noise_fit(n_obs, counts, range, max_iter, out, (hipStream_t)stream);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
