@@ -119,6 +119,39 @@ int unires_noise_hist(int32_t n_obs, const float *const *ptrs, const int64_t *si
 int unires_noise_fit(int32_t n_obs, const uint32_t *counts, const float *range, int32_t max_iter,
                      double *out, void *stream);
 
+/* Rigid coregistration by (normalised) mutual information (the reference's _init_reg -> nitorch
+ * affine_align, unires/_core.py:310-368; DESIGN 8.2 states the estimator).  Step 1: uint8
+ * quantisation of n_obs observations.  ptrs / sizes / outs: HOST arrays of n_obs device pointers to
+ * float32 voxels, their counts (1 .. 2^32 - 1) and uint8 outputs of the same size.
+ * counts: (n_obs, 1024) uint32 device, overwritten: histogram of the finite voxels over [min, max].
+ * params: (n_obs, 8) float32 device, overwritten: min, max, robust maximum mx, 255 / (mx - min),
+ * status (0 ok, 1 no finite voxel, 2 all finite voxels equal: the output is all 0), 3 scratch. */
+int unires_coreg_quantise(int32_t n_obs, const float *const *ptrs, const int64_t *sizes,
+                          uint8_t *const *outs, uint32_t *counts, float *params, void *stream);
+
+/* One joint-histogram job: the fixed image G and the moving image F (uint8, C-contiguous,
+ * every dimension >= 2), M (float32 row-major 3x4) maps a G voxel to an F voxel, step: the
+ * sampling step in G voxels per axis (> 0). */
+typedef struct {
+  const uint8_t *G;
+  const uint8_t *F;
+  int32_t dim_g[3];
+  int32_t dim_f[3];
+  float M[12];
+  float step[3];
+} unires_coreg_job_t;
+
+/* Step 2: the partial-volume joint histograms of n_jobs jobs (HOST array) in one launch.
+ * hist: (n_jobs, 256, 256) uint64 device, overwritten: hist[j][g][f] in Q16 units (every sample
+ * point inside G adds 65536; a point whose image falls outside F counts as f = 0).  At most 2^31 - 1 sample points per job. */
+int unires_coreg_hist(int32_t n_jobs, const unires_coreg_job_t *jobs, uint64_t *hist, void *stream);
+
+/* Step 3: the cost of n histograms in one launch.  cost_fun: 0 'nmi', 1 'mi', 2 'ecc'; fwhm: the
+ * histogram smoothing in bins (0 <= fwhm <= 16).  work: n x 2 x 256 x 256 float64 device scratch;
+ * cost: (n,) float64 device. */
+int unires_coreg_cost(int32_t n, const uint64_t *hist, int32_t cost_fun, double fwhm, double *work,
+                      double *cost, void *stream);
+
 /* nitorch grid_grad(src, affine_grid(M, gdim), 'linear', bound='zero', extrapolate=False)
  * (_update.py:508, the rigid Gauss-Newton's spatial derivatives): gradient of the trilinear
  * sample w.r.t. the voxel coordinate; dst3 is (gdim, 3), component fastest. */

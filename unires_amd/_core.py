@@ -2,13 +2,14 @@
 (unires/_core.py:371-399), of the label path ``_init_y_label`` /
 ``_warp_label`` (:402-436), of ``_resample_inplane`` (:457-492), and of the hyper-parameter step
 ``_estimate_hyperpar`` (:96-142) with the regularisation half of ``_format_y``, ``_init_lam``
-(:273-281).  Everything else in the reference's ``_core.py`` (I/O, coregistration, mean-space
-construction) is out of scope."""
+(:273-281), and of the coregistration step ``_init_reg`` (:310-368).  Everything else in the
+reference's ``_core.py`` (I/O, atlas alignment, mean-space construction) is out of scope."""
 import math
 
 import torch
 
-from . import _ops, stats
+from . import _ops, preproc, stats
+from ._rigid import affine_basis
 from .spatial import _mat_shape, _m12, voxel_size
 
 MAX_LABELS = 255  # the reference's limit (unires/_core.py:425)
@@ -144,3 +145,30 @@ def _init_lam(x, y, sett):
         y[c].lam0 = math.sqrt(1 / C) / torch.mean(mu_c)
         y[c].lam = math.sqrt(1 / C) / torch.mean(mu_c)
     return y
+
+
+def _init_reg(x, sett):
+    """Initialise registration (unires/_core.py:310-368): ``sett.rigid_basis = affine_basis('SE')``;
+    with ``sett.do_coreg`` and more than one observation, every observation is aligned rigidly to
+    the observation of flat index ``sett.fix`` (``preproc.affine_align`` with
+    ``sett.coreg_params``), ``sett.mat_coreg`` keeps the transforms and
+    ``x[c][n].mat = mat_a[i] \\ x[c][n].mat``; every ``x[c][n].rigid_q`` is set to zeros(6).
+    Labels are not touched (they share their image's orientation).  Atlas alignment is not built."""
+    if sett.do_atlas_align:
+        raise NotImplementedError('_init_reg: atlas alignment (do_atlas_align) is not built')
+    N = sum(len(xc) for xc in x)
+    sett.rigid_basis = affine_basis(group='SE', dtype=torch.float64)
+    if sett.do_coreg and N > 1:
+        imgs = [[x[c][n].dat, x[c][n].mat] for c in range(len(x)) for n in range(len(x[c]))]
+        mat_a = preproc.affine_align(imgs, **sett.coreg_params, fix=sett.fix, device=sett.device)[1]
+        sett.mat_coreg = mat_a
+        i = 0
+        for c in range(len(x)):
+            for n in range(len(x[c])):
+                mat = torch.as_tensor(x[c][n].mat, dtype=torch.float64)
+                x[c][n].mat = torch.linalg.solve(mat_a[i].to(mat), mat)
+                i += 1
+    for c in range(len(x)):
+        for n in range(len(x[c])):
+            x[c][n].rigid_q = torch.zeros(sett.rigid_basis.shape[0], device=sett.device, dtype=torch.float64)
+    return x, sett

@@ -3,6 +3,7 @@
 // _proj_apply / _proj('AtA') / the y-update RHS / nitorch-style cg().
 // Nothing here touches torch; the caller hands over raw device pointers and a
 // hipStream_t.
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +20,7 @@
 
 #include "admm.hpp"
 #include "aligned.hpp"
+#include "coreg.hpp"
 #include "cg.hpp"
 #include "fftpre.hpp"
 #include "fused.hpp"
@@ -222,6 +224,72 @@ extern "C" int unires_noise_fit(int32_t n_obs, const uint32_t *counts, const flo
   if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
   if (max_iter < 0) return fail(UNIRES_ERR_ARG, "max_iter must be >= 0");
   launch_noise_fit(n_obs, counts, range, max_iter, out, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_quantise(int32_t n_obs, const float *const *ptrs, const int64_t *sizes,
+                                     uint8_t *const *outs, uint32_t *counts, float *params, void *stream) {
+  if (!ptrs || !sizes || !outs || !counts || !params) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
+  for (int32_t o = 0; o < n_obs; ++o) {
+    if (!ptrs[o] || !outs[o]) return fail(UNIRES_ERR_NULL, "null observation pointer");
+    if (sizes[o] < 1 || sizes[o] > (int64_t)UINT32_MAX) return fail(UNIRES_ERR_DIM, "observation size out of range");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int32_t o = 0; o < n_obs; o += kCoregMaxObs) {
+    const int n = std::min<int32_t>(kCoregMaxObs, n_obs - o);
+    launch_coreg_quantise(n, ptrs + o, sizes + o, outs + o, counts + (size_t)o * kCoregQBins,
+                          params + (size_t)o * kCoregQOut, st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_hist(int32_t n_jobs, const unires_coreg_job_t *jobs, uint64_t *hist, void *stream) {
+  static_assert(sizeof(unires_coreg_job_t) == sizeof(CoregJobHost), "job layout");
+  if (!jobs || !hist) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_jobs < 1) return fail(UNIRES_ERR_ARG, "n_jobs must be >= 1");
+  const CoregJobHost *J = reinterpret_cast<const CoregJobHost *>(jobs);
+  for (int32_t o = 0; o < n_jobs; ++o) {
+    if (!J[o].G || !J[o].F) return fail(UNIRES_ERR_NULL, "null volume pointer");
+    for (int d = 0; d < 3; ++d) {
+      if (J[o].dim_g[d] < 2 || J[o].dim_f[d] < 2) return fail(UNIRES_ERR_DIM, "every dimension must be >= 2");
+      if (!(J[o].step[d] > 0.f) || !(J[o].step[d] <= 3.0e38f)) return fail(UNIRES_ERR_ARG, "step must be finite and > 0");
+    }
+    if (!dims_ok(J[o].dim_g) || !dims_ok(J[o].dim_f)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+    int32_t ng[3];
+    if (coreg_grid(J[o], ng) > (int64_t)INT32_MAX) return fail(UNIRES_ERR_DIM, "more than 2^31 - 1 sample points");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)n_jobs * kCoregBins * kCoregBins * sizeof(uint64_t), st));
+  for (int32_t o = 0; o < n_jobs; o += kCoregMaxJobs) {
+    const int n = std::min<int32_t>(kCoregMaxJobs, n_jobs - o);
+    launch_coreg_hist(n, J + o, hist + (size_t)o * kCoregBins * kCoregBins, st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_cost(int32_t n, const uint64_t *hist, int32_t cost_fun, double fwhm, double *work,
+                                 double *cost, void *stream) {
+  if (!hist || !work || !cost) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n < 1) return fail(UNIRES_ERR_ARG, "n must be >= 1");
+  if (cost_fun < 0 || cost_fun > 2) return fail(UNIRES_ERR_ARG, "cost_fun must be 0 (nmi), 1 (mi) or 2 (ecc)");
+  if (!(fwhm >= 0.0 && fwhm <= 16.0)) return fail(UNIRES_ERR_ARG, "fwhm must be in [0, 16]");
+  // SPM's histogram kernel (spm_coreg's smoothing_kernel): a Gaussian of the given FWHM convolved
+  // with the unit box, over -round(2 fwhm) .. round(2 fwhm), normalised to sum 1
+  const int R = (int)lround(2.0 * fwhm);
+  double taps[2 * kCoregMaxTapRadius + 1];
+  const double s = pow(fwhm / sqrt(8.0 * log(2.0)), 2) + DBL_EPSILON, w1 = 1.0 / sqrt(2.0 * s);
+  double sum = 0.0;
+  for (int k = -R; k <= R; ++k) {
+    const double v = 0.5 * (erf(w1 * (k + 0.5)) - erf(w1 * (k - 0.5)));
+    taps[k + R] = v > 0.0 ? v : 0.0;
+    sum += taps[k + R];
+  }
+  for (int k = 0; k <= 2 * R; ++k) taps[k] /= sum;
+  launch_coreg_cost(n, hist, cost_fun, taps, R, work, cost, (hipStream_t)stream);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

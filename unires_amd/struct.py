@@ -110,3 +110,9 @@ class settings:
         self.force_inplane_res = False
         # reconstruction voxel size: a scalar or one per axis (unires/struct.py:109)
         self.vx = 1.0
+        # coregistration of the observations (_core._init_reg; unires/struct.py:72-75, 90-93)
+        self.do_coreg = True
+        self.coreg_params = {'cost_fun': 'nmi', 'group': 'SE', 'samp': 1, 'fwhm': 7, 'mean_space': False}
+        self.fix = 0  # flat index (channels, then repeats) of the observation the others align to
+        self.do_atlas_align = False
+        self.mat_coreg = None  # (N, 4, 4) float64 transforms _init_reg found
