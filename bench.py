@@ -8,8 +8,14 @@ iterations of (tau AtA + rho lam^2 DtD) y = b in fixed-iteration mode
 (tolerance 0 - no early stop, so the work per step is constant).
 
 metric  = per-channel CG iterations per second, whole job (all ranks).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the line.  With --full it then also measures (never the headline):
+subjects_per_sec = complete ADMM iterations of one subject, fixed-iteration and
+           under the reference's default stopping rule.
 roofline = the CG matvec (AtA + rho lam^2 DtD) for one channel, algorithmic
            bytes B_mv = 4*(2 N_y + 2 N_x) / measured duration.
+variants = the reference-faithful CG and the rigid = identity subject.
 cpu_baseline = the CPU oracle (torch-CPU restatement of the reference path)
            timed on a bounded sample of the same workload on this box's cores.
 
@@ -369,6 +375,154 @@ def variants(name, x, y, z, w, rho, tmp, sett, device):
     return out
 
 
+def full_records(args, wl, x, y, z, w, rho, tmp, sett, step, device, rank, world):
+    """What `--full` adds to the line, measured after the timed steps (and after --dump-outputs has written what
+    they computed): subjects/sec under both stopping rules (every rank runs its subject), and on rank 0 the matvec
+    roofline, the job with one channel after the other, the variants and the CPU baseline.  Returns those records
+    on rank 0, None on the others."""
+    import torch.distributed as td
+    import unires_amd as U
+    dist = world > 1
+    C = wl['C']
+    iters_per_step = C * sett.cgs_max_iter
+    # subjects/sec (SURVEY 8(d)): EVERY rank runs n_admm full ADMM iterations (y-update C x 20 CG,
+    # objective, z- and w-update) of its own subject between barriers; time = max over ranks
+    n_admm = max(1, args.admm_iters)
+    sett.tolerance = 1e-4
+
+    def subject_leg(cgs_tol):
+        """One subject from a zero start (y, z, w): warm-up iteration, then n_admm timed ones.  Returns
+        (max over ranks, this rank's own time, every rank's time)."""
+        keep = sett.cgs_tol
+        sett.cgs_tol = cgs_tol
+        try:
+            for yc in y:
+                yc.dat.zero_()
+            z.zero_(), w.zero_()
+            obj = torch.zeros((n_admm + 1, 3), dtype=torch.float64, device=device)
+            U._update_admm(x, y, z, w, rho, tmp, obj, 0, sett)  # warm-up (plans, graphs)
+            torch.cuda.synchronize()
+            if dist:
+                td.barrier()
+                torch.cuda.synchronize()
+            ta = time.perf_counter()
+            for it in range(1, n_admm + 1):
+                U._update_admm(x, y, z, w, rho, tmp, obj, it, sett)
+            torch.cuda.synchronize()
+            own = time.perf_counter() - ta  # this rank's own subject, before it waits for the others
+            if dist:
+                td.barrier()
+                torch.cuda.synchronize()
+            t_all = time.perf_counter() - ta
+            per_rank = [own]
+            if dist:
+                t = torch.tensor([t_all], dtype=torch.float64, device=device)
+                td.all_reduce(t, op=td.ReduceOp.MAX)
+                t_all = float(t.item())
+                g = [torch.zeros(1, dtype=torch.float64, device=device) for _ in range(world)]
+                td.all_gather(g, torch.tensor([own], dtype=torch.float64, device=device))
+                per_rank = [float(v.item()) for v in g]
+            return t_all, own, per_rank
+        finally:
+            sett.cgs_tol = keep
+
+    t_subject, _, t_subject_ranks = subject_leg(0.0)
+    # the same subject with the reference's DEFAULT solver settings (struct.py:65-67: cgs_tol = 1e-3,
+    # 'max_gain'): the solves stop where the reference's would
+    t_subject_tol, _, t_subject_tol_ranks = subject_leg(1e-3) if not args.no_tol_leg else (None, None, [])
+    if rank != 0:
+        return None
+    # the headline figure is ONE fixed method (r1's): plain launches on the stream, HIP events around
+    # them - the figure that must agree with the rocprofv3 kernel durations committed under
+    # profiles/ (kernel sum 123.3 us vs 123 - 125 us by events; a hipGraph replay of the same launches
+    # carries ~2.5 us of barrier packet per kernel and is reported next to it, never mixed in)
+    t_mv_graph = time_matvec(x, y, rho, sett)
+    t_mv_eager = time_matvec(x, y, rho, sett, graph=False)
+    # (r3) the headline figure is the operator application as the timed region runs it: every A(p) of
+    # one y-update's CG solves between HIP events recorded by the library on its launch stream.  Since
+    # the iterate x is streamed past the caches the solver's matvecs find p warm, and the cold-operand
+    # figure (kept as us_per_launch_cold) came out ~5 % above the kernel durations rocprofv3 reports
+    # for this command.
+    t_mv, n_mv = time_matvec_in_solve(x, y, z, w, rho, tmp, sett)
+    t_mv_ingraph, t_yu1, t_yu2 = time_matvec_in_graph(x, y, z, w, rho, tmp, sett)
+    streams_on = bool(U._update.channel_streams_on(sett, y[0].dat)) and C > 1
+    t_mv_shared = time_matvec_in_solve(x, y, z, w, rho, tmp, sett, serial=False)[0] if streams_on else None
+    # ... and the job the other way round: the same steps with one channel after the other
+    value_serial = None
+    if streams_on and world == 1:
+        keep_cs = sett.channel_streams
+        sett.channel_streams = False
+        try:
+            # (three warm-up steps: the plans leave the shared-chip mode, their solves are captured anew, and the
+            # SECOND replay of a fresh graph still costs ~30 ms on this runtime - one warm-up step read 3 100 it/s)
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            value_serial = args.steps * iters_per_step / (time.perf_counter() - ts)
+        finally:
+            sett.channel_streams = keep_cs
+    per_channel = [time_matvec(x, y, rho, sett, ring=4, channels=[c], graph=False) * 1e6 for c in range(len(x))]
+    b_mv = alg_bytes_matvec(x[0], wl['dim_y'], sett.do_proj)
+    achieved = b_mv / t_mv / 1e9
+    traffic = pmc_traffic(args.workload)
+    out = {
+        # `value` with one channel after the other (settings.channel_streams = False), same steps
+        'value_channels_serial': value_serial,
+        'subjects_per_sec': world / t_subject,
+        'subjects_per_sec_note': 'subject = %d full ADMM iterations (y-update C x 20 CG, objective, z- and '
+                                 'w-update) run on every rank between barriers, max over ranks: %.3f s '
+                                 '(%.2f ms per ADMM iteration)' % (n_admm, t_subject, t_subject / n_admm * 1e3),
+        # the reference's default solver settings (cgs_tol = 1e-3, stop 'max_gain', struct.py:65-67)
+        'subjects_per_sec_tol1e-3': world / t_subject_tol if t_subject_tol else None,
+        'subjects_per_sec_tol1e-3_note': 'the same %d ADMM iterations with every CG solve stopping where the '
+                                         "reference's does (tolerance 1e-3 on the gain of the objective): %.3f s "
+                                         '(%.2f ms per ADMM iteration)' % (n_admm, t_subject_tol or 0.0,
+                                                                         (t_subject_tol or 0.0) / n_admm * 1e3),
+        # every rank's own time for its subject, before the closing barrier (s): a scaling run explains itself
+        't_subject_per_rank': {'min': min(t_subject_ranks), 'max': max(t_subject_ranks), 'all': t_subject_ranks},
+        't_subject_tol1e-3_per_rank': ({'min': min(t_subject_tol_ranks), 'max': max(t_subject_tol_ranks),
+                                        'all': t_subject_tol_ranks} if t_subject_tol_ranks else None),
+        'roofline': {'bound': 'hbm', 'kernel': 'ata_matvec (per launch inside the CG solves of one y-update, mean over channels)',
+                     'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                     'frac': achieved / HBM_PEAK_GBS,
+                     # HBM bytes per launch from the PMC counters (null if no profile of this workload is
+                     # committed); STATIC: read from the committed profile named in traffic_source
+                     'traffic': (traffic or {}).get('bytes_per_launch'), 'traffic_source': traffic,
+                     'alg_bytes_per_launch': b_mv, 'us_per_launch': t_mv * 1e6,
+                     'launches_timed': n_mv,
+                     # the same launches as the TIMED REGION runs them when the channels share the chip
+                     # (streams of their own, persistent grids sized for it): longer launches, a faster job
+                     'us_per_launch_channels_overlapped': None if t_mv_shared is None else t_mv_shared * 1e6,
+                     # ... and inside the replayed hipGraph that a fixed-iteration solve is in production (no host
+                     # launch latency): (y-update with every A(p) enqueued twice - plain y-update) / applications
+                     'us_per_launch_in_graph': t_mv_ingraph * 1e6,
+                     'frac_in_graph': b_mv / t_mv_ingraph / 1e9 / HBM_PEAK_GBS,
+                     'in_graph_y_update_ms': [t_yu1 * 1e3, t_yu2 * 1e3],
+                     'us_per_launch_cold': t_mv_eager * 1e6, 'frac_cold': b_mv / t_mv_eager / 1e9 / HBM_PEAK_GBS,
+                     'us_per_launch_graph': t_mv_graph * 1e6, 'us_per_launch_eager': t_mv_eager * 1e6,
+                     'us_per_launch_by_channel': per_channel,
+                     'timing': 'us_per_launch: HIP events recorded by the library around every A(p) of one '
+                               "y-update's CG solves, on the stream they are launched on (plain launches), one "
+                               'channel after the other - the kernels alone on the chip; '
+                               '_in_graph: marginal cost of an A(p) inside the hipGraph a tol = 0 solve is '
+                               'replayed as (doubled-matvec solves minus plain ones, medians of 10); '
+                               '_channels_overlapped: the same with the channels on streams of their own, as '
+                               "`value`'s timed region runs them; "
+                               '_cold = _eager: stand-alone launches cycling through more p / q buffers than the '
+                               'Infinity Cache holds (the round-2 method), _graph: those replayed as one hipGraph, '
+                               '_by_channel: cold, one channel at a time'},
+    }
+    if world == 1 and not args.no_variants:
+        out['variants'] = variants(args.workload, x, y, z, w, rho, tmp, sett, device)
+    if not args.no_cpu_baseline and world == 1:
+        out['cpu_baseline'] = cpu_baseline(wl, args.cpu_seconds, device=device)
+    return out
+
+
 def spawn_ranks(n, argv, dry_run=False):
     """`python bench.py --gpus N` without a launcher: run N ranks (one per GPU, RCCL) through
     torch.distributed.run on 127.0.0.1, exactly as the driver's command line does."""
@@ -390,6 +544,11 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='cfg3_256c3_thick6z', choices=list(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also measure what the headline figure does not need: subjects/sec '
+                         'under both stopping rules, the matvec roofline, the job with one channel after the other, '
+                         'the variants and the CPU baseline (with its full-size parity check); the --no-* options '
+                         'below, --cpu-seconds and --admm-iters shape these legs')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-variants', action='store_true')
     ap.add_argument('--serial-channels', action='store_true',
@@ -471,90 +630,8 @@ def main():
     C = wl['C']
     iters_per_step = C * sett.cgs_max_iter
     total_iters = world * args.steps * iters_per_step
-    # subjects/sec: EVERY rank runs n_admm full ADMM iterations (y-update C x 20 CG,
-    # objective, z- and w-update) of its own subject between barriers; time = max over ranks
-    n_admm = max(1, args.admm_iters)
-    sett.tolerance = 1e-4
-
-    def subject_leg(cgs_tol):
-        """One subject from a zero start (y, z, w): warm-up iteration, then n_admm timed ones.  Returns
-        (max over ranks, this rank's own time, every rank's time)."""
-        keep = sett.cgs_tol
-        sett.cgs_tol = cgs_tol
-        try:
-            for yc in y:
-                yc.dat.zero_()
-            z.zero_(), w.zero_()
-            obj = torch.zeros((n_admm + 1, 3), dtype=torch.float64, device=device)
-            U._update_admm(x, y, z, w, rho, tmp, obj, 0, sett)  # warm-up (plans, graphs)
-            torch.cuda.synchronize()
-            if dist:
-                td.barrier()
-                torch.cuda.synchronize()
-            ta = time.perf_counter()
-            for it in range(1, n_admm + 1):
-                U._update_admm(x, y, z, w, rho, tmp, obj, it, sett)
-            torch.cuda.synchronize()
-            own = time.perf_counter() - ta  # this rank's own subject, before it waits for the others
-            if dist:
-                td.barrier()
-                torch.cuda.synchronize()
-            t_all = time.perf_counter() - ta
-            per_rank = [own]
-            if dist:
-                t = torch.tensor([t_all], dtype=torch.float64, device=device)
-                td.all_reduce(t, op=td.ReduceOp.MAX)
-                t_all = float(t.item())
-                g = [torch.zeros(1, dtype=torch.float64, device=device) for _ in range(world)]
-                td.all_gather(g, torch.tensor([own], dtype=torch.float64, device=device))
-                per_rank = [float(v.item()) for v in g]
-            return t_all, own, per_rank
-        finally:
-            sett.cgs_tol = keep
-
-    t_subject, _, t_subject_ranks = subject_leg(0.0)
-    # the same subject with the reference's DEFAULT solver settings (struct.py:65-67: cgs_tol = 1e-3,
-    # 'max_gain'): the solves stop where the reference's would
-    t_subject_tol, _, t_subject_tol_ranks = subject_leg(1e-3) if not args.no_tol_leg else (None, None, [])
-    out = None
+    full = full_records(args, wl, x, y, z, w, rho, tmp, sett, step, device, rank, world) if args.full else None
     if rank == 0:
-        # the headline figure is ONE fixed method (r1's): plain launches on the stream, HIP events around
-        # them - the figure that must agree with the rocprofv3 kernel durations committed under
-        # profiles/ (kernel sum 123.3 us vs 123 - 125 us by events; a hipGraph replay of the same launches
-        # carries ~2.5 us of barrier packet per kernel and is reported next to it, never mixed in)
-        t_mv_graph = time_matvec(x, y, rho, sett)
-        t_mv_eager = time_matvec(x, y, rho, sett, graph=False)
-        # (r3) the headline figure is the operator application as the timed region runs it: every A(p) of
-        # one y-update's CG solves between HIP events recorded by the library on its launch stream.  Since
-        # the iterate x is streamed past the caches the solver's matvecs find p warm, and the cold-operand
-        # figure (kept as us_per_launch_cold) came out ~5 % above the kernel durations rocprofv3 reports
-        # for this command.
-        t_mv, n_mv = time_matvec_in_solve(x, y, z, w, rho, tmp, sett)
-        t_mv_ingraph, t_yu1, t_yu2 = time_matvec_in_graph(x, y, z, w, rho, tmp, sett)
-        streams_on = bool(U._update.channel_streams_on(sett, y[0].dat)) and C > 1
-        t_mv_shared = time_matvec_in_solve(x, y, z, w, rho, tmp, sett, serial=False)[0] if streams_on else None
-        # ... and the job the other way round: the same steps with one channel after the other
-        value_serial = None
-        if streams_on and world == 1:
-            keep_cs = sett.channel_streams
-            sett.channel_streams = False
-            try:
-                # (three warm-up steps: the plans leave the shared-chip mode, their solves are captured anew, and the
-                # SECOND replay of a fresh graph still costs ~30 ms on this runtime - one warm-up step read 3 100 it/s)
-                for _ in range(3):
-                    step()
-                torch.cuda.synchronize()
-                ts = time.perf_counter()
-                for _ in range(args.steps):
-                    step()
-                torch.cuda.synchronize()
-                value_serial = args.steps * iters_per_step / (time.perf_counter() - ts)
-            finally:
-                sett.channel_streams = keep_cs
-        per_channel = [time_matvec(x, y, rho, sett, ring=4, channels=[c], graph=False) * 1e6 for c in range(len(x))]
-        b_mv = alg_bytes_matvec(x[0], wl['dim_y'], sett.do_proj)
-        achieved = b_mv / t_mv / 1e9
-        traffic = pmc_traffic(args.workload)
         out = {
             'metric': 'cg_iters_per_sec', 'value': total_iters / elapsed, 'unit': 'cg_iters/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -567,58 +644,11 @@ def main():
                        'channel_streams': bool(U._update.channel_streams_on(sett, y[0].dat)),
                        'channel_streams_setting': getattr(sett, 'channel_streams', 'auto'),
                        'parallelism': 'one subject per GPU, no data-path collective'},
-            # `value` with one channel after the other (settings.channel_streams = False), same steps
-            'value_channels_serial': value_serial,
-            'subjects_per_sec': world / t_subject,
-            'subjects_per_sec_note': 'subject = %d full ADMM iterations (y-update C x 20 CG, objective, z- and '
-                                     'w-update) run on every rank between barriers, max over ranks: %.3f s '
-                                     '(%.2f ms per ADMM iteration)' % (n_admm, t_subject, t_subject / n_admm * 1e3),
-            # the reference's default solver settings (cgs_tol = 1e-3, stop 'max_gain', struct.py:65-67)
-            'subjects_per_sec_tol1e-3': world / t_subject_tol if t_subject_tol else None,
-            'subjects_per_sec_tol1e-3_note': 'the same %d ADMM iterations with every CG solve stopping where the '
-                                             "reference's does (tolerance 1e-3 on the gain of the objective): %.3f s "
-                                             '(%.2f ms per ADMM iteration)' % (n_admm, t_subject_tol or 0.0,
-                                                                             (t_subject_tol or 0.0) / n_admm * 1e3),
-            # every rank's own time for its subject, before the closing barrier (s): a scaling run explains itself
-            't_subject_per_rank': {'min': min(t_subject_ranks), 'max': max(t_subject_ranks), 'all': t_subject_ranks},
-            't_subject_tol1e-3_per_rank': ({'min': min(t_subject_tol_ranks), 'max': max(t_subject_tol_ranks),
-                                            'all': t_subject_tol_ranks} if t_subject_tol_ranks else None),
-            'roofline': {'bound': 'hbm', 'kernel': 'ata_matvec (per launch inside the CG solves of one y-update, mean over channels)',
-                         'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS,
-                         # HBM bytes per launch from the PMC counters (null if no profile of this workload is
-                         # committed); STATIC: read from the committed profile named in traffic_source
-                         'traffic': (traffic or {}).get('bytes_per_launch'), 'traffic_source': traffic,
-                         'alg_bytes_per_launch': b_mv, 'us_per_launch': t_mv * 1e6,
-                         'launches_timed': n_mv,
-                         # the same launches as the TIMED REGION runs them when the channels share the chip
-                         # (streams of their own, persistent grids sized for it): longer launches, a faster job
-                         'us_per_launch_channels_overlapped': None if t_mv_shared is None else t_mv_shared * 1e6,
-                         # ... and inside the replayed hipGraph that a fixed-iteration solve is in production (no host
-                         # launch latency): (y-update with every A(p) enqueued twice - plain y-update) / applications
-                         'us_per_launch_in_graph': t_mv_ingraph * 1e6,
-                         'frac_in_graph': b_mv / t_mv_ingraph / 1e9 / HBM_PEAK_GBS,
-                         'in_graph_y_update_ms': [t_yu1 * 1e3, t_yu2 * 1e3],
-                         'us_per_launch_cold': t_mv_eager * 1e6, 'frac_cold': b_mv / t_mv_eager / 1e9 / HBM_PEAK_GBS,
-                         'us_per_launch_graph': t_mv_graph * 1e6, 'us_per_launch_eager': t_mv_eager * 1e6,
-                         'us_per_launch_by_channel': per_channel,
-                         'timing': 'us_per_launch: HIP events recorded by the library around every A(p) of one '
-                                   "y-update's CG solves, on the stream they are launched on (plain launches), one "
-                                   'channel after the other - the kernels alone on the chip; '
-                                   '_in_graph: marginal cost of an A(p) inside the hipGraph a tol = 0 solve is '
-                                   'replayed as (doubled-matvec solves minus plain ones, medians of 10); '
-                                   '_channels_overlapped: the same with the channels on streams of their own, as '
-                                   "`value`'s timed region runs them; "
-                                   '_cold = _eager: stand-alone launches cycling through more p / q buffers than the '
-                                   'Infinity Cache holds (the round-2 method), _graph: those replayed as one hipGraph, '
-                                   '_by_channel: cold, one channel at a time'},
         }
+        if full is not None:
+            out.update(full)
         if dumped is not None:
             out['dumped_outputs'] = {'dir': args.dump_outputs, 'shapes': dumped}
-        if world == 1 and not args.no_variants:
-            out['variants'] = variants(args.workload, x, y, z, w, rho, tmp, sett, device)
-        if not args.no_cpu_baseline and world == 1:
-            out['cpu_baseline'] = cpu_baseline(wl, args.cpu_seconds, device=device)
         print(json.dumps(out))
         sys.stdout.flush()
     if dist:

@@ -5,7 +5,7 @@
 #   usage: tools/ab.sh <variant file>
 cd $GRAFT_REPO_ROOT
 last="__none__"
-b() { python bench.py --no-cpu-baseline --no-variants --admm-iters 2 "$@" 2>/dev/null | grep '^{"metric"' | python -c "
+b() { python bench.py --full --no-cpu-baseline --no-variants --admm-iters 2 "$@" 2>/dev/null | grep '^{"metric"' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('%-28s it/s %8.0f  ms/step %7.3f  matvec %7.1f us (cold: graph %.1f eager %.1f)  frac %.3f' % (d['config']['workload'], d['value'], d['ms_per_step'], r['us_per_launch'], r['us_per_launch_graph'], r['us_per_launch_eager'], r['frac']))"; }

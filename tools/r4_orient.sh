@@ -5,11 +5,11 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r04; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 for wl in cfg3_256c3_thick6_orient cfg3_256c3_thick6xyz; do
-  UNIRES_PULL2_VERBOSE=1 UNIRES_SPLAT2_VERBOSE=1 python bench.py --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 \
+  UNIRES_PULL2_VERBOSE=1 UNIRES_SPLAT2_VERBOSE=1 python bench.py --full --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 \
     2>$OUT/plan_$wl.err | grep '^{"metric"' > $OUT/bench_$wl.json
   grep '^\[pull2\]\|^\[splat2\]' $OUT/plan_$wl.err | sort | uniq -c > $OUT/r04_plan_lines_$wl.txt
 done
-UNIRES_NO_CANON=1 python bench.py --workload cfg3_256c3_thick6_orient --no-cpu-baseline --no-variants --admm-iters 10 \
+UNIRES_NO_CANON=1 python bench.py --full --workload cfg3_256c3_thick6_orient --no-cpu-baseline --no-variants --admm-iters 10 \
   2>/dev/null | grep '^{"metric"' > $OUT/bench_cfg3_256c3_thick6_orient_nocanon.json
 python - <<'PY'
 import json, os

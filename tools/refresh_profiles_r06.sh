@@ -20,28 +20,28 @@ for wl in cfg2_181c3_1mm dn_256c3_1mm; do
 done >> $OUT/r06_traffic_other_configs.jsonl 2>>$OUT/traffic.err
 fi
 if has 2; then
-# 2. the driver's command: one bench line (with cpu_baseline and variants)
-python bench.py > $OUT/bench.log 2>&1; grep '^{"metric"' $OUT/bench.log | tail -1 > $OUT/r06_bench.json
+# 2. the full bench line (--full: with roofline, subjects/s, cpu_baseline and variants)
+python bench.py --full > $OUT/bench.log 2>&1; grep '^{"metric"' $OUT/bench.log | tail -1 > $OUT/r06_bench.json
 fi
 if has 3; then
 # 3. rocprofv3 --kernel-trace --stats of the same command and of the explicitly serial form; + one bench line
 #    with the three channel streams forced
-cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kt1 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt1 -o k -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-variants --admm-iters 5 > $OUT/bench_prof_default.log 2>&1
-cp /tmp/kt1/k_kernel_stats.csv $OUT/r06_bench_kernel_stats.csv
-rm -rf /tmp/kt2 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt2 -o k -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-variants --serial-channels --admm-iters 5 > $OUT/bench_prof_serial.log 2>&1
-cp /tmp/kt2/k_kernel_stats.csv $OUT/r06_bench_serial_kernel_stats.csv
+REPO=$PWD; KT=$(mktemp -d); cd $KT && export TMPDIR=$KT
+rm -rf kt1 && rocprofv3 --kernel-trace --stats --output-format csv -d kt1 -o k -- python $REPO/bench.py --full --no-cpu-baseline --no-variants --admm-iters 5 > $OUT/bench_prof_default.log 2>&1
+cp kt1/k_kernel_stats.csv $OUT/r06_bench_kernel_stats.csv
+rm -rf kt2 && rocprofv3 --kernel-trace --stats --output-format csv -d kt2 -o k -- python $REPO/bench.py --full --no-cpu-baseline --no-variants --serial-channels --admm-iters 5 > $OUT/bench_prof_serial.log 2>&1
+cp kt2/k_kernel_stats.csv $OUT/r06_bench_serial_kernel_stats.csv
 grep '^{"metric"' $OUT/bench_prof_serial.log | tail -1 > $OUT/r06_bench_serial.json
 # ... and the same without the leg under the reference's stopping rule: every matvec launch of this run is a real one (the
 # guarded rule's launches that return at entry deflate the averages above: k_splat2 61 us over 4 233 calls)
-rm -rf /tmp/kt2b && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt2b -o k -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-variants --no-tol-leg --serial-channels --admm-iters 5 > $OUT/bench_prof_serial_fixed.log 2>&1
-cp /tmp/kt2b/k_kernel_stats.csv $OUT/r06_bench_serial_fixed_kernel_stats.csv
+rm -rf kt2b && rocprofv3 --kernel-trace --stats --output-format csv -d kt2b -o k -- python $REPO/bench.py --full --no-cpu-baseline --no-variants --no-tol-leg --serial-channels --admm-iters 5 > $OUT/bench_prof_serial_fixed.log 2>&1
+cp kt2b/k_kernel_stats.csv $OUT/r06_bench_serial_fixed_kernel_stats.csv
 grep '^{"metric"' $OUT/bench_prof_serial_fixed.log | tail -1 > $OUT/r06_bench_serial_fixed.json
-python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-variants --channel-streams --admm-iters 5 2>/dev/null | grep '^{"metric"' | tail -1 > $OUT/r06_bench_streams.json
+python $REPO/bench.py --full --no-cpu-baseline --no-variants --channel-streams --admm-iters 5 2>/dev/null | grep '^{"metric"' | tail -1 > $OUT/r06_bench_streams.json
 # ... and of config 2 (the single-pass kernel inside the CG solves)
-rm -rf /tmp/kt3 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt3 -o k -- python $GRAFT_REPO_ROOT/bench.py --workload cfg2_181c3_1mm --no-cpu-baseline --no-variants --serial-channels --admm-iters 5 > $OUT/bench_prof_cfg2.log 2>&1
-cp /tmp/kt3/k_kernel_stats.csv $OUT/r06_bench_cfg2_serial_kernel_stats.csv
-cd $GRAFT_REPO_ROOT
+rm -rf kt3 && rocprofv3 --kernel-trace --stats --output-format csv -d kt3 -o k -- python $REPO/bench.py --full --workload cfg2_181c3_1mm --no-cpu-baseline --no-variants --serial-channels --admm-iters 5 > $OUT/bench_prof_cfg2.log 2>&1
+cp kt3/k_kernel_stats.csv $OUT/r06_bench_cfg2_serial_kernel_stats.csv
+cd $REPO
 fi
 if has 4; then
 # 4. SQ counters: the config-3 matvec kernels, and the single-pass kernel on config 2 and at 256^3
@@ -53,14 +53,14 @@ if has 5; then
 # 5. one bench line per configuration + per-kernel durations of one channel's matvecs
 : > $OUT/r06_configs.jsonl; : > $OUT/r06_config_kernels.txt
 for wl in cfg1_181c1_denoise cfg2_181c3_1mm dn_256c3_1mm cfg3_256c3_thick6z cfg3_256c3_thick6z_aligned cfg3_256c3_thick6z_shift cfg3_256c3_thick6xyz cfg3_256c3_thick6_orient cfg4_384c4_iso2 cfg4_384c4_iso2_gauss demo_181c3_thick4xyz; do
-  python bench.py --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 2>$OUT/cfg_$wl.err | grep '^{"metric"' >> $OUT/r06_configs.jsonl
+  python bench.py --full --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 2>$OUT/cfg_$wl.err | grep '^{"metric"' >> $OUT/r06_configs.jsonl
   for c in 0 1; do
     echo "== $wl (channel $c, 20 matvecs; rocprofv3 --kernel-trace)" >> $OUT/r06_config_kernels.txt
     WL=$wl CH=$c bash tools/prof.sh tools/pmc5.py 2>&1 | grep "unires::k_" | grep -v "build\|plan" >> $OUT/r06_config_kernels.txt
   done
 done
 for wl in cfg2_181c3_1mm dn_256c3_1mm; do
-  UNIRES_NO_ATA1=1 python bench.py --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 2>/dev/null | grep '^{"metric"' | sed 's/"workload": "\([a-z0-9_]*\)"/"workload": "\1 (UNIRES_NO_ATA1=1: the pull + splat pair)"/' >> $OUT/r06_configs.jsonl
+  UNIRES_NO_ATA1=1 python bench.py --full --workload $wl --no-cpu-baseline --no-variants --admm-iters 10 2>/dev/null | grep '^{"metric"' | sed 's/"workload": "\([a-z0-9_]*\)"/"workload": "\1 (UNIRES_NO_ATA1=1: the pull + splat pair)"/' >> $OUT/r06_configs.jsonl
   for c in 0 1; do
     echo "== $wl with UNIRES_NO_ATA1=1: the pull + splat pair of round 4 (channel $c)" >> $OUT/r06_config_kernels.txt
     UNIRES_NO_ATA1=1 WL=$wl CH=$c bash tools/prof.sh tools/pmc5.py 2>&1 | grep "unires::k_" | grep -v "build\|plan" >> $OUT/r06_config_kernels.txt
@@ -95,7 +95,7 @@ if has 8; then
 #    reference-default stopping rule's kernel account and the gains its guard band sees
 bash tools/r6_share_scan.sh > /dev/null 2>&1; cp gpurun_out/r6_share_scan.txt $OUT/r06_share_scan.txt
 { echo "# cfg3_256c3_thick6z, three bench.py runs per cap (UNIRES_SHARE_S2 = splat workgroups per 16 CUs: 64 = no cap, 28 = 448 of 1024, the default)"
-  for s in 64 28; do for rep in 1 2 3; do UNIRES_SHARE_S2=$s python bench.py --no-cpu-baseline --no-variants --admm-iters 1 2>/dev/null | python -c "
+  for s in 64 28; do for rep in 1 2 3; do UNIRES_SHARE_S2=$s python bench.py --full --no-cpu-baseline --no-variants --admm-iters 1 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{\"metric'):
