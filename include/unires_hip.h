@@ -228,7 +228,7 @@ int unires_plan_set_repeat(unires_plan_t *plan, int32_t n, const unires_repeat_t
 /* Hint: the caller keeps `n_concurrent` solves (this plan's and other plans') in flight on the device at once - the
  * channels of one y-update, which do not couple (unires/_update.py:122-150), each on a stream of its own.  The
  * plan then sizes the persistent kernels of its matvec so that other channels' kernels find room on the CUs (see
- * api.hip; results are unchanged, reductions are summed in another - still fixed - order).  1 = the default. */
+ * api_plan.hip; results are unchanged, reductions are summed in another - still fixed - order).  1 = the default. */
 int unires_plan_set_concurrency(unires_plan_t *plan, int32_t n_concurrent);
 /* Bytes of device workspace the plan owns. */
 int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);

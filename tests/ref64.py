@@ -22,7 +22,7 @@ For every output voxel v a float32 implementation must satisfy
   coordinate lies within eta = max delta of an integer, the floor itself may differ, so the unit-weight corners
   along d are every integer in [floor(g - eta), floor(g + eta) + 1].
 - ``R`` = max_i (sum_j |M_ij| (n_j - 1) + |t_i|): the magnitude of the coordinate arithmetic (reported).
-- ``D_v`` = |A_dropped| |p|: the end taps ``trim_taps`` (api.hip) drops, below 2^-22 sum |t|.  Zero for the rect and
+- ``D_v`` = |A_dropped| |p|: the end taps ``trim_taps`` (api_plan.hip) drops, below 2^-22 sum |t|.  Zero for the rect and
   triangular profiles (their dropped taps are exact zeros); zero by construction with ``trimmed=True``, where the
   reference is built with the taps the plan uses.
 
@@ -77,7 +77,7 @@ TRIM_REL = 2.384185791015625e-7  # trim_taps: |t| < 2^-22 sum |t|
 
 
 def trimmed_taps(taps_1d):
-    """trim_taps (api.hip) restated: per axis, the leading / trailing taps below 2^-22 sum |t| (sum in double, at
+    """trim_taps (api_plan.hip) restated: per axis, the leading / trailing taps below 2^-22 sum |t| (sum in double, at
     least one tap kept).  Returns per axis a 0/1 float64 mask of the taps the plan keeps."""
     keep = []
     for t in taps_1d:

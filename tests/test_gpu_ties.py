@@ -97,7 +97,7 @@ def test_denoising_disagreements_lie_within_reach_of_fov_ties(dev, trans, rot):
 def test_reoriented_storage_disagreements_lie_within_reach_of_fov_ties(dev, iperm, trans, rot):
     """The same for observations STORED in another voxel order (sagittal / coronal / reflected: a signed axis
     permutation in the affine).  The plan relabels their axes and evaluates the grid coordinates from permuted,
-    sign-flipped terms with the flip offset folded into the translation (api.hip: canonicalise) - equal to the
+    sign-flipped terms with the flip offset folded into the translation (api_plan.hip: canonicalise) - equal to the
     reference's `lin @ ijk + off` to the last ulp or one off: a mask may flip where a coordinate
     ties with a threshold, nowhere else.  Thresholds hit by integer, half-voxel and 0.05-voxel translations."""
     import unires_amd as U

@@ -58,12 +58,12 @@ repeat_info can show it, and relies on the switch otherwise:
 The conv-table pair: a rect profile at ratio r has r + 1 taps, so the table has r n_x + 1 entries: 1272 itself is
 no table length at ratio 6, and 1267 / 1273 are the two lengths either side of the limit.
 
-The last-resort forward (api.hip: ata_forward / unires_proj_apply, launch_pull + conv_down on the untrimmed R.A /
+The last-resort forward (api_operator.hip: forward, launch_pull + conv_down on the untrimmed R.A /
 R.T / R.dim_g) runs only when launch_pull_conv fails.  launch_pull_conv (fused.hip) halves its output tile
 (pick_out_tile) down to one voxel until the pulled tile fits 24 KB of LDS, so it fails (over 64 KB) only when the
 product of the taps exceeds ~16k.  Such profiles are separable (R.sep: more than 64 taps in all) and run the
 separable passes on R.Af / R.Tf; the hybrid form, which resets sep, is kept only where the window plan of pull2
-exists (build_repeat_kernels) and its forward is hybrid_forward.  So that path is not reached, and its untrimmed taps
+exists (build_repeat_kernels) and its forward is the hybrid branch.  So that path is not reached, and its untrimmed taps
 never meet the trimmed push.  z_nopull2 runs k_pull_conv, on the trimmed R.Af / R.Tf.
 
 Observed on an MI355X (largest err / tol over every check of the case; voxels excluded as FOV ties): z_thick 0.350

@@ -1,0 +1,523 @@
+// api_cg.hip - CG (nitorch.core.optim.cg as UniRes calls it): how a solve (CgSolve,
+// api_internal.hpp) is enqueued - whole, with the iterate update deferred over a ring of directions, or in chunks
+// that follow the device's progress -, the hipGraphs it is captured into, and unires_cg_solve(_many).
+#include <time.h>
+
+#include <functional>
+
+#include "api_internal.hpp"
+
+using namespace unires;
+
+// The solve is enqueued in two parts: the start (r = b - A x, p, r.z, obj[0]) and runs of iterations.
+// `dev_k`: the iteration index is the device state's own counter (a captured chunk of iterations then
+// serves any part of a solve); `hostw`: the scalar kernel that ends an iteration publishes the state's
+// (generation, done, iterations) to this host-mapped word.
+static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long long *hostw, hipStream_t st) {
+  const size_t ny = pl->dy.numel();
+  const bool check = s.tol != 0.0;
+  CgState *S = pl->state;
+  const int gv = vec_num_blocks(ny);
+  // r = b - A(x); p = r; rz = r.r; obj[0]
+  HIP_TRY(hipMemsetAsync(&S->done, 0, sizeof(int), st));
+  matvec(pl, s.rho, s.lam, s.x, pl->ap, nullptr, nullptr, st);
+  const bool want_obj0 = check && s.stop != UNIRES_STOP_RESIDUAL;
+  launch_residual_init(s.b, pl->ap, s.x, pl->r, pl->p, ny, pl->part0, want_obj0 ? pl->part1 : nullptr, s.M, st);
+  if (s.fft) {  // z = M^-1 r ; p = z ; rz = r.z
+    if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
+    HIP_TRY(hipMemcpyAsync(pl->p, pl->fft.z, ny * sizeof(float), hipMemcpyDeviceToDevice, st));
+    launch_dot(pl->r, pl->fft.z, ny, pl->part0, nullptr, st);
+  }
+  launch_sc_init(S, pl->part0, pl->part1, gv, s.stop, check ? 1 : 0, hostw, st);
+  return UNIRES_OK;
+}
+
+// slot j of the plan's direction ring (slot 0: the buffer the start writes p into)
+static float *ring_slot(unires_plan *pl, int j) {
+  return j == 0 ? pl->p : pl->ring + (size_t)(j - 1) * (align_up(pl->dy.numel() * 4) / 4);
+}
+
+// Iterations k_first .. k_first + count - 1 of the solve.
+// s.ring > 1 (tol = 0 solves enqueued whole, cg_ring_prepare): the iterate update is deferred - iteration k's
+// direction is slot (k - k_first) mod ring, and x takes the window's alpha p terms at every ring-th iteration and at
+// the last (k_update_p_flush, cg.hip).
+static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
+                            unsigned long long *hostw, hipStream_t st) {
+  const size_t ny = pl->dy.numel();
+  const bool check = s.tol != 0.0;
+  const int ring = s.ring;
+  CgState *S = pl->state;
+  const int *done = &S->done;
+  const int gv = vec_num_blocks(ny);
+  if (ring > 1 && (check || s.fft || dev_k || ring > kMaxRing || ring - 1 > pl->ring_slots))
+    return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
+  RingPtrs rp = {};
+  for (int j = 0; j < ring && ring > 1; ++j) rp.p[j] = ring_slot(pl, j);
+  for (int k = k_first; k < k_first + count; ++k) {
+    const int kk = dev_k ? -1 : k;
+    const int slot = ring > 1 ? (k - k_first) % ring : 0;
+    float *p = ring > 1 ? ring_slot(pl, slot) : pl->p;  // this iteration's direction
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (pl->timing && hipEventCreate(&ev0) == hipSuccess) {
+      if (hipEventCreate(&ev1) == hipSuccess) {
+        (void)hipEventRecord(ev0, st);
+      } else {
+        (void)hipEventDestroy(ev0);
+        ev0 = nullptr;
+      }
+    }
+    if (pl->twice) (void)matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);  // (measurement: see the header)
+    const int g = matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);
+    if (ev0 && ev1) {
+      (void)hipEventRecord(ev1, st);
+      if (pl->tev.size() >= 65536) {  // a caller that never collects: forget the oldest pair
+        (void)hipEventDestroy(pl->tev.front().first), (void)hipEventDestroy(pl->tev.front().second);
+        pl->tev.erase(pl->tev.begin());
+      }
+      pl->tev.emplace_back(ev0, ev1);
+    }
+    const bool guarded = check && s.stop == UNIRES_STOP_MAXGAIN_GUARDED;
+    const bool recur = check && (s.stop == UNIRES_STOP_MAXGAIN_RECURRED || guarded);
+    int obj_kind = 0;
+    if (check && s.stop == UNIRES_STOP_RESIDUAL) obj_kind = 1;
+    if (recur) obj_kind = 2;
+    // "x += alpha p" rides with the p update unless sc_beta can stop the solve in between
+    const bool lazy_x = obj_kind == 0;
+    launch_sc_alpha(S, pl->part0, g, st);
+    launch_update_xr(S, p, pl->ap, lazy_x ? nullptr : s.x, pl->r, s.b, ny, pl->part0,
+                     recur ? pl->part1 : nullptr, s.M, st);
+    if (s.fft) {  // (the transforms also run after convergence: hipFFT has no device-side skip)
+      if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
+      launch_dot(pl->r, pl->fft.z, ny, pl->part0, done, st);
+    }
+    if (guarded)
+      launch_sc_beta_guarded(S, pl->part0, pl->part1, gv, kk, s.tol, hostw, st);
+    else
+      launch_sc_beta(S, pl->part0, pl->part1, gv, kk, obj_kind, s.tol, obj_kind ? hostw : nullptr, st);
+    if (ring > 1 && (slot == ring - 1 || k == k_first + count - 1))
+      launch_update_p_flush(S, pl->r, rp, slot + 1, ring_slot(pl, (slot + 1) % ring), ny, s.M, s.x, st);
+    else if (ring > 1)
+      launch_update_p_ring(S, pl->r, p, ring_slot(pl, slot + 1), slot, ny, s.M, st);
+    else
+      launch_update_p(S, s.fft ? pl->fft.z : pl->r, pl->p, ny, s.M, lazy_x ? s.x : nullptr, st);
+    if (check && s.stop == UNIRES_STOP_MAXGAIN) {
+      // objective sum x (Ax - 2b) folded into the matvec epilogue: A(x) is never stored
+      const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, done, st, s.b);
+      launch_sc_obj(S, pl->part1, go, kk, s.tol, hostw, st);
+    }
+    if (guarded) {
+      // ... the same, but its kernels return at entry unless k_sc_beta_guarded asked for it (cg.hip)
+      const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, &S->skip_fresh, st, s.b);
+      launch_sc_obj_guarded(S, pl->part1, go, kk, s.tol, hostw, st);
+    }
+  }
+  return UNIRES_OK;
+}
+
+// Enqueues the whole solve (every kernel of nitorch's cg()) on `st`.
+static int cg_enqueue(unires_plan *pl, const CgSolve &s, hipStream_t st) {
+  const int rc = cg_enqueue_start(pl, s, nullptr, st);
+  if (rc) return rc;
+  return cg_enqueue_iters(pl, s, 1, s.max_iter, false, nullptr, st);
+}
+
+// K of the deferred iterate update for a solve that nothing reads x of before it ends (tol = 0, no FFT
+// preconditioner; the caller checks that): unires_plan_cg_ring's request, else
+// UNIRES_CG_RING, else 8, clamped to 1 .. kMaxRing.  The K - 1 extra direction buffers are allocated at the plan's
+// first such solve, within a budget (UNIRES_CG_RING_MB, default an eighth of the free device memory); the ring is
+// never grown or freed after that (a graph - ours or a caller's capture - may have its buffers baked in), so later
+// requests get at most what was allocated then.  No room, a failed allocation, or a stream under capture at that
+// first solve: K = 1, the iterate updated every iteration.
+static int cg_ring_prepare(unires_plan *pl, hipStream_t st) {
+  static const int env_k = [] {
+    const char *e = getenv("UNIRES_CG_RING");
+    return e ? atoi(e) : 8;
+  }();
+  int want = pl->ring_req > 0 ? pl->ring_req : env_k;
+  want = std::max(1, std::min(want, kMaxRing));
+  if (want <= 1) return 1;
+  if (!pl->ring_tried) {
+    if (stream_capturing(st)) return 1;  // (no allocation inside a capture: decided at the next plain solve)
+    pl->ring_tried = true;
+    const size_t slot = align_up(pl->dy.numel() * 4);
+    size_t budget = 0;
+    if (const char *e = getenv("UNIRES_CG_RING_MB")) {
+      budget = (size_t)std::max(0.0, atof(e) * 1048576.0);
+    } else {
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = free_b / 8;
+      (void)hipGetLastError();
+    }
+    const int n = (int)std::min<size_t>((size_t)(want - 1), budget / slot);
+    if (n < 1) return 1;
+    if (hipMalloc((void **)&pl->ring, (size_t)n * slot) != hipSuccess) {
+      (void)hipGetLastError();
+      pl->ring = nullptr;
+      return 1;
+    }
+    pl->ring_slots = n;
+  }
+  return std::min(want, pl->ring_slots + 1);
+}
+
+// --------------------------------------------------------------------------
+// Chunked solves (round 4): a solve that can stop early (tolerance > 0: the reference's default,
+// struct.py:65-67 cgs_tol = 1e-3, 'max_gain') is enqueued as the start + chunks of `chunk` iterations,
+// one chunk of look-ahead.  The kernel that ends an iteration publishes (generation, done, iterations)
+// to a host-mapped word; the host enqueues the next chunk when the older of the two in flight has
+// finished and the flag is not up - no stream synchronisation, the device never idles, and at most
+// 2 chunk - 1 iterations run as no-op kernels after convergence (enqueuing all max_iter iterations, as
+// rounds 1-3 did, ran 45 of config 3's 60 iterations as ~10 no-op kernels each).  The realised
+// iteration count, iterate and objective trace are those of the full enqueue: the same kernels in
+// the same order, the stopping test on the device.  Start and chunk are hipGraphs, captured once per
+// (b, x, rho, lam, options) and replayed.
+// --------------------------------------------------------------------------
+struct CgRun {
+  unires_plan *pl = nullptr;
+  CgSolve s;  // (s.chunk: iterations per chunk)
+  hipStream_t st = nullptr;
+  int enqueued = 0;     // iterations enqueued so far
+  unsigned gen = 0;     // generation of this solve
+  bool finished = false;
+  bool use_graph = false;
+};
+
+// The host counts the solves it starts (cg_gen), k_sc_init counts the ones that run (state->gen); the chunked
+// driver matches the two in the progress word.  After an enqueue / capture / launch that FAILED somewhere
+// between the two increments they may be out of step for the life of the plan: read the device's back.
+static void cg_resync_gen(unires_plan *pl) {
+  (void)hipDeviceSynchronize();
+  (void)hipGetLastError();
+  unsigned g = pl->cg_gen;
+  if (pl->state && hipMemcpy(&g, &pl->state->gen, sizeof(g), hipMemcpyDeviceToHost) == hipSuccess) pl->cg_gen = g;
+  (void)hipGetLastError();
+}
+
+// UNIRES_CG_CHUNK, read once per process: iterations per chunk (default 2, at most 64); 0: no chunked solves
+static int cg_chunk_env() {
+  static const int v = [] {
+    const char *e = getenv("UNIRES_CG_CHUNK");
+    return e ? atoi(e) : 2;
+  }();
+  return v;
+}
+static int cg_chunk_size() { return std::max(1, std::min(cg_chunk_env(), 64)); }
+
+static int capture_graph(hipStream_t st, hipGraphExec_t *exec, const std::function<int()> &body) {
+  *exec = nullptr;
+  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;  // capture refused: the caller launches plainly
+  }
+  const int rc = body();
+  hipGraph_t graph = nullptr;
+  const hipError_t ce = hipStreamEndCapture(st, &graph);
+  if (rc) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+  }
+  if (ce != hipSuccess || !graph) return fail(UNIRES_ERR_HIP, "hipStreamEndCapture failed");
+  const hipError_t ge = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (ge != hipSuccess) {
+    *exec = nullptr;
+    return fail(UNIRES_ERR_HIP, "hipGraphInstantiate failed");
+  }
+  return UNIRES_OK;
+}
+
+static int cg_run_enqueue_chunk(CgRun &R) {
+  unires_plan *pl = R.pl;
+  const int n = std::min(R.s.chunk, R.s.max_iter - R.enqueued);
+  if (n <= 0) return UNIRES_OK;
+  if (R.use_graph && n == R.s.chunk && pl->cg_chunk_exec) {
+    HIP_TRY(hipGraphLaunch(pl->cg_chunk_exec, R.st));
+  } else {
+    const int rc = cg_enqueue_iters(pl, R.s, R.enqueued + 1, n, true, pl->progress_dev, R.st);
+    if (rc) return rc;
+  }
+  R.enqueued += n;
+  return UNIRES_OK;
+}
+
+static int cg_run_start_impl(CgRun &R) {
+  unires_plan *pl = R.pl;
+  if (!pl->progress) {
+    HIP_TRY(hipHostMalloc((void **)&pl->progress, 64, hipHostMallocMapped));
+    *pl->progress = 0ull;
+    HIP_TRY(hipHostGetDevicePointer((void **)&pl->progress_dev, (void *)pl->progress, 0));
+  }
+  R.gen = ++pl->cg_gen;
+  R.enqueued = 0;
+  R.finished = false;
+  // the start and chunk graphs serve a solve of any length, and see the preconditioner as a diagonal or none
+  CgSolve key = R.s;
+  key.max_iter = 0;
+  key.pre = R.s.M ? UNIRES_PRECOND_JACOBI : UNIRES_PRECOND_IDENTITY;
+  if (R.use_graph && !(pl->cg_start_exec && pl->cg_chunk_exec && pl->cg_chunk_key.same_graph(key))) {
+    drop_cg_chunk_graphs(pl);
+    int rc = capture_graph(R.st, &pl->cg_start_exec, [&] { return cg_enqueue_start(pl, R.s, pl->progress_dev, R.st); });
+    if (rc > 0) return rc;
+    if (rc == 0)
+      rc = capture_graph(R.st, &pl->cg_chunk_exec, [&] {
+        return cg_enqueue_iters(pl, R.s, 1, R.s.chunk, true, pl->progress_dev, R.st);
+      });
+    if (rc > 0) return rc;
+    if (rc < 0 || !pl->cg_start_exec || !pl->cg_chunk_exec) {
+      drop_cg_chunk_graphs(pl);
+      R.use_graph = false;
+    } else {
+      pl->cg_chunk_key = key;
+    }
+  }
+  if (R.use_graph) {
+    HIP_TRY(hipGraphLaunch(pl->cg_start_exec, R.st));
+  } else {
+    const int rc = cg_enqueue_start(pl, R.s, pl->progress_dev, R.st);
+    if (rc) return rc;
+  }
+  // two chunks in flight
+  int rc = cg_run_enqueue_chunk(R);
+  if (!rc) rc = cg_run_enqueue_chunk(R);
+  if (rc) return rc;
+  if (R.enqueued >= R.s.max_iter) R.finished = true;
+  return UNIRES_OK;
+}
+
+static int cg_run_start(CgRun &R) {
+  const int rc = cg_run_start_impl(R);
+  if (rc) cg_resync_gen(R.pl);
+  return rc;
+}
+
+// One look at the progress word (never blocks): enqueues the next chunk when the older chunk in flight is
+// through and the solve has not converged.
+static int cg_run_poll(CgRun &R) {
+  if (R.finished) return UNIRES_OK;
+  const unsigned long long w = __atomic_load_n(R.pl->progress, __ATOMIC_ACQUIRE);
+  if ((unsigned)(w >> 32) != R.gen) return UNIRES_OK;  // this solve's first kernels have not run yet
+  if (w & 0x80000000ull) {
+    R.finished = true;
+    return UNIRES_OK;
+  }
+  const int iters = (int)(w & 0x7fffffffull);
+  while (!R.finished && iters >= R.enqueued - R.s.chunk) {
+    const int rc = cg_run_enqueue_chunk(R);
+    if (rc) return rc;
+    if (R.enqueued >= R.s.max_iter) R.finished = true;
+  }
+  return UNIRES_OK;
+}
+
+// Drive a set of runs (each on its own plan and stream) until every one has everything it needs
+// enqueued.  The host spins on the progress words; every so often it asks the streams for errors.
+static int cg_runs_drive(std::vector<CgRun> &runs) {
+  unsigned spins = 0;
+  for (;;) {
+    bool all = true;
+    for (CgRun &R : runs) {
+      if (R.finished) continue;
+      const int rc = cg_run_poll(R);
+      if (rc) return rc;
+      all = all && R.finished;
+    }
+    if (all) return UNIRES_OK;
+    // a chunk is hundreds of microseconds of device work and one more is queued behind it: after a short spin
+    // the thread sleeps between looks (eight ranks on one host must not each burn a core on the wait)
+    if (++spins > 256) {
+      const struct timespec nap = {0, 50000};
+      (void)nanosleep(&nap, nullptr);
+    }
+    // (a watchdog, not the progress signal - the word is: every 512th nap, ~25 ms, catches a faulted stream as
+    // well as every 16th did, and a stream query on running work is not free: the runtime submits a marker
+    // packet for it and its signal thread handles the completion)
+    if ((spins <= 256 && (spins & 0xff) == 0) || (spins > 256 && (spins & 0x1ff) == 0)) {
+      for (CgRun &R : runs) {
+        if (R.finished) continue;
+        const hipError_t q = hipStreamQuery(R.st);
+        if (q == hipSuccess) {
+          // the stream drained: whatever was enqueued has run and published; a look at the word must
+          // either end the run or enqueue more
+          const int before = R.enqueued;
+          const int rc = cg_run_poll(R);
+          if (rc) return rc;
+          if (!R.finished && R.enqueued == before)
+            return fail(UNIRES_ERR_HIP, "chunked CG: the stream drained without the expected progress");
+        } else if (q != hipErrorNotReady) {
+          g_err = std::string("chunked CG: ") + hipGetErrorString(q);
+          return UNIRES_ERR_HIP;
+        }
+      }
+    }
+  }
+}
+
+static int cg_check_args(unires_plan *plan, float rho, float lam, const float *b, float *x, int32_t max_iter,
+                         double tol, int32_t stop_mode, int32_t precond_mode) {
+  if (!plan || !b || !x) return fail(UNIRES_ERR_NULL, "null argument");
+  if (b == x) return fail(UNIRES_ERR_ARG, "b and x must not alias");
+  if (max_iter < 0) return fail(UNIRES_ERR_ARG, "max_iter out of range");
+  if (max_iter > kMaxCgIter && !(tol > 0.0))
+    return fail(UNIRES_ERR_ARG, "max_iter beyond 4096 needs a tolerance (the solve is then enqueued in chunks)");
+  if (stop_mode < 0 || stop_mode > 3) return fail(UNIRES_ERR_ARG, "bad stop mode");
+  if (precond_mode < UNIRES_PRECOND_IDENTITY || precond_mode > UNIRES_PRECOND_FFT)
+    return fail(UNIRES_ERR_UNSUPPORTED, "preconditioner modes: identity (0), Jacobi (1), FFT (2)");
+  if (precond_mode != UNIRES_PRECOND_IDENTITY &&
+      (!plan->prec_ready || plan->prec_mode != precond_mode || plan->prec_rho != rho ||
+       plan->prec_lam != lam))
+    return fail(UNIRES_ERR_ARG, "call unires_precond_build with this mode, rho and lam first");
+  if (!(tol >= 0.0)) return fail(UNIRES_ERR_ARG, "tolerance must be >= 0");
+  return UNIRES_OK;
+}
+
+static bool cg_graphs_on() {
+  static const bool on = !(getenv("UNIRES_CG_GRAPH") && getenv("UNIRES_CG_GRAPH")[0] == '0');
+  return on;
+}
+
+// chunked enqueue: solves that can stop early, unless switched off (UNIRES_CG_CHUNK=0: the full enqueue)
+static bool cg_chunked(double tol, int max_iter) {
+  const bool off = cg_chunk_env() == 0;
+  return tol != 0.0 && max_iter > 0 && (!off || max_iter > kMaxCgIter);
+}
+
+static CgSolve cg_describe(const unires_plan *pl, float rho, float lam, const float *b, float *x, int max_iter,
+                           double tol, int stop_mode, int precond_mode) {
+  CgSolve s;
+  s.b = b, s.x = x, s.rho = rho, s.lam = lam, s.max_iter = max_iter, s.stop = stop_mode, s.pre = precond_mode;
+  s.tol = tol;
+  s.M = precond_mode == UNIRES_PRECOND_JACOBI ? pl->precM : nullptr;
+  s.fft = precond_mode == UNIRES_PRECOND_FFT;
+  return s;
+}
+
+static CgRun cg_make_run(unires_plan *pl, CgSolve s, hipStream_t st) {
+  CgRun R;
+  R.pl = pl, R.s = s, R.st = st;
+  R.s.chunk = cg_chunk_size();
+  R.use_graph = cg_graphs_on() && !s.fft && !pl->timing;
+  return R;
+}
+
+static int cg_read_back(unires_plan *pl, int max_iter, double tol, int32_t *iters_out, double *obj_trace,
+                        hipStream_t st) {
+  CgState *S = pl->state;
+  int it = 0;
+  HIP_TRY(hipMemcpyAsync(&it, &S->iters, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (obj_trace && tol != 0.0)
+    HIP_TRY(hipMemcpyAsync(obj_trace, S->obj, sizeof(double) * (size_t)(std::min(max_iter, kMaxCgIter) + 1),
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *iters_out = it;
+  return UNIRES_OK;
+}
+
+extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const float *b, float *x,
+                               int32_t max_iter, double tol, int32_t stop_mode,
+                               int32_t precond_mode, int32_t *iters_out, double *obj_trace,
+                               void *stream) {
+  int rc = cg_check_args(plan, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  unires_plan *pl = plan;
+  CgSolve s = cg_describe(pl, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode);
+  mark_use(pl, st);  // (before anything is enqueued: a failed start or drive below is remembered too)
+
+  // (a stream under capture - e.g. the caller's torch.cuda.graph - runs nothing until the graph is launched: the
+  // chunk feeder would wait for progress that never comes.  The whole solve then joins the capture, as in r3;
+  // kernels after convergence return at entry.)
+  if (stream_capturing(st) && tol != 0.0 && max_iter > kMaxCgIter)
+    return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
+                                "(it is fed to the device chunk by chunk, following its progress)");
+  if (cg_chunked(tol, max_iter) && !(stream_capturing(st) && max_iter <= kMaxCgIter)) {
+    pl->last_ring = 1;
+    std::vector<CgRun> runs(1, cg_make_run(pl, s, st));
+    if ((rc = cg_run_start(runs[0]))) return rc;
+    if ((rc = cg_runs_drive(runs))) return rc;
+    mark_use(pl, st);
+    CHECK_LAUNCH();
+    return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
+  }
+  ++pl->cg_gen;  // (k_sc_init counts every solve)
+  // deferred iterate update: only where nothing reads x before the solve ends
+  s.ring = tol == 0.0 && !s.fft && max_iter > 0 ? cg_ring_prepare(pl, st) : 1;
+  pl->last_ring = s.ring;
+
+  // hipGraph replay (UNIRES_CG_GRAPH=0 disables): the ~8 launches per iteration of a solve are
+  // captured once and re-launched as one graph while the arguments stay the same
+  const bool graphable = cg_graphs_on() && !s.fft && max_iter > 0 && !pl->timing;  // (events go with plain launches)
+  if (graphable && pl->cg_exec && pl->cg_key.same_graph(s)) {
+    HIP_TRY(hipGraphLaunch(pl->cg_exec, st));
+  } else {
+    if (graphable && pl->cg_exec) drop_cg_graph(pl);
+    rc = graphable ? capture_graph(st, &pl->cg_exec, [&] { return cg_enqueue(pl, s, st); }) : -1;
+    if (rc > 0) {
+      cg_resync_gen(pl);
+      return rc;
+    }
+    if (rc == 0) {
+      pl->cg_key = s;
+      if (hipGraphLaunch(pl->cg_exec, st) != hipSuccess) {
+        cg_resync_gen(pl);
+        return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
+      }
+    } else if ((rc = cg_enqueue(pl, s, st))) {
+      cg_resync_gen(pl);
+      return rc;
+    }
+  }
+  mark_use(pl, st);
+  CHECK_LAUNCH();
+  return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
+}
+
+// Several channels' solves at once, each on its own plan and stream (unires/_update.py:122-150 loops over
+// the channels; they do not couple inside the y-update): the chunks of all of them are fed from one host
+// loop, so that the channels still overlap on the device where they run on separate streams.
+extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, const float *rho, const float *lam,
+                                    const float *const *b, float *const *x, int32_t max_iter, double tol,
+                                    int32_t stop_mode, int32_t precond_mode, int32_t *iters_out,
+                                    double *obj_trace, void *const *streams) {
+  if (n < 1 || !plans || !rho || !lam || !b || !x || !streams) return fail(UNIRES_ERR_NULL, "null argument");
+  for (int c = 0; c < n; ++c) {
+    const int rc = cg_check_args(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode);
+    if (rc) return rc;
+    for (int d = 0; d < c; ++d)
+      if (plans[d] == plans[c]) return fail(UNIRES_ERR_ARG, "one plan per solve");
+  }
+  bool capturing = false;
+  for (int c = 0; c < n; ++c) capturing = capturing || stream_capturing((hipStream_t)streams[c]);
+  if (capturing && tol != 0.0 && max_iter > kMaxCgIter)
+    return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
+                                "(it is fed to the device chunk by chunk, following its progress)");
+  for (int c = 0; c < n; ++c) mark_use(plans[c], (hipStream_t)streams[c]);  // (before anything is enqueued)
+  if (!cg_chunked(tol, max_iter) || (capturing && max_iter <= kMaxCgIter)) {  // nothing to steer: each solve is enqueued whole
+    for (int c = 0; c < n; ++c) {
+      const int rc = unires_cg_solve(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode,
+                                     nullptr, nullptr, streams[c]);
+      if (rc) return rc;
+    }
+  } else {
+    std::vector<CgRun> runs;
+    for (int c = 0; c < n; ++c) plans[c]->last_ring = 1;
+    for (int c = 0; c < n; ++c)
+      runs.push_back(cg_make_run(plans[c], cg_describe(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode,
+                                                       precond_mode), (hipStream_t)streams[c]));
+    for (CgRun &R : runs) {
+      const int rc = cg_run_start(R);
+      if (rc) return rc;
+    }
+    const int rc = cg_runs_drive(runs);
+    if (rc) return rc;
+    for (int c = 0; c < n; ++c) mark_use(plans[c], (hipStream_t)streams[c]);
+    CHECK_LAUNCH();
+  }
+  if (iters_out)
+    for (int c = 0; c < n; ++c) {
+      const int rc = cg_read_back(plans[c], max_iter, tol, iters_out + c,
+                                  obj_trace ? obj_trace + (size_t)c * (std::min(max_iter, kMaxCgIter) + 1) : nullptr,
+                                  (hipStream_t)streams[c]);
+      if (rc) return rc;
+    }
+  return UNIRES_OK;
+}

@@ -1,0 +1,249 @@
+// api_internal.hpp - what the translation units behind the C ABI (include/unires_hip.h) share: error plumbing,
+// the description of an operator and the device tables built for it, the plan object, the description of a CG
+// solve, and the few functions that cross files.  api.hip: op-level entry points, ADMM sums, marks; api_plan.hip:
+// the plan and its table builds; api_operator.hip: which kernels apply A, A^T, A^T A and the matvec; api_cg.hip:
+// the CG driver.  Host-only.
+#pragma once
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/unires_hip.h"
+#include "ata1.hpp"
+#include "cg.hpp"
+#include "fftpre.hpp"
+#include "fused.hpp"
+#include "orient.hpp"
+#include "pull2.hpp"
+#include "shift.hpp"
+#include "splat2.hpp"
+
+namespace unires {
+
+// --------------------------------------------------------------------------
+// error plumbing (the string unires_last_error returns; defined in api.hip)
+// --------------------------------------------------------------------------
+extern thread_local std::string g_err;
+
+inline int fail(int code, const char *msg) {
+  g_err = msg;
+  return code;
+}
+
+#define HIP_TRY(expr)                                                               \
+  do {                                                                              \
+    hipError_t e_ = (expr);                                                         \
+    if (e_ != hipSuccess) {                                                         \
+      unires::g_err = std::string(#expr) + ": " + hipGetErrorString(e_);            \
+      return UNIRES_ERR_HIP;                                                        \
+    }                                                                               \
+  } while (0)
+
+#define CHECK_LAUNCH()                                                              \
+  do {                                                                              \
+    hipError_t e_ = hipGetLastError();                                              \
+    if (e_ != hipSuccess) {                                                         \
+      unires::g_err = std::string("kernel launch: ") + hipGetErrorString(e_);       \
+      return UNIRES_ERR_HIP;                                                        \
+    }                                                                               \
+  } while (0)
+
+inline bool dims_ok(const int32_t d[3]) {
+  return d[0] > 0 && d[1] > 0 && d[2] > 0 && d[0] <= 65535 &&
+         (long long)d[0] * d[1] * d[2] < (1ll << 40);
+}
+inline bool vx_ok(const float vx[3]) { return vx && vx[0] > 0 && vx[1] > 0 && vx[2] > 0; }
+inline Dim3i mk(const int32_t d[3]) { return Dim3i{d[0], d[1], d[2]}; }
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// argument checking shared by the op level and the plan (api.hip)
+int make_taps(const float *const taps[3], const int32_t ntaps[3], const int32_t stride[3], Taps &T);
+int check_conv_dims(const Dim3i &hi, const Dim3i &lo, const Taps &T);  // hi = (lo - 1) * stride + ntaps
+bool invert_affine(const Affine &A, Affine &out);  // row-major 3x4 float32, computed in double
+
+// --------------------------------------------------------------------------
+// taps and scaling
+// --------------------------------------------------------------------------
+constexpr Scaling kNoScaling{1.f, 1.f, -1};
+
+inline Scaling make_scaling(float scl, int dim) {
+  if (scl == 0.f) return kNoScaling;
+  return Scaling{expf(scl), expf(-scl), dim};
+}
+
+// axis d has a Dirac profile: one tap of 1, stride 1 (conv_down / conv_up along it are the identity)
+inline bool is_dirac(const Taps &T, int d) { return T.n[d] == 1 && T.s[d] == 1 && T.t[d][0] == 1.f; }
+inline void set_dirac(Taps &T, int d) { T.n[d] = T.s[d] = 1, T.t[d][0] = 1.f; }
+// x-space voxels a grid voxel of axis d contributes to (what the fused push kernels tabulate up to 2 of)
+inline int fan_in(const Taps &T, int d) { return (T.n[d] + T.s[d] - 1) / T.s[d]; }
+
+// UNIRES_PUSH, read once per process.  Unset: the schedule-driven splat (k_splat2) and ata_forward's one-kernel
+// x / y forms, then the general kernels where an operator is outside their domain.  "tile": the general tile kernel
+// only (the tests' cross-check).  Any other value: neither of those - k_splat, then the tile kernel.
+enum class PushMode { kDefault, kTile, kNoSchedule };
+inline PushMode push_mode() {
+  static const PushMode mode = [] {
+    const char *e = getenv("UNIRES_PUSH");
+    return !e ? PushMode::kDefault : !strcmp(e, "tile") ? PushMode::kTile : PushMode::kNoSchedule;
+  }();
+  return mode;
+}
+
+// --------------------------------------------------------------------------
+// one repeat (observation) of a plan: the operator's description, and the device tables built for it
+// --------------------------------------------------------------------------
+// What fill_repeat derives from a unires_repeat_t.  Trivially copyable; owns nothing.
+struct RepeatDesc {
+  // Everything below is in the plan's CANONICAL voxel layout of the observation: x-space axis d runs
+  // mainly along +d of the output (orient.hpp).  `orient` maps it to the caller's layout, `dim_xu`
+  // are the caller's x-space dims; only 'A' outputs and 'At' / RHS inputs are ever re-ordered.
+  Orient orient;
+  bool oriented = false;
+  Dim3i dim_xu;
+  Dim3i dim_x, dim_g;
+  Affine A;
+  Taps T;
+  float scl;
+  int dim_thick;
+  float tau;
+  // fused path: zero taps trimmed, grid shifted accordingly, inverse affine
+  Dim3i dim_gf;
+  Affine Af, Afinv;
+  Taps Tf;
+  SplatSafety safe;  // of Af (the linear part is the same for A)
+  bool sep = false;  // many-tap profile: convolutions run as separable 1-D passes
+  bool sep0 = false; // ... as decided from the taps alone (the hybrid form clears `sep`; kept for its fallback)
+  // profile along x and / or y AND z with a z fan-in <= 2 (isotropic down-sampling, BASELINE config
+  // 4): the x / y part runs as 1-D passes through a (gf.x, gf.y, xd.z) intermediate, the z part
+  // stays fused in the pull / splat kernels, which then cost what they cost for a z-only profile
+  // (build_repeat_kernels revises hyb / hybf / sep where the kernels turn out to be unavailable)
+  bool hyb = false;
+  // forward-only hybrid (r3): many-tap profiles (sep) whose z part the window pull can still fuse -
+  // any number of z taps - while conv_up keeps its 1-D passes (the splat tabulates a fan-in of 2 only):
+  // the default Gaussian in-plane profile of BASELINE config 4
+  bool hybf = false;
+  Taps Tz, Txy;
+  Dim3i dim_h;
+};
+
+// What the build_* functions make for a description; keeps its device allocations across unires_plan_set_repeat
+// (contents rebuilt), freed by free_tables.
+struct RepeatTables {
+  // schedule-driven splat (splat2.hip): per-tile segment lists of this operator + conv_up tables
+  // along the schedule's axis ([0] no scaling, [1] S(scl)); ctab_n entries, second x-space value
+  // ctab_step elements after the first
+  SplatSched sched;
+  float *ctab_dev[2] = {nullptr, nullptr};
+  int ctab_n = 0, ctab_cap = 0;
+  unsigned ctab_step = 1, src_stride = 1;
+  float *xytab_dev[2] = {nullptr, nullptr};  // axis 3: conv_up tables along x and y (schedule build)
+  int xytab_cap[2] = {0, 0};
+  PullPlan pplan;   // LDS-window pull: per-workgroup geometry of this operator (pull2.hip)
+  ShiftPlan shift;  // translation-only operators: factors of AtA for the one-kernel matvec (shift.hip)
+  F1Sched f1;       // denoising regime: schedule of the single-pass AtA kernel (ata1.hip)
+};
+
+struct Repeat : RepeatDesc, RepeatTables {};
+
+// --------------------------------------------------------------------------
+// one CG solve: what the caller asked for, what follows from it, and how it is enqueued.  The parameter of the
+// cg_enqueue_* functions, and the key a captured graph is compared against.
+// --------------------------------------------------------------------------
+struct CgSolve {
+  const float *b = nullptr;
+  float *x = nullptr;
+  float rho = 0.f, lam = 0.f;
+  int max_iter = -1, stop = -1, pre = -1;
+  double tol = -1.0;
+  int ring = 1;   // direction buffers of the deferred iterate update (1: the iterate updated every iteration)
+  int chunk = 0;  // iterations per chunk of a chunked solve; 0: the solve is enqueued whole
+  // derived (not compared): the Jacobi diagonal, or nullptr; the FFT-diagonal preconditioner
+  const float *M = nullptr;
+  bool fft = false;
+  // a graph captured for `o` serves this solve (a captured solve has every one of these baked in)
+  bool same_graph(const CgSolve &o) const {
+    return b == o.b && x == o.x && rho == o.rho && lam == o.lam && max_iter == o.max_iter && stop == o.stop &&
+           pre == o.pre && ring == o.ring && chunk == o.chunk && tol == o.tol;
+  }
+};
+
+}  // namespace unires
+
+struct unires_plan {
+  unires::Dim3i dy;
+  float vx[3];
+  int regime;
+  float fov_tol;
+  std::vector<unires::Repeat> reps;
+  // device workspace (one allocation)
+  char *ws = nullptr;
+  size_t ws_bytes = 0;
+  float *r = nullptr, *p = nullptr, *ap = nullptr, *ax = nullptr;  // N_y each
+  // measurement aid (unires_plan_time_matvecs): event pairs around the operator applications of a solve
+  bool timing = false;
+  bool twice = false;  // unires_plan_time_matvecs(plan, 2): every A(p) of a solve is enqueued twice (same result)
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+  float *gbuf = nullptr;                                           // max N_g
+  float *gbuf2 = nullptr;  // second grid-space scratch, only for many-tap profiles (separable passes)
+  float *xbuf = nullptr;                                           // max N_x
+  float *xperm = nullptr;  // max N_x: an x-space volume on its way between the caller's layout and the canonical one
+  double *part0 = nullptr, *part1 = nullptr;                       // kMaxPartials each
+  unires::CgState *state = nullptr;
+  size_t cap_g = 0, cap_x = 0;
+  // the whole CG solve as one hipGraph, re-launched while (b, x, rho, lam, options) stay the
+  // same - the ADMM loop calls it with identical arguments until the schedule changes
+  unires::CgSolve cg_key;
+  hipGraphExec_t cg_exec = nullptr;
+  // chunked solves: start + chunk graphs, the host-mapped progress word and the solve counter
+  unires::CgSolve cg_chunk_key;
+  hipGraphExec_t cg_start_exec = nullptr, cg_chunk_exec = nullptr;
+  unsigned long long *progress = nullptr, *progress_dev = nullptr;
+  unsigned cg_gen = 0;
+  float *precM = nullptr;  // Jacobi diagonal (own allocation, made by unires_precond_build)
+  // deferred iterate update of tol = 0 solves (cg_ring_prepare): ring slot 0 is `p`, slots 1 .. ring_slots live in
+  // `ring` (own allocation, made at the first such solve, freed with the plan only: a graph may have it baked in)
+  float *ring = nullptr;
+  int ring_slots = 0;
+  bool ring_tried = false;  // the allocation was decided (made, refused by the budget, or failed)
+  int ring_req = 0;         // unires_plan_cg_ring: K asked for (0: UNIRES_CG_RING or the default)
+  int last_ring = 1;        // K of the plan's last solve (1: the iterate updated every iteration)
+  unires::FftPre fft;      // FFT-diagonal preconditioner (plans + buffers, made on demand)
+  float prec_rho = 0.f, prec_lam = 0.f;
+  int prec_mode = UNIRES_PRECOND_IDENTITY;
+  bool prec_ready = false;
+  // the last launch that reads this plan's tables: unires_plan_set_repeat / the graph teardown wait for THIS
+  // event instead of the whole device (other channels' streams keep running).  A launch enqueued while its
+  // stream was being captured cannot be waited for through an event: `captured_use` sends those to the
+  // device-wide wait.
+  hipEvent_t last_use = nullptr;
+  std::vector<hipStream_t> use_streams;
+  bool captured_use = false;
+  // unires_plan_set_concurrency: how many solves the caller keeps in flight on the device (channels of a y-update on
+  // streams of their own), and the caps on the persistent kernels' grids that follow from it (0: the whole chip)
+  int concurrency = 1;
+  int cap_s2 = 0, cap_f1 = 0;
+};
+
+namespace unires {
+
+// api_plan.hip
+bool stream_capturing(hipStream_t st);
+void mark_use(unires_plan *pl, hipStream_t st);  // note the plan's last use (see unires_plan::last_use) ...
+void await_use(unires_plan *pl);                 // ... and wait for it
+void drop_cg_chunk_graphs(unires_plan *pl);
+void drop_cg_graph(unires_plan *pl);  // every captured solve of the plan, the chunk graphs included
+
+// api_operator.hip
+// q = sum_n tau_n AtA_n p + rho lam^2 DtD p ; optional dot partials of sum(p*q).
+// With objb (and part): the partials hold sum (q - 2 objb) * p instead and the final q is not
+// stored (q is still scratch for the partial sums of a multi-repeat operator).
+// Returns the number of partials written (0 if none requested).
+int matvec(unires_plan *pl, float rho, float lam, const float *p, float *q, double *part, const int *done,
+           hipStream_t st, const float *objb = nullptr);
+
+}  // namespace unires

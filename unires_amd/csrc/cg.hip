@@ -325,145 +325,15 @@ __global__ void __launch_bounds__(kBlock)
     y[i] = fmaf(a, x[i], y[i]);
 }
 
-// ---- folded forms: the scalar steps ride in the prologues of the vector kernels ------------
-// (r2 tried the opposite fold - the LAST workgroup of the producer sums the partials - which needs
-// an agent-scope release per workgroup, an L2 write-back each: 4 200 -> 1 550 iterations/s.  Here
-// nothing crosses workgroups inside a launch: every consumer workgroup reads the producer's <= 8192
-// partials (L2 hits, 64 KB at most) after the kernel boundary and sums them in the same fixed
-// order.)
-__device__ __forceinline__ double reduce_all(const double *__restrict__ part, int g) {
-  __shared__ double s_tot[kBlock / kWave];
-  double v = 0.0;
-  int i = threadIdx.x;
-  for (; i + 7 * kBlock < g; i += 8 * kBlock) {
-    double t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = part[i + u * kBlock];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v += t[u];
-  }
-  for (; i < g; i += kBlock) v += part[i];
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) s_tot[threadIdx.x / kWave] = v;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int w = 0; w < kBlock / kWave; ++w) tot += s_tot[w];
-  return tot;  // the same value, bit for bit, in every thread of every workgroup
-}
-
-// Chunked form of the fused updates: a workgroup takes chunks of kFoldIt * kBlock float4, ALL loads of
-// a chunk are issued before anything else, and the partial-sum reduction of the prologue runs behind
-// them (first chunk only): its round trip (L2 reads of the partials, one LDS exchange) overlaps the
-// latency of the chunk's own loads instead of preceding it.  4096 workgroups, as the unfolded kernels
-// (1024 persistent ones lost 12 % of the streaming rate: 57 instead of 50 us for the x / p update).
-constexpr int kFoldIt = 4;
-static inline int vec_blocks_fold(size_t n) {
-  size_t b = (n / 4 + (size_t)kFoldIt * kBlock - 1) / ((size_t)kFoldIt * kBlock);
-  if (b < 1) b = 1;
-  return (int)(b < 4096 ? b : 4096);
-}
-
-// r update: 1024 persistent workgroups (3 volume passes keep the streaming rate at this size; its
-// <= 1024 partial sums are what the 4096 workgroups of the x / p update re-reduce - 4 loads per thread)
-static inline int vec_blocks_rfold(size_t n) {
-  size_t b = (n / 4 + kBlock - 1) / kBlock;
-  if (b < 1) b = 1;
-  return (int)(b < 1024 ? b : 1024);
-}
-__global__ void __launch_bounds__(kBlock)
-    k_update_r_fold(CgState *__restrict__ st, const double *__restrict__ part_pap, int g, int k,
-                    const float *__restrict__ ap, float *__restrict__ r, size_t n,
-                    double *__restrict__ part_rr, const float *__restrict__ M) {
-  if (st->done) return;
-  const double pap = reduce_all(part_pap, g);
-  const double alpha_d = st->rzpp[(k - 1) & 1] / pap;
-  if (blockIdx.x == 0 && threadIdx.x == 0) st->pAp = pap, st->alpha = alpha_d;
-  const float alpha = (float)alpha_d;
-  GRID_STRIDE_VEC4(n);
-  double rr = 0.0;
-  for (size_t i = tid0; i < n4; i += stride) {
-    const float4 va = ld4(ap, i);
-    float4 vr = ld4(r, i);
-    vr.x = __fsub_rn(vr.x, __fmul_rn(alpha, va.x));
-    vr.y = __fsub_rn(vr.y, __fmul_rn(alpha, va.y));
-    vr.z = __fsub_rn(vr.z, __fmul_rn(alpha, va.z));
-    vr.w = __fsub_rn(vr.w, __fmul_rn(alpha, va.w));
-    st4(r, i, vr);
-    const float4 vz = zval4(vr, M, i);
-    rr += (double)__fmul_rn(vr.x, vz.x) + (double)__fmul_rn(vr.y, vz.y) +
-          (double)__fmul_rn(vr.z, vz.z) + (double)__fmul_rn(vr.w, vz.w);
-  }
-  for (size_t i = n4 * 4 + tid0; i < n; i += stride) {
-    const float vr = __fsub_rn(r[i], __fmul_rn(alpha, ap[i]));
-    r[i] = vr;
-    rr += (double)__fmul_rn(vr, zval1(vr, M, i));
-  }
-  const double t = block_sum(rr);
-  if (threadIdx.x == 0) part_rr[blockIdx.x] = t;
-}
-
-__global__ void __launch_bounds__(kBlock)
-    k_update_px_fold(CgState *__restrict__ st, const double *__restrict__ part_rr, int g, int k,
-                     const float *__restrict__ r, float *__restrict__ p, float *__restrict__ x, size_t n,
-                     const float *__restrict__ M) {
-  if (st->done) return;
-  const size_t n4 = n / 4, chunk = (size_t)kFoldIt * kBlock;
-  float alpha = 0.f, beta = 0.f;
-  bool have = false;
-  for (size_t c = blockIdx.x; c * chunk < n4 || !have; c += gridDim.x) {
-    float4 vz[kFoldIt], vp[kFoldIt], vx[kFoldIt];
-    size_t idx[kFoldIt];
-#pragma unroll
-    for (int u = 0; u < kFoldIt; ++u) {
-      idx[u] = c * chunk + (size_t)u * kBlock + threadIdx.x;
-      if (idx[u] < n4) vz[u] = zval4(ld4(r, idx[u]), M, idx[u]), vp[u] = ld4(p, idx[u]), vx[u] = ld4(x, idx[u]);
-    }
-    if (!have) {
-      const double rrs = reduce_all(part_rr, g);
-      const double rz0 = st->rzpp[(k - 1) & 1];
-      const double beta_d = rrs / rz0;
-      beta = (float)beta_d, alpha = (float)st->alpha;
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        st->rzpp[k & 1] = rrs;
-        st->rz = rrs;
-        st->beta = beta_d;
-        st->iters = k;
-      }
-      have = true;
-    }
-#pragma unroll
-    for (int u = 0; u < kFoldIt; ++u) {
-      if (idx[u] < n4) {
-        float4 a = vx[u], b = vp[u];
-        a.x = __fadd_rn(a.x, __fmul_rn(alpha, b.x));
-        a.y = __fadd_rn(a.y, __fmul_rn(alpha, b.y));
-        a.z = __fadd_rn(a.z, __fmul_rn(alpha, b.z));
-        a.w = __fadd_rn(a.w, __fmul_rn(alpha, b.w));
-        st4(x, idx[u], a);
-        b.x = __fadd_rn(__fmul_rn(beta, b.x), vz[u].x);
-        b.y = __fadd_rn(__fmul_rn(beta, b.y), vz[u].y);
-        b.z = __fadd_rn(__fmul_rn(beta, b.z), vz[u].z);
-        b.w = __fadd_rn(__fmul_rn(beta, b.w), vz[u].w);
-        st4(p, idx[u], b);
-      }
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail
-    const size_t i = n4 * 4 + threadIdx.x;
-    const float vp = p[i];
-    x[i] = __fadd_rn(x[i], __fmul_rn(alpha, vp));
-    p[i] = __fadd_rn(__fmul_rn(beta, vp), zval1(r[i], M, i));
-  }
-}
-
 // ---- scalar kernels: <<<1, kBlock>>> -------------------------------------
 // (Tried and dropped, r2: folding k_sc_alpha / k_sc_beta into the kernels that write their
 // partials - every workgroup takes a ticket, the last one sums all partials in a fixed order.  The
 // ticket needs an agent-scope release so that the partials of workgroups on other XCDs are visible,
 // and on gfx950 that is an L2 write-back per workgroup: config 3 fell from 4 200 to 1 550 CG
-// iterations/s, the aligned variant from 6 400 to 1 800.  Two 5 us launches per iteration it is.)
+// iterations/s, the aligned variant from 6 400 to 1 800.  Two 5 us launches per iteration it is.
+// r3 tried the other direction - every workgroup of the CONSUMER re-reduces the partials in its prologue, no
+// release needed - as k_update_r / k_update_px variants behind a switch: correct, no gain in two measurements
+// (EXPERIMENTS E3, E15); removed.)
 __device__ __forceinline__ double sum_partials(const double *part, int g) {
   // loads batched eight deep (the additions keep their order): this one-block kernel is pure
   // latency, and sixteen dependent load->add steps per thread were most of its 6 us
@@ -690,17 +560,6 @@ __global__ void __launch_bounds__(kBlock) k_sum_to(const double *part, int g, do
 
 // ---- launchers -------------------------------------------------------------
 int vec_num_blocks(size_t n) { return vec_blocks(n); }
-int vec_num_blocks_fold(size_t n) { return vec_blocks_rfold(n); }  // partials the r update writes
-void launch_update_r_fold(CgState *s, const double *part_pap, int g, int k, const float *ap, float *r,
-                          size_t n, double *part_rr, const float *M, hipStream_t st) {
-  hipLaunchKernelGGL(k_update_r_fold, dim3(vec_blocks_rfold(n)), dim3(kBlock), 0, st, s, part_pap, g, k, ap, r,
-                     n, part_rr, M);
-}
-void launch_update_px_fold(CgState *s, const double *part_rr, int g, int k, const float *r, float *p,
-                           float *x, size_t n, const float *M, hipStream_t st) {
-  hipLaunchKernelGGL(k_update_px_fold, dim3(vec_blocks_fold(n)), dim3(kBlock), 0, st, s, part_rr, g, k, r, p,
-                     x, n, M);
-}
 
 void launch_residual_init(const float *b, const float *ax, const float *x, float *r, float *p,
                           size_t n, double *part_rr, double *part_obj, const float *M,

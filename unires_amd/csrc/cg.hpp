@@ -5,14 +5,13 @@
 namespace unires {
 
 constexpr int kMaxCgIter = 4096;
-constexpr int kMaxRing = 8;  // most direction buffers a deferred-iterate solve keeps (api.hip: cg_ring_prepare)
+constexpr int kMaxRing = 8;  // most direction buffers a deferred-iterate solve keeps (api_cg.hip: cg_ring_prepare)
 
 struct CgState {  // lives in device memory, owned by the plan
   double rz, pAp, alpha, beta, obj_max, obj_min;
   int done, iters;
   unsigned gen, pad_;  // solves started on this plan (k_sc_init counts); tags the published progress word
-  double rzpp[2];  // r.z of iterations k (slot k & 1) and k - 1: the folded kernels read one slot while
-                   // workgroup 0 of the same launch writes the other
+  double rzpp[2];  // r.z of iterations k (slot k & 1) and k - 1, kept by the scalar kernels
   double obj[kMaxCgIter + 1];  // objective trace; iteration k at slot k % (kMaxCgIter + 1)
   // UNIRES_STOP_MAXGAIN_GUARDED (k_sc_beta_guarded / k_sc_obj_guarded)
   int skip_fresh;        // 1: this iteration's fresh objective (a second A(x)) is not needed - its kernels return at entry
@@ -28,7 +27,7 @@ struct RingPtrs {  // the ring's direction buffers, slot j = the j-th iteration 
 };
 
 // Progress word of a solve, published by its scalar kernels to host-mapped memory (chunked solves,
-// api.hip): generation << 32 | done << 31 | iterations completed.
+// api_cg.hip): generation << 32 | done << 31 | iterations completed.
 __host__ __device__ inline unsigned long long cg_progress_word(unsigned gen, int done, int iters) {
   return ((unsigned long long)gen << 32) | (done ? 0x80000000ull : 0ull) | (unsigned)(iters & 0x7fffffff);
 }
@@ -46,7 +45,7 @@ void launch_update_xr(const CgState *s, const float *p, const float *ap, float *
 // pass less per iteration (only valid when nothing stops the solve between the two launches)
 void launch_update_p(const CgState *s, const float *r, float *p, size_t n, const float *M, float *x,
                      hipStream_t st);
-// Deferred iterate update (tol = 0 solves, api.hip): the directions of up to kMaxRing iterations stay in a ring and
+// Deferred iterate update (tol = 0 solves, api_cg.hip): the directions of up to kMaxRing iterations stay in a ring and
 // x takes their alpha p terms at once, in iteration order, with the same roundings.
 // ring: p_out = beta p_in + z for the iteration whose direction is ring slot `slot`; records its alpha and whether it
 // was committed (the state not done).
@@ -71,24 +70,12 @@ void launch_sc_beta(CgState *s, const double *part_rr, const double *part_obj, i
                     int obj_kind, double tol, unsigned long long *hostw, hipStream_t st);
 void launch_sc_obj(CgState *s, const double *part, int g, int k, double tol, unsigned long long *hostw,
                    hipStream_t st);
-// guarded 'max_gain' (api.hip: cg_enqueue_iters): sc_beta with the recurred objective decides whether the fresh one is
+// guarded 'max_gain' (api_cg.hip: cg_enqueue_iters): sc_beta with the recurred objective decides whether the fresh one is
 // needed; sc_obj, if it runs, decides with it
 void launch_sc_beta_guarded(CgState *s, const double *part_rr, const double *part_obj, int g, int k, double tol,
                             unsigned long long *hostw, hipStream_t st);
 void launch_sc_obj_guarded(CgState *s, const double *part, int g, int k, double tol, unsigned long long *hostw,
                            hipStream_t st);
 void launch_sum_to(const double *part, int g, double *out, hipStream_t st);
-// Folded forms (no scalar kernels between the matvec and the vector updates): EVERY workgroup
-// re-reduces the producer's partial sums in a fixed order in its prologue - visibility comes from
-// the kernel boundary, the order is the same everywhere, so all workgroups hold the same alpha /
-// beta bit for bit; workgroup 0 records them in the state.
-int vec_num_blocks_fold(size_t n);
-// r -= alpha Ap with alpha = rz / sum(part_pap[0..g)); part_rr (vec_num_blocks_fold(n) doubles, NOT the
-// buffer part_pap lives in) gets sum r*z
-void launch_update_r_fold(CgState *s, const double *part_pap, int g, int k, const float *ap, float *r,
-                          size_t n, double *part_rr, const float *M, hipStream_t st);
-// x += alpha p; p = z + beta p with beta = sum(part_rr[0..g)) / rz; records rz, beta, iters = k
-void launch_update_px_fold(CgState *s, const double *part_rr, int g, int k, const float *r, float *p,
-                           float *x, size_t n, const float *M, hipStream_t st);
 
 }  // namespace unires

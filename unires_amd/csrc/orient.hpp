@@ -6,7 +6,7 @@
 // permuted against the world axes) and LAS-vs-RAS reflections reach A as a signed axis permutation
 // in the linear part of M = mat_y \ rigid mat_yx.  The kernels of the fused path are built for
 // grids whose axis d runs mainly along +d of the output; the plan therefore relabels the x-space
-// voxel axes ONCE per operator (fill_repeat, api.hip) so that they do, and the few entry points
+// voxel axes ONCE per operator (fill_repeat, api_plan.hip) so that they do, and the few entry points
 // that take or return x-space volumes in the caller's layout re-order them with the kernels here.
 #pragma once
 #include "common.hpp"

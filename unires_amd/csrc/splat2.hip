@@ -79,7 +79,7 @@ static int s2_ntiles(Dim3i dd) {
 }
 
 // workgroups of the persistent launch; `share_cap` > 0: the caller runs other work next to it (channels of a y-update
-// on streams of their own) and wants room left on the CUs - see unires_plan_set_concurrency (api.hip)
+// on streams of their own) and wants room left on the CUs - see unires_plan_set_concurrency (api_plan.hip)
 static int s2_grid(Dim3i dd, int share_cap = 0) {
   const int nt = s2_ntiles(dd);
   static const int cap_env = getenv("UNIRES_SPLAT2_BLOCKS") ? atoi(getenv("UNIRES_SPLAT2_BLOCKS")) : 0;
