@@ -1,16 +1,23 @@
 """Initial guess of the reconstruction - counterparts of ``_init_y_dat``
 (unires/_core.py:371-399), of the label path ``_init_y_label`` /
 ``_warp_label`` (:402-436), of ``_resample_inplane`` (:457-492), and of the hyper-parameter step
-``_estimate_hyperpar`` (:96-142) with the regularisation half of ``_format_y``, ``_init_lam``
-(:273-281), and of the coregistration step ``_init_reg`` (:310-368).  Everything else in the
-reference's ``_core.py`` (I/O, atlas alignment, mean-space construction) is out of scope."""
+``_estimate_hyperpar`` (:96-142), of the coregistration step ``_init_reg`` (:310-368), and of the
+steps between them that make ``run.init`` whole: ``_read_data`` (:495-584), the ``_fix_affine`` guard
+(:145-168), ``_format_y`` (:171-285) with its regularisation half ``_init_lam`` (:273-281),
+``_proj_info_add`` (:439-454) and ``_write_data`` (:587-670).  Atlas alignment and cropping
+(``_crop_y``, ``reset_origin``) are out of scope."""
 import math
+import os
 
 import torch
 
-from . import _ops, preproc, stats
-from ._rigid import affine_basis
-from .spatial import _mat_shape, _m12, voxel_size
+from . import _ops, nifti, preproc, stats
+from . import _math
+from ._project import _proj_info
+from ._rigid import _expm, affine_basis
+from ._util import _read_image, _read_label, _write_image
+from .spatial import _mat_shape, _mean_space, _m12, affine_matrix_classic, voxel_size
+from .struct import _input, _output
 
 MAX_LABELS = 255  # the reference's limit (unires/_core.py:425)
 
@@ -172,3 +179,201 @@ def _init_reg(x, sett):
         for n in range(len(x[c])):
             x[c][n].rigid_q = torch.zeros(sett.rigid_basis.shape[0], device=sett.device, dtype=torch.float64)
     return x, sett
+
+
+_NOT_BUILT = {'crop': 'cropping to the atlas field of view', 'common_output': 'the atlas-aligned common output grid',
+              'do_atlas_align': 'atlas alignment', 'write_jtv': 'writing the JTV image'}
+
+
+def _not_built(sett, names):
+    """NotImplementedError for those of the settings ``names`` that are set (they need nitorch's atlas,
+    or an output fit() does not hand out); the message names the setting."""
+    for name in names:
+        if getattr(sett, name, False):
+            raise NotImplementedError('sett.%s: %s is not built' % (name, _NOT_BUILT[name]))
+
+
+def _read_data(data, sett):
+    """Parse the input data into ``x[c][n]`` structs (unires/_core.py:495-584).  ``data``: a path, a
+    list of paths (one per channel), a list of lists (repeats of a channel), ``[dat, mat]`` pairs in
+    the same nestings, an (X, Y, Z, C) array with its affine in ``sett.mat``, or the path of a 4-D
+    NIfTI.  Labels come from ``sett.label = (path, (channel, repeat))``."""
+    mat_vol = sett.mat
+    if isinstance(data, str):
+        file = nifti.map_file(data)
+        if len(file.shape) > 3:  # path to a 4-D NIfTI
+            data = file.fdata()
+            mat_vol = file.affine
+    try:
+        data.shape
+        data = data[..., None]
+        data = data[:, :, :, :, 0]
+        if mat_vol is None:
+            raise ValueError('Image data given as array, please also provide affine matrix in sett.mat!')
+    except AttributeError:
+        pass
+    if isinstance(data, str):
+        data = [data]
+    C = data.shape[3] if mat_vol is not None else len(data)
+
+    def one(src):
+        xn = _input()
+        xn.dat, xn.dim, xn.mat, xn.fname, xn.direc, xn.nam, xn.file, xn.ct = \
+            _read_image(src, sett.device, is_ct=sett.ct)
+        xn.dat = xn.dat.contiguous()  # (a channel of an (X, Y, Z, C) array is a strided view)
+        return xn
+    x = []
+    for c in range(C):
+        if mat_vol is None and isinstance(data[c], list) and isinstance(data[c][0], (str, list)):
+            x.append([one(data[c][n]) for n in range(len(data[c]))])  # possibly several repeats
+        elif mat_vol is not None:
+            x.append([one([data[..., c], mat_vol])])
+        else:
+            x.append([one(data[c])])
+    if sett.label is not None:
+        pth_label, (c, n) = sett.label[0], sett.label[1]
+        if 0 <= c < len(x) and 0 <= n < len(x[c]):
+            x[c][n] = _read_label(x[c][n], pth_label, sett)
+    if sett.do_print >= 1:
+        for c in range(len(x)):
+            for n in range(len(x[c])):
+                print('c={:}, n={:} | fname={:}'.format(c, n, x[c][n].fname))
+    return x
+
+
+def _fix_affine(x, sett):
+    """The reference resets the origin of CT observations here (unires/_core.py:145-168, nitorch's
+    ``reset_origin``); that is not built, so the combination is refused."""
+    if sett.do_res_origin and any(xn.ct for xc in x for xn in xc):
+        raise NotImplementedError('sett.do_res_origin: resetting the origin of CT observations is not built')
+    return x
+
+
+def _all_mat_dim_vx(x):
+    mats = torch.stack([torch.as_tensor(xn.mat).detach().to('cpu', torch.float64) for xc in x for xn in xc])
+    dims = torch.tensor([[float(d) for d in xn.dim] for xc in x for xn in xc], dtype=torch.float64)
+    return mats, dims, torch.stack([voxel_size(m) for m in mats])
+
+
+def _format_y(x, sett):
+    """Construct the output structs (unires/_core.py:171-285): decides between the three operator
+    regimes - ``sett.do_proj = False`` (A = I: one voxel size, one grid), 'denoising' with projection
+    (one voxel size, different fields of view: pull / push) and 'super-resolution' (thick slices) -,
+    builds the mean space (``spatial._mean_space``) where one is needed, applies ``sett.pow`` and
+    sets ``y[c].lam0`` (``_init_lam``).  ``y[c].mat`` is a float64 tensor on the host, like every
+    4x4 of this package; ``y[c].dim`` a tuple of ints."""
+    _not_built(sett, ('crop',))
+    vx_y = sett.vx
+    if vx_y == 0:
+        vx_y = None
+    if vx_y is not None:
+        if isinstance(vx_y, int):
+            vx_y = float(vx_y)
+        if isinstance(vx_y, float):
+            vx_y = (vx_y,) * 3
+        vx_y = torch.tensor(vx_y, dtype=torch.float64)
+    all_mat, all_dim, all_vx = _all_mat_dim_vx(x)
+    N = all_mat.shape[0]
+    if N == 1:
+        sett.unified_rigid = False
+        sett.clean_fov = True
+    mat_same = dim_same = vx_same = True
+    for n in range(1, N):
+        mat_same = mat_same & torch.equal(_math.round(all_mat[n - 1], 3), _math.round(all_mat[n], 3))
+        dim_same = dim_same & torch.equal(_math.round(all_dim[n - 1], 3), _math.round(all_dim[n], 3))
+        vx_same = vx_same & torch.equal(_math.round(all_vx[n - 1], 3), _math.round(all_vx[n], 3))
+    do_sr = True
+    sett.do_proj = True
+    if vx_y is None and ((N == 1) or vx_same):  # voxel size not given: the inputs'
+        vx_y = all_vx[0]
+    if vx_y is None:  # (the reference fails on the subtraction below)
+        raise ValueError('sett.vx = 0 or None keeps the voxel size of the inputs, which must then share one')
+    do_pow = (isinstance(sett.pow, (tuple, list)) and len(sett.pow) == 3) \
+        or (isinstance(sett.pow, int) and sett.pow > 0)
+    if vx_same and bool((torch.abs(all_vx[0] - vx_y) < 1e-3).all()):
+        do_sr = False
+        if mat_same and dim_same and not sett.unified_rigid and not do_pow:
+            mat, dim = all_mat[0], all_dim[0]
+            sett.do_proj = False
+    if do_sr or sett.do_proj:
+        mat, dim, vx_y = _mean_space(all_mat, all_dim, vx_y)
+        if do_pow:  # fixed output dimensions, centred on the mean space's
+            if isinstance(sett.pow, int):
+                dim2 = _math.ceil_pow(dim, p=2.0, l=2.0, mx=sett.pow)
+                dim3 = _math.ceil_pow(dim, p=2.0, l=3.0, mx=sett.pow)
+                ndim = torch.minimum(dim2, dim3)
+            else:
+                ndim = torch.as_tensor(sett.pow)
+            mat = mat.mm(affine_matrix_classic(-((ndim - dim) / 2).round()))
+            dim = ndim
+    sett.method = 'super-resolution' if do_sr else 'denoising'
+    if sett.method == 'denoising' or (N == 1 and x[0][0].ct):
+        sett.scaling = False
+    dim = tuple(dim.int().tolist())
+    if sett.do_print >= 1:
+        print('Mean space | dim={}, vx={}'.format(dim, tuple(float('%4.2f' % v) for v in voxel_size(mat).tolist())))
+    y = []
+    for c in range(len(x)):
+        y.append(_output())
+        y[c].dim = dim
+        y[c].mat = mat.double().clone()
+    return _init_lam(x, y, sett), sett
+
+
+RATIO_TOL = 1e-6  # relative: what _proj_info_add lets a voxel-size ratio exceed an integer by before rounding it up
+
+
+def _proj_info_add(x, y, sett):
+    """Adds the projection-operator descriptor ``po`` to every observation
+    (unires/_core.py:439-454).  The voxel ratio is rounded up with ``ratio_tol = RATIO_TOL``: against a
+    mean space, and after coregistration, the ratio of an axis that is not thick is 1 only up to the
+    rounding of the 4x4 algebra, and the plain ceil of ``_proj_info`` would make it 2 by chance."""
+    for c in range(len(x)):
+        for xn in x[c]:
+            rigid = _expm(xn.rigid_q, sett.rigid_basis)
+            xn.po = _proj_info(y[c].dim, y[c].mat, xn.dim, xn.mat, prof_ip=sett.profile_ip,
+                               prof_tp=sett.profile_tp, gap=sett.gap, device=sett.device, rigid=rigid,
+                               ratio_tol=RATIO_TOL)
+    return x
+
+
+def _write_data(x, y, sett):
+    """Format the output (unires/_core.py:587-670): every ``y[c].dat`` is clamped, in place, to the
+    range of its channel's observations; with ``sett.write_out`` the channels are written as
+    ``prefix + name`` (one file each, or one 4-D file when the data came as an array with
+    ``sett.mat``) into ``sett.dir_out``, else the first input's directory, else 'UniRes-output', and
+    the label image as ``prefix + 'label_' + name``.  Returns ``(dat_y (dim_y, C), pth_y, label,
+    pth_label)``; as in the reference the paths are the ones before the ``bids`` tag is added."""
+    _not_built(sett, ('write_jtv',))
+    mat = y[0].mat
+    dir_out = sett.dir_out
+    if dir_out is None:
+        dir_out = 'UniRes-output' if x[0][0].direc is None else x[0][0].direc
+    if sett.write_out and not os.path.isdir(dir_out):
+        os.makedirs(dir_out, exist_ok=True)
+
+    def path(c):
+        nam = str(c) + '.nii.gz' if x[c][0].nam is None else x[c][0].nam
+        return nam, os.path.join(dir_out, sett.prefix + nam)
+    pth_y, pth_label, label, chans = [], None, None, []
+    for c in range(len(x)):
+        dat = y[c].dat
+        mn = torch.stack([torch.min(xn.dat) for xn in x[c]]).min()
+        mx = torch.stack([torch.max(xn.dat) for xn in x[c]]).max()
+        torch.clamp(dat, min=mn, max=mx, out=dat)
+        if sett.write_out and sett.mat is None:
+            nam, fname = path(c)
+            pth_y.append(fname)
+            _write_image(dat, fname, bids=sett.bids, mat=mat, file=x[c][0].file, do_print=sett.do_print > 0)
+            if y[c].label is not None:
+                pth_label = os.path.join(dir_out, sett.prefix + 'label_' + nam)
+                label = y[c].label
+                _write_image(label, pth_label, bids=sett.bids, mat=mat, file=x[c][0].label[1],
+                             do_print=sett.do_print > 0)
+        chans.append(dat)
+    dat_y = torch.stack(chans, dim=3)
+    if sett.write_out and sett.mat is not None:
+        _, fname = path(0)
+        pth_y.append(fname)
+        _write_image(dat_y, fname, bids=sett.bids, mat=mat, file=x[0][0].file, do_print=sett.do_print > 0)
+    return dat_y, pth_y, label, pth_label

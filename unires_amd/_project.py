@@ -29,7 +29,7 @@ def _apply_scaling(dat, scl, dim):
 
 
 def _proj_info(dim_y, mat_y, dim_x, mat_x, rigid=None, prof_ip=0, prof_tp=0, gap=0.0,
-               device='cuda', scl=0.0, samp=0, gauss_lim=None):
+               device='cuda', scl=0.0, samp=0, gauss_lim=None, ratio_tol=0.0):
     """Define a projection operator object for _proj_apply.  All 4x4 arithmetic is
     float64 on the host (it is set-up work: once per input, again per rigid update)."""
     po = _proj_op()
@@ -68,9 +68,13 @@ def _proj_info(dim_y, mat_y, dim_x, mat_x, rigid=None, prof_ip=0, prof_tp=0, gap
         if min(dim_x) < 1:
             raise ValueError('sub-sampling leaves an empty image')
         po.dim_x, po.mat_x, po.vx_x = dim_x, mat_x, voxel_size(mat_x)
-    # low-res / high-res voxel ratio, rounded up, at least one
+    # low-res / high-res voxel ratio, rounded up, at least one.  ratio_tol (relative; 0: the reference's plain
+    # ceil) is the fraction by which a ratio may exceed an integer and still count as that integer: the ratio of
+    # equal voxel sizes comes out of the solve as 1 + 2e-16 as soon as mat_x carries a rotation (after
+    # coregistration, against a mean space), and a rotated affine read from a float32 sform as r (1 + 1e-7); the
+    # plain ceil turns either into the next integer
     lin = torch.linalg.solve(mat_y, mat_x)[:3, :3]
-    ratio = (lin ** 2).sum(0).sqrt().ceil().clamp(1)
+    ratio = ((lin ** 2).sum(0).sqrt() * (1.0 - float(ratio_tol))).ceil().clamp(1)
     po.ratio = tuple(int(r) for r in ratio.tolist())
     # intermediate (high-res sampling of the low-res FOV) space
     po.mat_yx = mat_x.matmul(torch.diag(torch.cat((1.0 / ratio, torch.ones(1, dtype=_F64)))))

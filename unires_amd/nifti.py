@@ -28,10 +28,8 @@ def _quaternion_affine(b, c, d, qfac, pixdim, offset):
     return M
 
 
-def read(path):
-    """Returns (data float32 ndarray, affine float64 (4,4), header dict)."""
-    with _open(path, 'rb') as f:
-        raw = f.read()
+def _header(raw):
+    """(shape, numpy dtype, data offset, slope, inter, affine, header dict) of the first 352 bytes."""
     if len(raw) < 352:
         raise ValueError('not a NIfTI-1 file: too short')
     end = '<' if struct.unpack('<i', raw[:4])[0] == 348 else '>'
@@ -49,13 +47,6 @@ def read(path):
     if datatype not in _DTYPES:
         raise ValueError('unsupported NIfTI datatype %d' % datatype)
     shape = tuple(int(d) for d in dim[1:1 + dim[0]])
-    n = int(np.prod(shape))
-    dt = np.dtype(end + _DTYPES[datatype])
-    off = int(vox_offset)
-    arr = np.frombuffer(raw, dtype=dt, count=n, offset=off).reshape(shape, order='F')
-    data = arr.astype(np.float32)
-    if slope not in (0.0,) and not (slope == 1.0 and inter == 0.0) and np.isfinite(slope):
-        data = data * np.float32(slope) + np.float32(inter)
     if sform_code > 0:
         affine = np.vstack([srow, [0, 0, 0, 1.0]])
     elif qform_code > 0:
@@ -64,7 +55,45 @@ def read(path):
         affine = np.diag([pixdim[1] or 1.0, pixdim[2] or 1.0, pixdim[3] or 1.0, 1.0])
     hdr = dict(dim=shape, datatype=datatype, pixdim=pixdim[1:4], slope=slope, inter=inter,
                qform_code=qform_code, sform_code=sform_code, endian=end)
-    return np.ascontiguousarray(data), affine.astype(np.float64), hdr
+    return shape, np.dtype(end + _DTYPES[datatype]), int(vox_offset), slope, inter, affine.astype(np.float64), hdr
+
+
+def read(path):
+    """Returns (data float32 ndarray, affine float64 (4,4), header dict)."""
+    with _open(path, 'rb') as f:
+        raw = f.read()
+    shape, dt, off, slope, inter, affine, hdr = _header(raw)
+    n = int(np.prod(shape))
+    arr = np.frombuffer(raw, dtype=dt, count=n, offset=off).reshape(shape, order='F')
+    data = arr.astype(np.float32)
+    if slope not in (0.0,) and not (slope == 1.0 and inter == 0.0) and np.isfinite(slope):
+        data = data * np.float32(slope) + np.float32(inter)
+    return np.ascontiguousarray(data), affine, hdr
+
+
+class _Mapped:
+    """What ``map_file`` returns: the file's shape and affine from its header; the voxels on demand."""
+
+    def __init__(self, path):
+        self._path = path
+        with _open(path, 'rb') as f:
+            self.shape, _, _, _, _, affine, self.header = _header(f.read(352))
+        import torch
+        self.affine = torch.from_numpy(affine)
+
+    def filename(self):
+        return self._path
+
+    def fdata(self, dtype=None, device='cpu', **kw):
+        import torch
+        dat = torch.from_numpy(read(self._path)[0]).to(device)
+        return dat if dtype is None else dat.to(dtype)
+
+
+def map_file(path):
+    """nitorch.io.map for the uses the reference makes of it (unires/_core.py:508-513): an object
+    with ``shape``, ``affine`` (float64 tensor), ``fdata()`` (float32 tensor) and ``filename()``."""
+    return _Mapped(path)
 
 
 def write(path, data, affine):

@@ -1,10 +1,15 @@
 """fit() - host-side mirror of the iteration loop of unires/run.py:24-207 on device-resident
 structs (no file I/O, no plotting): coarse-to-fine regularisation schedule, ADMM iterations
 until the model negative log-likelihood stops improving, optional even/odd slice-scaling
-updates, clean_fov post-processing.  Everything heavy goes through libunires_hip.so."""
+updates, clean_fov post-processing.  Everything heavy goes through libunires_hip.so.
+
+init() and preproc() - the reference's entry points around it (unires/run.py:210-318): from
+paths or arrays to the structs fit() takes, and from its result to clamped images on disk."""
 import torch
 
 from . import _lib
+from ._core import (_estimate_hyperpar, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
+                    _not_built, _proj_info_add, _read_data, _resample_inplane, _write_data)
 from ._host import wait_blocking
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
@@ -12,6 +17,7 @@ from ._rigid import _update_rigid
 from ._update import _admm_aux, _step_size, _update_admm, _update_scaling
 from .optim import get_gain
 from .spatial import _m12
+from .struct import settings
 
 
 def _get_sched(N, sett):
@@ -107,3 +113,43 @@ def fit(x, y, sett):
         dat_y = torch.stack([yc.dat for yc in y], dim=-1)
         info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone())
         return dat_y, y[0].mat, R, info
+
+
+def init(data, sett=None):
+    """Model initialiser (unires/run.py:210-282): reads the data, estimates the noise and intensity
+    hyper-parameters (with ``max_iter > 0``), resamples in plane where asked, coregisters, builds the
+    output space and the projection operators, and makes the initial guess of images and labels.
+
+    ``data``: paths (``['T1.nii', 'T2.nii']``; with repeats ``[['T1_1.nii', 'T1_2.nii'], ['T2.nii']]``),
+    ``[dat, mat]`` pairs in the same nestings, an (X, Y, Z, C) array with ``sett.mat``, or the path
+    of a 4-D NIfTI.  ``sett``: a ``settings()``; the defaults when None.  Returns ``(x, y, sett)``,
+    what ``fit`` takes."""
+    sett = settings() if sett is None else sett
+    _not_built(sett, ('crop', 'common_output', 'do_atlas_align', 'write_jtv'))
+    for name in ('plot_conv', 'show_hyperpar', 'show_jtv'):
+        if getattr(sett, name, False):
+            raise NotImplementedError('sett.%s: plotting is not built' % name)
+    with torch.no_grad():
+        x = _read_data(data, sett)
+        del data
+        if sett.max_iter > 0:
+            x = _estimate_hyperpar(x, sett)
+        x = _fix_affine(x, sett)
+        x = _resample_inplane(x, sett)
+        x, sett = _init_reg(x, sett)
+        y, sett = _format_y(x, sett)
+        x = _proj_info_add(x, y, sett)
+        y = _init_y_dat(x, y, sett)
+        y = _init_y_label(x, y, sett)
+        return x, y, sett
+
+
+def preproc(data, sett=None):
+    """Preprocess images (unires/run.py:285-318): ``init``, ``fit``, then ``_write_data``.  Returns
+    ``(dat_y, mat_y, pth_y)``: the reconstructions (dim_y, C) float32, clamped to the range of their
+    observations, the output affine, and the paths written (``prefix + name``; none with
+    ``write_out = False``).  With ``max_iter = 0`` the result is the initial guess."""
+    x, y, sett = init(data, sett)
+    _, mat_y, _, _ = fit(x, y, sett)
+    dat_y, pth_y, _, _ = _write_data(x, y, sett)
+    return dat_y, mat_y, pth_y

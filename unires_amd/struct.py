@@ -1,7 +1,7 @@
 """Data structures the hot path reads - counterparts of unires/struct.py:4-111.
 
-Only the fields the y-update path touches carry meaning here; the rest of the
-reference's ``settings`` (I/O, registration, plotting) is out of scope.
+``settings`` carries every field of the reference's, with the reference's defaults unless
+noted; the atlas and plotting fields exist so that ``init`` can refuse them by name.
 """
 
 
@@ -19,6 +19,11 @@ class _input:
         self.sd = 1.0
         self.rigid_q = None
         self.label = None   # [dat, header] of a manual label volume (_util._read_label)
+        # where the observation was read from (_core._read_data; None for in-memory data)
+        self.file = None    # the header the file was read with
+        self.fname = None
+        self.direc = None
+        self.nam = None
 
 
 class _output:
@@ -116,3 +121,22 @@ class settings:
         self.fix = 0  # flat index (channels, then repeats) of the observation the others align to
         self.do_atlas_align = False
         self.mat_coreg = None  # (N, 4, 4) float64 transforms _init_reg found
+        # ---- init() / preproc() (run.py, _core._format_y / _read_data / _write_data; unires/struct.py) ----
+        self.mat = None  # affine of the observations when they are given as one (X, Y, Z, C) array
+        self.ct = False  # the data could be CT
+        self.pow = 0  # output dimensions: an int > 0 (powers of two or 3 * powers of two, at most pow) or a 3-tuple
+        self.dir_out = None  # output directory; None: the first input's, else 'UniRes-output'
+        self.prefix = 'u_'
+        self.bids = False  # add the '_space-unires_' tag to the written names
+        self.write_out = True
+        # the atlas, the CT origin reset, the JTV file and plotting are not built: init() / _format_y / _write_data
+        # raise NotImplementedError when one of the switches below is set (atlas_rigid and fov only qualify them)
+        self.atlas_rigid = False
+        self.common_output = False
+        self.crop = False
+        self.do_res_origin = False
+        self.fov = 'brain'
+        self.write_jtv = False
+        self.plot_conv = False
+        self.show_hyperpar = False
+        self.show_jtv = False
