@@ -196,6 +196,24 @@ int unires_div_fwd_zero(const float *src3, const int32_t dim[3], const float vx[
 int unires_dtd(const float *src, const int32_t dim[3], const float vx[3], float a, float c,
                float *dst, void *stream);
 
+/* The difference the regulariser's D takes (nitorch diff1d / div1d `which`, the reference's sett.diff; zero bound:
+ * samples outside the volume read as 0).  Restated from nitorch's published definitions  [recalled]:
+ *   forward : (D y)[i] = (y[i+1] - y[i]) / vx         (Dt g)[i] = (g[i-1] - g[i]) / vx
+ *   backward: (D y)[i] = (y[i] - y[i-1]) / vx         (Dt g)[i] = (g[i] - g[i+1]) / vx
+ *   central : (D y)[i] = (y[i+1] - y[i-1]) / (2 vx)   (Dt g)[i] = (g[i-1] - g[i+1]) / (2 vx)
+ * Any other value is UNIRES_ERR_ARG.  UNIRES_DIFF_FORWARD gives the bits of the entry points without `which`. */
+#define UNIRES_DIFF_FORWARD 0
+#define UNIRES_DIFF_BACKWARD 1
+#define UNIRES_DIFF_CENTRAL 2
+
+/* unires_grad_fwd_zero / unires_div_fwd_zero / unires_dtd with the difference chosen. */
+int unires_grad_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
+                      float *dst3, void *stream);
+int unires_div_which(const float *src3, const int32_t dim[3], const float vx[3], int32_t which,
+                     float *dst, void *stream);
+int unires_dtd_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which, float a,
+                     float c, float *dst, void *stream);
+
 /* ------------------------------------------------------------------------
  * Fused level - plan + matvec + RHS + CG  (unires/_update.py:118-152)
  * ---------------------------------------------------------------------- */
@@ -230,6 +248,11 @@ int unires_plan_set_repeat(unires_plan_t *plan, int32_t n, const unires_repeat_t
  * plan then sizes the persistent kernels of its matvec so that other channels' kernels find room on the CUs (see
  * api_plan.hip; results are unchanged, reductions are summed in another - still fixed - order).  1 = the default. */
 int unires_plan_set_concurrency(unires_plan_t *plan, int32_t n_concurrent);
+/* The difference of the plan's regulariser (UNIRES_DIFF_*; a new plan has UNIRES_DIFF_FORWARD): the D of the matvec,
+ * of the right-hand side and of the FFT preconditioner's symbol.  A non-forward plan applies every AtA on the
+ * kernels a forward plan uses, without their stencil epilogue, and closes the matvec with one streaming stencil
+ * pass (stencil.hip: k_dtd_flat_w).  Changing it drops the captured CG graphs and the built preconditioner. */
+int unires_plan_set_diff(unires_plan_t *plan, int32_t which);
 /* Bytes of device workspace the plan owns. */
 int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
 /* Which kernels repeat n's operator runs on (no counterpart in the reference, whose _proj_apply
@@ -346,6 +369,14 @@ int unires_zw_update(const float *const *y_ptrs, const float *lam, int32_t n_cha
 /* -ln p(y) = sum_v sqrt(sum_c |lam_c D y_c|^2)  (_update.py:419-425) -> *out_dev (float64). */
 int unires_nll_prior(const float *const *y_ptrs, const float *lam, int32_t n_channels,
                      const int32_t dim[3], const float vx[3], double *out_dev, void *stream);
+
+/* unires_zw_update / unires_nll_prior with the difference of D chosen (UNIRES_DIFF_*). */
+int unires_zw_update_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                           const int32_t dim[3], const float vx[3], int32_t which, float rho, float alpha,
+                           float *z, float *w, float *jtv, void *stream);
+int unires_nll_prior_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                           const int32_t dim[3], const float vx[3], int32_t which, double *out_dev,
+                           void *stream);
 
 /* sum_{x != 0} (x - ay)^2 in float64  (_update.py:414-417; the caller multiplies by tau/2). */
 int unires_masked_sse(const float *x, const float *ay, int64_t n, double *out_dev, void *stream);

@@ -64,11 +64,16 @@ SIGNATURES = {
     'unires_div_fwd_zero': (C.c_int, [C.c_void_p, c_i32x3, c_f32x3, C.c_void_p, C.c_void_p]),
     'unires_dtd': (C.c_int, [C.c_void_p, c_i32x3, c_f32x3, C.c_float, C.c_float, C.c_void_p,
                              C.c_void_p]),
+    'unires_grad_which': (C.c_int, [C.c_void_p, c_i32x3, c_f32x3, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_div_which': (C.c_int, [C.c_void_p, c_i32x3, c_f32x3, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_dtd_which': (C.c_int, [C.c_void_p, c_i32x3, c_f32x3, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                   C.c_void_p]),
     'unires_plan_create': (C.c_int, [C.POINTER(C.c_void_p), c_i32x3, c_f32x3, C.c_int32,
                                      C.c_int32, C.POINTER(Repeat), C.c_float]),
     'unires_plan_destroy': (C.c_int, [C.c_void_p]),
     'unires_plan_set_repeat': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Repeat)]),
     'unires_plan_set_concurrency': (C.c_int, [C.c_void_p, C.c_int32]),
+    'unires_plan_set_diff': (C.c_int, [C.c_void_p, C.c_int32]),
     'unires_plan_workspace_bytes': (C.c_int64, [C.c_void_p]),
     'unires_orient_of': (C.c_int, [c_f32x12, c_i32x3, c_i32x3]),
     'unires_plan_repeat_info': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32 * 8]),
@@ -99,6 +104,11 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     'unires_nll_prior': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, c_i32x3,
                                    c_f32x3, C.c_void_p, C.c_void_p]),
+    'unires_zw_update_which': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, c_i32x3,
+                                         c_f32x3, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    'unires_nll_prior_which': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, c_i32x3,
+                                         c_f32x3, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_scaling_sums': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p,
                                       C.c_void_p]),
     'unires_rigid_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_float * 72,
@@ -110,6 +120,18 @@ SIGNATURES = {
     'unires_mark_signal': (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     'unires_mark_read': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
+
+# sett.diff / nitorch's `which` -> UNIRES_DIFF_*
+DIFF = {'forward': 0, 'backward': 1, 'central': 2}
+
+
+def diff_code(which, arg='diff'):
+    """UNIRES_DIFF_* of a difference name; anything but the three built is a ValueError naming ``arg``."""
+    try:
+        return DIFF[which]
+    except (KeyError, TypeError):
+        raise ValueError("%s must be 'forward', 'backward' or 'central', not %r" % (arg, which)) from None
+
 
 _lib = None
 

@@ -55,7 +55,8 @@ def _repeat_desc(po, tau, method, regime, keep):
 class ChannelPlan:
     """One channel's fused operator. ``xs``: list of (po, tau) per repeat."""
 
-    def __init__(self, dim_y, vx_y, repeats, method, do_proj, fov_tol=FOV_TOL, device=None):
+    def __init__(self, dim_y, vx_y, repeats, method, do_proj, fov_tol=FOV_TOL, device=None, diff='forward'):
+        _lib.diff_code(diff, 'diff')
         self.lib = _lib.load()
         # the plan's workspace lives on ONE device: the one current when it is created
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
@@ -63,6 +64,7 @@ class ChannelPlan:
             self.device = torch.device('cuda', torch.cuda.current_device())
         with torch.cuda.device(self.device):
             self._create(dim_y, vx_y, repeats, method, do_proj, fov_tol)
+        self.set_diff(diff)
 
     def _create(self, dim_y, vx_y, repeats, method, do_proj, fov_tol):
         self.dim_y = tuple(int(d) for d in dim_y)
@@ -74,6 +76,7 @@ class ChannelPlan:
                                        for po, tau in repeats])
         self._h = C.c_void_p()
         self._concurrency = 1
+        self.diff = 'forward'
         check(self.lib.unires_plan_create(C.byref(self._h), i3(self.dim_y), f3(vx_y), self.regime,
                                           len(repeats), arr, fov_tol))
         self.dims_x = [self.dim_y if self.regime == REGIME_IDENTITY else tuple(po.dim_x)
@@ -149,6 +152,16 @@ class ChannelPlan:
         if n != self._concurrency:
             check(self.lib.unires_plan_set_concurrency(self._h, n))
             self._concurrency = n
+
+    def set_diff(self, diff):
+        """The difference of the plan's D: 'forward' (a new plan's) | 'backward' | 'central' (``unires_plan_set_diff``):
+        the matvec, the right-hand side and the FFT preconditioner follow it.  Free when it is what the plan has;
+        a change drops the captured solve and the built preconditioner."""
+        code = _lib.diff_code(diff, 'diff')
+        if diff != self.diff:
+            with torch.cuda.device(self.device):
+                check(self.lib.unires_plan_set_diff(self._h, code))
+            self.diff = diff
 
     def _y(self, t, name):
         v, _ = _vol(t, name)

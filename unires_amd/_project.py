@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import _kernels, _ops
+from . import _kernels, _lib, _ops
 from ._plan import ChannelPlan, proj_matrix
 from .spatial import _m12, voxel_size
 from .struct import _proj_op
@@ -152,9 +152,17 @@ def _plan_signature(x, y, method, do):
     return tuple(sig)
 
 
-def _channel_plan(x, y, method, do, vx_y=None):
+def _channel_plan(x, y, method, do, vx_y=None, diff=None):
     """Fused per-channel plan, cached on the output struct and rebuilt when any
-    operator parameter (rigid, scl, tau, dims) changed."""
+    operator parameter (rigid, scl, tau, dims) changed.  ``diff``: the difference of the plan's D
+    ('forward' | 'backward' | 'central'); None leaves the plan's as it is (callers that do not involve D)."""
+    plan = _channel_plan_any(x, y, method, do, vx_y)
+    if diff is not None:
+        plan.set_diff(diff)
+    return plan
+
+
+def _channel_plan_any(x, y, method, do, vx_y=None):
     sig = _plan_signature(x, y, method, do)
     cached = getattr(y, '_plan', None)
     if cached is not None and cached[0] == sig:
@@ -173,12 +181,14 @@ def _channel_plan(x, y, method, do, vx_y=None):
             return plan
         except ValueError:
             pass  # the new repeat does not fit the workspace: build a new plan
+    old_diff = 'forward'
     if cached is not None:
+        old_diff = cached[1].diff
         cached[1].close()
     if vx_y is None:
         vx_y = voxel_size(y.mat)
     vx = [float(v) for v in torch.as_tensor(vx_y).detach().cpu().tolist()]
-    plan = ChannelPlan(y.dim, vx, [(xn.po, xn.tau) for xn in x], method, do, device=y.dat.device)
+    plan = ChannelPlan(y.dim, vx, [(xn.po, xn.tau) for xn in x], method, do, device=y.dat.device, diff=old_diff)
     y._plan = (sig, plan)
     return plan
 
@@ -188,9 +198,10 @@ def _proj(operator, dat, x, y, method='super-resolution', do=True, rho=1, n=0, v
     """Projects image data by A, At or AtA; ``x`` is the list of repeats of one
     channel, ``y`` its output struct.  'AtA' is the fused
     sum_n tau_n AtA_n dat + rho lam^2 DtD dat."""
-    if bound != 'zero' or diff != 'forward' or interpolation not in ('linear', 1):
-        raise NotImplementedError("only bound='zero', diff='forward', linear are built")
-    plan = _channel_plan(x, y, method, do, vx_y)
+    _lib.diff_code(diff, 'diff')
+    if bound != 'zero' or interpolation not in ('linear', 1):
+        raise NotImplementedError("only bound='zero', linear are built")
+    plan = _channel_plan(x, y, method, do, vx_y, diff=diff if operator == 'AtA' else None)
     if operator == 'AtA':
         return plan.matvec(dat, float(rho), float(y.lam))
     if operator not in ('A', 'At'):
@@ -199,10 +210,11 @@ def _proj(operator, dat, x, y, method='super-resolution', do=True, rho=1, n=0, v
 
 
 def _DtD(dat, vx_y, bound='zero', diff='forward'):
-    """Divergence of the gradient, one 7-point stencil pass."""
-    if bound != 'zero' or diff != 'forward':
-        raise NotImplementedError("only bound='zero', diff='forward' are built")
-    return _ops.dtd(dat, vx_y, a=0.0, c=1.0)
+    """Divergence of the gradient, one stencil pass (7 points; central differences: the 6 at distance 2)."""
+    _lib.diff_code(diff, 'diff')
+    if bound != 'zero':
+        raise NotImplementedError("only bound='zero' is built")
+    return _ops.dtd(dat, vx_y, a=0.0, c=1.0, which=diff)
 
 
 def _check_adjoint(po, method, bound='zero', interpolation='linear', dtype=torch.float32):

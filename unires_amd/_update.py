@@ -37,6 +37,13 @@ def _step_size(x, y, sett, verbose=False):
     return sett.rho_scl * torch.sqrt(torch.mean(all_tau)) / torch.mean(all_lam)
 
 
+def _diff(sett):
+    """sett.diff ('forward' where the settings object has none), checked: the D of every term of the regulariser."""
+    diff = getattr(sett, 'diff', 'forward')
+    _lib.diff_code(diff, 'sett.diff')
+    return diff
+
+
 class _Precond:
     """Callable x -> x / M like the lambda unires/_update.py:100 returns; carries the plan
     that holds the device copy of M so cg() can run the preconditioned iteration on device."""
@@ -54,7 +61,7 @@ def _precond(x, y, rho, sett):
     M = tau AtA(1) + 2 rho lam^2 sum(1/vx^2) for one channel (x = x[c], y = y[c])."""
     if len(x) != 1:
         raise ValueError('CG pre-conditioning only supports one repeat per contrast.')
-    plan = _channel_plan(x, y, sett.method, sett.do_proj, voxel_size(y.mat).float())
+    plan = _channel_plan(x, y, sett.method, sett.do_proj, voxel_size(y.mat).float(), diff=_diff(sett))
     M = torch.empty(tuple(y.dim), dtype=torch.float32, device=y.dat.device)
     plan.precond_build(float(rho), float(y.lam), mode='jacobi', out=M)
     return _Precond(plan, M, 'jacobi')
@@ -86,7 +93,7 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
     pre = getattr(sett, 'cgs_precond', 'none')
     if not concurrent:
         for c in range(C):
-            plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y)
+            plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett))
             plan.set_concurrency(1)
             lam = float(y[c].lam)
             if getattr(sett, 'cache_atx', True) and not sync:
@@ -106,7 +113,7 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
     streams = _side_streams(y[0].dat.device, C)
     plans, bs = [], []
     for c in range(C):
-        plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y)
+        plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett))
         plan.set_concurrency(C)  # (its persistent kernels leave the other channels' kernels room on the CUs)
         lam = float(y[c].lam)
         b = tmp if c == 0 else plan.rhs_buffer(tmp)
@@ -177,8 +184,13 @@ def _update_zw(y, z, w, rho, tmp, sett):
         raise ValueError('unires_amd: tmp must be a contiguous (X,Y,Z) tensor')
     vx = [float(v) for v in voxel_size(y[0].mat).tolist()]
     ptrs, lams = _chan_args(y)
-    check(_lib.load().unires_zw_update(ptrs, lams, len(y), i3(y[0].dim), f3(vx), float(rho),
-                                       float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
+    diff = _lib.diff_code(_diff(sett), 'sett.diff')
+    if diff == 0:
+        check(_lib.load().unires_zw_update(ptrs, lams, len(y), i3(y[0].dim), f3(vx), float(rho),
+                                           float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
+    else:
+        check(_lib.load().unires_zw_update_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, float(rho),
+                                                 float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
     return z, w, tmp
 
 
@@ -199,7 +211,11 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64):
             nll_xy = nll_xy + 0.5 * float(x[c][n].tau) * sse
     ptrs, lams = _chan_args(y)
     nll_y = torch.zeros((), dtype=torch.float64, device=dev)
-    check(lib.unires_nll_prior(ptrs, lams, len(y), i3(y[0].dim), f3(vx), _ptr(nll_y), _stream()))
+    diff = _lib.diff_code(_diff(sett), 'sett.diff')
+    if diff == 0:
+        check(lib.unires_nll_prior(ptrs, lams, len(y), i3(y[0].dim), f3(vx), _ptr(nll_y), _stream()))
+    else:
+        check(lib.unires_nll_prior_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, _ptr(nll_y), _stream()))
     return nll_xy + nll_y, nll_xy, nll_y
 
 

@@ -24,13 +24,27 @@ struct ChanPtrs {  // up to 8 channels per launch; more channels run as chained 
   int last;   // 0: the running squared magnitude is stored to `scale` instead of the final result
 };
 
-// forward differences of y at (i,j,k), zero bound, times lam / vx
+// differences of y at (i,j,k), zero bound, times lam / vx: forward, or W's (sx, sy, sz then carry diff_grad_scale(W))
+template <int W>
 __device__ __forceinline__ void grad_at(const float *__restrict__ y, size_t idx, int i, int j,
                                         int k, const Dim3i &d, float sx, float sy, float sz,
                                         float &gx, float &gy, float &gz) {
   const size_t px = (size_t)d.y * d.z, py = d.z;
   const bool hx = i + 1 < d.x, hy = j + 1 < d.y, hz = k + 1 < d.z;
   const float c = y[idx];
+  if (W != kDiffForward) {
+    const bool lx = i > 0, ly = j > 0, lz = k > 0;
+    const float mx = y[lx ? idx - px : idx], my = y[ly ? idx - py : idx], mz = y[lz ? idx - 1 : idx];
+    float ux = c, uy = c, uz = c;  // backward: y[i] - y[i-1]
+    if (W == kDiffCentral) {       // central: y[i+1] - y[i-1]
+      const float vx = y[hx ? idx + px : idx], vy = y[hy ? idx + py : idx], vz = y[hz ? idx + 1 : idx];
+      ux = hx ? vx : 0.f, uy = hy ? vy : 0.f, uz = hz ? vz : 0.f;
+    }
+    gx = (ux - (lx ? mx : 0.f)) * sx;
+    gy = (uy - (ly ? my : 0.f)) * sy;
+    gz = (uz - (lz ? mz : 0.f)) * sz;
+    return;
+  }
   const float vx = y[hx ? idx + px : idx], vy = y[hy ? idx + py : idx], vz = y[hz ? idx + 1 : idx];
   gx = ((hx ? vx : 0.f) - c) * sx;
   gy = ((hy ? vy : 0.f) - c) * sy;
@@ -43,7 +57,7 @@ __device__ __forceinline__ void grad_at(const float *__restrict__ y, size_t idx,
 // divisions (r3's flat tile loop paid two 64-bit divisions per tile: 1.6 - 2.9 TB/s); NC channels compiled
 // in (0: any number up to 8), so that the 7 loads per channel and voxel of all channels are in flight
 // together; the sum over channels keeps its order and float32 arithmetic.
-template <int NC>
+template <int NC, int W>
 __global__ void __launch_bounds__(kBlock)
     k_jtv_scale(ChanPtrs C, const float *__restrict__ w, const float *__restrict__ z_old, Dim3i d,
                 float ivx, float ivy, float ivz, float rho, float alpha, float *__restrict__ scale,
@@ -64,7 +78,7 @@ __global__ void __launch_bounds__(kBlock)
       for (int c = 0; c < (NC ? NC : 8); ++c) {
         if (c >= nc) break;
         float gx, gy, gz;
-        grad_at(C.y[c], idx, i, j, k, d, C.lam[c] * ivx, C.lam[c] * ivy, C.lam[c] * ivz, gx, gy, gz);
+        grad_at<W>(C.y[c], idx, i, j, k, d, C.lam[c] * ivx, C.lam[c] * ivy, C.lam[c] * ivz, gx, gy, gz);
         const size_t o = (size_t)(C.c0 + c) * 3 * n + idx;
         if (alpha != 1.f) {  // Dy = alpha*Dy + (1-alpha)*z_old   (_update.py:169-170)
           gx = alpha * gx + (1.f - alpha) * z_old[o];
@@ -94,6 +108,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // z_c = s * (w_c/rho + Dy_c);  w_c += rho * (Dy_c - z_c)     for ONE channel
+template <int W>
 __global__ void __launch_bounds__(kBlock)
     k_zw_update(const float *__restrict__ y, float lam, const float *__restrict__ scale,
                 float *__restrict__ z, float *__restrict__ w, Dim3i d, float ivx, float ivy,
@@ -105,7 +120,7 @@ __global__ void __launch_bounds__(kBlock)
   const size_t n = d.numel();
   const size_t idx = ((size_t)i * d.y + j) * d.z + k;
   float g[3];
-  grad_at(y, idx, i, j, k, d, lam * ivx, lam * ivy, lam * ivz, g[0], g[1], g[2]);
+  grad_at<W>(y, idx, i, j, k, d, lam * ivx, lam * ivy, lam * ivz, g[0], g[1], g[2]);
   const float s = scale[idx], irho = 1.f / rho;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -298,7 +313,7 @@ int jtv_scale_blocks(Dim3i d) {
 
 int launch_jtv_scale(const float *const *y, const float *lam, int nc, const float *w,
                      const float *z_old, Dim3i d, const float vx[3], float rho, float alpha,
-                     float *scale, double *part, double *out, int norm_only, hipStream_t st) {
+                     float *scale, double *part, double *out, int norm_only, hipStream_t st, int which) {
   // The joint-TV magnitude couples all channels of a voxel (unires/_update.py:166-173 loops over any
   // C); the kernel takes 8 channel pointers by value, so more channels run as a chain of launches
   // that carry the running sum of squares in `scale`.
@@ -307,14 +322,23 @@ int launch_jtv_scale(const float *const *y, const float *lam, int nc, const floa
   const dim3 grid = jtv_grid(d);
   const int g = (int)(grid.x * grid.y * grid.z);
   double *partials = out ? part : nullptr;
+  // (central's 1/2 goes into the scale: a power of two, exact)
+  const float h = diff_grad_scale(which);
+  const float ivx = 1.f / vx[0] * h, ivy = 1.f / vx[1] * h, ivz = 1.f / vx[2] * h;
   for (int c0 = 0; c0 < nc; c0 += 8) {
     ChanPtrs C;
     C.n = nc - c0 < 8 ? nc - c0 : 8;
     C.c0 = c0, C.first = c0 == 0, C.last = c0 + 8 >= nc;
     for (int c = 0; c < 8; ++c) C.y[c] = y[c0 + (c < C.n ? c : 0)], C.lam[c] = lam[c0 + (c < C.n ? c : 0)];
-#define JTV_LAUNCH(NCV)                                                                               \
-  hipLaunchKernelGGL(k_jtv_scale<NCV>, grid, vblock(), 0, st, C, w, z_old, d, 1.f / vx[0], 1.f / vx[1], \
-                     1.f / vx[2], rho, alpha, scale, partials, norm_only)
+#define JTV_LAUNCH_W(NCV, WV)                                                                            \
+  hipLaunchKernelGGL((k_jtv_scale<NCV, WV>), grid, vblock(), 0, st, C, w, z_old, d, ivx, ivy, ivz, rho, alpha, \
+                     scale, partials, norm_only)
+#define JTV_LAUNCH(NCV)                                      \
+  switch (which) {                                           \
+    case kDiffBackward: JTV_LAUNCH_W(NCV, kDiffBackward); break; \
+    case kDiffCentral: JTV_LAUNCH_W(NCV, kDiffCentral); break;   \
+    default: JTV_LAUNCH_W(NCV, kDiffForward); break;         \
+  }
     switch (C.n) {
       case 1: JTV_LAUNCH(1); break;
       case 2: JTV_LAUNCH(2); break;
@@ -323,16 +347,25 @@ int launch_jtv_scale(const float *const *y, const float *lam, int nc, const floa
       default: JTV_LAUNCH(0); break;
     }
 #undef JTV_LAUNCH
+#undef JTV_LAUNCH_W
   }
   if (out) launch_sum_cols(part, g, 1, out, st);
   return g;
 }
 
 void launch_zw_update(const float *y, float lam, const float *scale, float *z, float *w, Dim3i d,
-                      const float vx[3], float rho, float alpha, hipStream_t st) {
+                      const float vx[3], float rho, float alpha, hipStream_t st, int which) {
   const dim3 grid((d.z + kWave - 1) / kWave, (d.y + 3) / 4, d.x);
-  hipLaunchKernelGGL(k_zw_update, grid, vblock(), 0, st, y, lam, scale, z, w, d, 1.f / vx[0],
-                     1.f / vx[1], 1.f / vx[2], rho, alpha);
+  const float h = diff_grad_scale(which);
+  const float ivx = 1.f / vx[0] * h, ivy = 1.f / vx[1] * h, ivz = 1.f / vx[2] * h;
+#define ZW_LAUNCH(WV) \
+  hipLaunchKernelGGL(k_zw_update<WV>, grid, vblock(), 0, st, y, lam, scale, z, w, d, ivx, ivy, ivz, rho, alpha)
+  switch (which) {
+    case kDiffBackward: ZW_LAUNCH(kDiffBackward); break;
+    case kDiffCentral: ZW_LAUNCH(kDiffCentral); break;
+    default: ZW_LAUNCH(kDiffForward); break;
+  }
+#undef ZW_LAUNCH
 }
 
 int masked_sse_blocks(size_t n) {

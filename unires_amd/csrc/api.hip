@@ -309,35 +309,63 @@ extern "C" int unires_conv_up3d(const float *src, const int32_t sdim[3],
   return UNIRES_OK;
 }
 
-extern "C" int unires_grad_fwd_zero(const float *src, const int32_t dim[3], const float vx[3],
-                                    float *dst3, void *stream) {
+static int grad_impl(const float *src, const int32_t dim[3], const float vx[3], int which, float *dst3, void *stream) {
   if (!src || !dst3 || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
-  launch_grad(src, mk(dim), vx, dst3, (hipStream_t)stream);
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
+  launch_grad(src, mk(dim), vx, dst3, (hipStream_t)stream, which);
   CHECK_LAUNCH();
   return UNIRES_OK;
+}
+
+static int div_impl(const float *src3, const int32_t dim[3], const float vx[3], int which, float *dst, void *stream) {
+  if (!src3 || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
+  launch_div(src3, nullptr, 1.f, 0.f, mk(dim), vx, 1.f, nullptr, dst, (hipStream_t)stream, which);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+static int dtd_impl(const float *src, const int32_t dim[3], const float vx[3], int which, float a, float c, float *dst,
+                    void *stream) {
+  if (!src || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
+  if (src == dst) return fail(UNIRES_ERR_ARG, "dtd cannot run in place");
+  launch_dtd(src, mk(dim), vx, a, c, dst, nullptr, nullptr, nullptr, (hipStream_t)stream, which);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_grad_fwd_zero(const float *src, const int32_t dim[3], const float vx[3],
+                                    float *dst3, void *stream) {
+  return grad_impl(src, dim, vx, kDiffForward, dst3, stream);
+}
+extern "C" int unires_grad_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
+                                 float *dst3, void *stream) {
+  return grad_impl(src, dim, vx, which, dst3, stream);
 }
 
 extern "C" int unires_div_fwd_zero(const float *src3, const int32_t dim[3], const float vx[3],
                                    float *dst, void *stream) {
-  if (!src3 || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
-  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
-  if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
-  launch_div(src3, nullptr, 1.f, 0.f, mk(dim), vx, 1.f, nullptr, dst, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return UNIRES_OK;
+  return div_impl(src3, dim, vx, kDiffForward, dst, stream);
+}
+extern "C" int unires_div_which(const float *src3, const int32_t dim[3], const float vx[3], int32_t which,
+                                float *dst, void *stream) {
+  return div_impl(src3, dim, vx, which, dst, stream);
 }
 
 extern "C" int unires_dtd(const float *src, const int32_t dim[3], const float vx[3], float a,
                           float c, float *dst, void *stream) {
-  if (!src || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
-  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
-  if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
-  if (src == dst) return fail(UNIRES_ERR_ARG, "dtd cannot run in place");
-  launch_dtd(src, mk(dim), vx, a, c, dst, nullptr, nullptr, nullptr, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return UNIRES_OK;
+  return dtd_impl(src, dim, vx, kDiffForward, a, c, dst, stream);
+}
+extern "C" int unires_dtd_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
+                                float a, float c, float *dst, void *stream) {
+  return dtd_impl(src, dim, vx, which, a, c, dst, stream);
 }
 
 // --------------------------------------------------------------------------
@@ -351,31 +379,42 @@ static int check_channels(const float *const *y_ptrs, const float *lam, int32_t 
   return UNIRES_OK;
 }
 
-extern "C" int unires_zw_update(const float *const *y_ptrs, const float *lam, int32_t n_channels,
-                                const int32_t dim[3], const float vx[3], float rho, float alpha,
-                                float *z, float *w, float *jtv, void *stream) {
+static int zw_impl(const float *const *y_ptrs, const float *lam, int32_t n_channels, const int32_t dim[3],
+                   const float vx[3], int which, float rho, float alpha, float *z, float *w, float *jtv, void *stream) {
   int rc = check_channels(y_ptrs, lam, n_channels);
   if (rc) return rc;
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
   if (!z || !w || !jtv || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
   if (!(rho > 0.f)) return fail(UNIRES_ERR_ARG, "rho must be positive");
   hipStream_t st = (hipStream_t)stream;
   const Dim3i d = mk(dim);
-  launch_jtv_scale(y_ptrs, lam, n_channels, w, z, d, vx, rho, alpha, jtv, nullptr, nullptr, 0, st);
+  launch_jtv_scale(y_ptrs, lam, n_channels, w, z, d, vx, rho, alpha, jtv, nullptr, nullptr, 0, st, which);
   const size_t n = d.numel();
   for (int c = 0; c < n_channels; ++c)
     launch_zw_update(y_ptrs[c], lam[c], jtv, z + (size_t)c * 3 * n, w + (size_t)c * 3 * n, d, vx,
-                     rho, alpha, st);
+                     rho, alpha, st, which);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
 
-extern "C" int unires_nll_prior(const float *const *y_ptrs, const float *lam, int32_t n_channels,
-                                const int32_t dim[3], const float vx[3], double *out_dev,
-                                void *stream) {
+extern "C" int unires_zw_update(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                const int32_t dim[3], const float vx[3], float rho, float alpha,
+                                float *z, float *w, float *jtv, void *stream) {
+  return zw_impl(y_ptrs, lam, n_channels, dim, vx, kDiffForward, rho, alpha, z, w, jtv, stream);
+}
+extern "C" int unires_zw_update_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                      const int32_t dim[3], const float vx[3], int32_t which, float rho,
+                                      float alpha, float *z, float *w, float *jtv, void *stream) {
+  return zw_impl(y_ptrs, lam, n_channels, dim, vx, which, rho, alpha, z, w, jtv, stream);
+}
+
+static int nll_prior_impl(const float *const *y_ptrs, const float *lam, int32_t n_channels, const int32_t dim[3],
+                          const float vx[3], int which, double *out_dev, void *stream) {
   int rc = check_channels(y_ptrs, lam, n_channels);
   if (rc) return rc;
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
   if (!out_dev || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
@@ -406,9 +445,20 @@ extern "C" int unires_nll_prior(const float *const *y_ptrs, const float *lam, in
   }
   double *part = nullptr;
   if ((rc = reduce_scratch(st, (size_t)jtv_scale_blocks(mk(dim)), &part))) return rc;
-  launch_jtv_scale(y_ptrs, lam, n_channels, nullptr, nullptr, mk(dim), vx, 1.f, 1.f, acc, part, out_dev, 1, st);
+  launch_jtv_scale(y_ptrs, lam, n_channels, nullptr, nullptr, mk(dim), vx, 1.f, 1.f, acc, part, out_dev, 1, st, which);
   CHECK_LAUNCH();
   return UNIRES_OK;
+}
+
+extern "C" int unires_nll_prior(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                const int32_t dim[3], const float vx[3], double *out_dev,
+                                void *stream) {
+  return nll_prior_impl(y_ptrs, lam, n_channels, dim, vx, kDiffForward, out_dev, stream);
+}
+extern "C" int unires_nll_prior_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                      const int32_t dim[3], const float vx[3], int32_t which, double *out_dev,
+                                      void *stream) {
+  return nll_prior_impl(y_ptrs, lam, n_channels, dim, vx, which, out_dev, stream);
 }
 
 extern "C" int unires_scaling_sums(const float *x, const float *ay, const int32_t dim[3],

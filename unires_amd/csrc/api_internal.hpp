@@ -179,6 +179,7 @@ struct unires_plan {
   float vx[3];
   int regime;
   float fov_tol;
+  int diff = UNIRES_DIFF_FORWARD;  // the difference of the regulariser's D (unires_plan_set_diff)
   std::vector<unires::Repeat> reps;
   // device workspace (one allocation)
   char *ws = nullptr;

@@ -231,6 +231,47 @@ extern "C" int unires_proj_apply(unires_plan_t *plan, int32_t n, int32_t op, con
   return UNIRES_OK;
 }
 
+// q (+)= c DtD_W p for a backward / central plan: the flat streaming kernel (stencil.hip), the general one where the
+// shape is outside its domain (lines shorter than 4, tiny volumes).  wr: c (1 / vx_d^2).  accumulate: q holds the data
+// term already.  Returns the number of partials written.
+static int stencil_close(unires_plan *pl, float c, const float wr[3], float a0, bool accumulate, const float *p, float *q,
+                         double *part, const int *done, hipStream_t st, const float *objb) {
+  const float h = diff_dtd_scale(pl->diff);
+  if (!launch_dtd_flat_w(pl->diff, p, q, pl->dy, a0, wr[0] * h, wr[1] * h, wr[2] * h, accumulate, part, objb, done, st))
+    return part ? dtd_flat_w_blocks(pl->dy) : 0;
+  launch_dtd(p, pl->dy, pl->vx, a0, c, q, part, objb, done, st, pl->diff, accumulate);
+  return part ? dtd_num_blocks(pl->dy) : 0;
+}
+
+// The matvec of a plan whose D is not forward's.  Every AtA runs on the kernel it runs on in a forward plan, with no
+// stencil epilogue (zero weights) and no partials; one stencil pass then adds c DtD_W p and closes the matvec with
+// the dot or the objective.  A = I is that pass alone.
+static int matvec_nonforward(unires_plan *pl, float c, const float wr[3], const float *p, float *q, double *part,
+                             const int *done, hipStream_t st, const float *objb) {
+  static const bool no_aligned = getenv("UNIRES_NO_ALIGNED") != nullptr;
+  if (pl->regime == UNIRES_REGIME_IDENTITY) {
+    float a0 = 0.f;
+    for (const Repeat &R : pl->reps) a0 += R.tau;
+    return stencil_close(pl, c, wr, a0, false, p, q, part, done, st, objb);
+  }
+  const size_t nrep = pl->reps.size();
+  bool have = false;
+  if (nrep == 1 && !no_aligned) {  // (the one-kernel forms, chosen as matvec() chooses them)
+    const Repeat &R = pl->reps[0];
+    have = (shift_fast(R.shift, pl->dy) &&
+            !launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st)) ||
+           !launch_ata_aligned(p, q, pl->dy, R.dim_gf, R.dim_x, R.Tf, make_scaling(2.f * R.scl, R.dim_thick), R.Af, R.tau,
+                               0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st) ||
+           !launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st);
+  }
+  for (size_t n = 0; !have && n < nrep; ++n) {
+    PushEpilogue ep;
+    ep.accumulate = n > 0;
+    ata_apply(pl, pl->reps[n], p, pl->reps[n].tau, ep, true, q, done, st);
+  }
+  return stencil_close(pl, c, wr, 0.f, true, p, q, part, done, st, objb);
+}
+
 int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float *q, double *part, const int *done,
                    hipStream_t st, const float *objb) {
   static const bool no_aligned = getenv("UNIRES_NO_ALIGNED") != nullptr;
@@ -242,6 +283,7 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
     const float v2 = pl->vx[d] * pl->vx[d];
     wr[d] = c * (1.f / v2), wq[d] = c / v2;
   }
+  if (pl->diff != kDiffForward) return matvec_nonforward(pl, c, wr, p, q, part, done, st, objb);
   if (pl->regime == UNIRES_REGIME_IDENTITY) {
     float a0 = 0.f;
     for (const Repeat &R : pl->reps) a0 += R.tau;
@@ -316,7 +358,7 @@ extern "C" int unires_precond_build(unires_plan_t *plan, int32_t precond_mode, f
   mark_use(plan, st);  // (before anything is enqueued: an error return below is remembered too)
   const size_t ny = plan->dy.numel();
   if (precond_mode == UNIRES_PRECOND_FFT) {
-    if (int rc = fftpre_setup(plan->fft, plan->dy))
+    if (int rc = fftpre_setup(plan->fft, plan->dy, plan->diff))
       return fail(rc == 2 ? UNIRES_ERR_ALLOC : UNIRES_ERR_HIP, "hipFFT plan / buffer creation failed");
     FftPre &F = plan->fft;
     // a = mean diagonal of the data term: mean_v sum_n tau_n (AtA_n 1)(v)
@@ -394,7 +436,7 @@ extern "C" int unires_rhs_assemble(unires_plan_t *plan, const float *const *x_pt
   hipStream_t st = (hipStream_t)stream;
   mark_use(plan, st);  // (before anything is enqueued: an error return below is remembered too)
   // b = -lam * Dt(w - rho z)   (unires/_update.py:131-133)
-  launch_div(w_c, z_c, 1.f, -rho, plan->dy, plan->vx, -lam, nullptr, b, st);
+  launch_div(w_c, z_c, 1.f, -rho, plan->dy, plan->vx, -lam, nullptr, b, st, plan->diff);
   // b += tau_n At_n x_n         (unires/_update.py:125-128)
   for (size_t n = 0; n < plan->reps.size(); ++n)
     at_accumulate(plan, plan->reps[n], x_ptrs[n], b, plan->reps[n].tau, true, st);
@@ -422,7 +464,7 @@ extern "C" int unires_rhs_from_atx(unires_plan_t *plan, const float *atx, const 
                                    const float *z_c, float rho, float lam, float *b,
                                    void *stream) {
   if (!plan || !atx || !w_c || !z_c || !b) return fail(UNIRES_ERR_NULL, "null argument");
-  launch_div(w_c, z_c, 1.f, -rho, plan->dy, plan->vx, -lam, atx, b, (hipStream_t)stream);
+  launch_div(w_c, z_c, 1.f, -rho, plan->dy, plan->vx, -lam, atx, b, (hipStream_t)stream, plan->diff);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

@@ -601,6 +601,19 @@ extern "C" int unires_plan_set_concurrency(unires_plan_t *plan, int32_t n_concur
   return UNIRES_OK;
 }
 
+// The difference of the plan's D.  A captured solve has the matvec's kernels baked in and a built preconditioner
+// the old symbol: both go, like set_repeat's.
+extern "C" int unires_plan_set_diff(unires_plan_t *plan, int32_t which) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
+  if (which == plan->diff) return UNIRES_OK;
+  await_use(plan);  // (the FFT preconditioner's eigenvalue tables are rewritten at the next build)
+  drop_cg_graph(plan);
+  plan->prec_ready = false;
+  plan->diff = which;
+  return UNIRES_OK;
+}
+
 extern "C" int64_t unires_plan_workspace_bytes(const unires_plan_t *plan) {
   return plan ? (int64_t)plan->ws_bytes : 0;
 }

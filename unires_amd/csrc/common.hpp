@@ -274,13 +274,65 @@ __device__ __forceinline__ void matvec_emit(float *__restrict__ dst, size_t idx,
   }
 }
 
+// The epilogue of the stencil pass that closes a NON-forward matvec (k_dtd_flat_w, k_dtd<DOT, W != forward, ACC>): like
+// matvec_emit, but a term of the dot is the exact product of the two float32 values (53 bits hold it), so the sum
+// returned IS the float64 dot of the vectors as stored - it does not wander by 2^-24 per term around it.  (matvec_emit's
+// float32 product is what the forward kernels were validated with bit for bit; it stays theirs.)
+__device__ __forceinline__ double dot_term(float pc, float q) { return (double)pc * (double)q; }
+__device__ __forceinline__ void matvec_emit_w(float *__restrict__ dst, size_t idx, float q, float pc,
+                                              const float *__restrict__ objb, bool want_dot, double &dot) {
+  if (objb) {
+    dot += (double)obj_term(q, objb[idx], pc);
+  } else {
+    dst[idx] = q;
+    if (want_dot) dot += dot_term(pc, q);
+  }
+}
+
+// Which difference the regulariser's D takes along every axis (nitorch diff1d / div1d `which`; UNIRES_DIFF_* of the
+// C ABI).  Zero bound throughout: samples outside the volume read as 0.  A compile-time parameter of the stencil
+// family (dtd_at, grad_at, k_grad, k_div, k_dtd, k_dtd_flat_w); a bound rule would become a second one beside it.
+//   forward : (D y)[i] = (y[i+1] - y[i]) / vx      rows of DtD: [1,-1] at 0, [-1,2,-1] inside, [-1,2] at n-1
+//   backward: (D y)[i] = (y[i] - y[i-1]) / vx      forward's, mirrored: [2,-1] at 0 ... [-1,1] at n-1
+//   central : (D y)[i] = (y[i+1] - y[i-1]) / 2 vx  DtD reaches i +- 2, nothing at i +- 1
+constexpr int kDiffForward = UNIRES_DIFF_FORWARD, kDiffBackward = UNIRES_DIFF_BACKWARD, kDiffCentral = UNIRES_DIFF_CENTRAL;
+__host__ __device__ constexpr int diff_reach(int which) { return which == kDiffCentral ? 2 : 1; }
+// factor on the per-axis stencil weights c / vx^2 and on the gradient scale 1 / vx (powers of two: exact)
+__host__ __device__ constexpr float diff_dtd_scale(int which) { return which == kDiffCentral ? 0.25f : 1.f; }
+__host__ __device__ constexpr float diff_grad_scale(int which) { return which == kDiffCentral ? 0.5f : 1.f; }
+inline bool diff_ok(int which) { return which == kDiffForward || which == kDiffBackward || which == kDiffCentral; }
+
+// One axis of DtD in difference form, tb - tf with tb = (D p)[i-1 side] and tf = (D p)[i+1 side], unscaled.  c: the
+// centre; lo / hi: the values R = diff_reach(W) voxels below / above it; l1, h1: voxel i -+ 1 exists; lr, hr: voxel
+// i -+ R exists (= l1, h1 for R = 1).
+template <int W>
+__device__ __forceinline__ float dtd_axis(float c, float lo, float hi, bool l1, bool lr, bool h1, bool hr) {
+  if (W == kDiffForward) return (l1 ? c - lo : 0.f) - ((h1 ? hi : 0.f) - c);
+  if (W == kDiffBackward) return (c - (l1 ? lo : 0.f)) - (h1 ? hi - c : 0.f);
+  return (l1 ? c - (lr ? lo : 0.f) : 0.f) - (h1 ? (hr ? hi : 0.f) - c : 0.f);
+}
+
 // (c . DtD p)[i,j,k] with per-axis weights cx,cy,cz = c/vx^2: forward differences, zero
 // bound -> rows [1,-1] at 0, [-1,2,-1] inside, [-1,2] at n-1.  Loads are unconditional
 // (clamped addresses) so the 7 of them issue together; `pc` returns the centre value.
+// W != forward: the same with backward / central differences (weights times diff_dtd_scale(W), applied by the caller).
+template <int W = kDiffForward>
 __device__ __forceinline__ float dtd_at(const float *__restrict__ p, size_t idx, int i, int j,
                                         int k, const Dim3i &d, float cx, float cy, float cz,
                                         float &pc) {
   const size_t sx = (size_t)d.y * d.z, sy = d.z;
+  if (W != kDiffForward) {
+    constexpr int R = diff_reach(W);
+    const bool hx = i + R < d.x, lx = i >= R, hy = j + R < d.y, ly = j >= R, hz = k + R < d.z, lz = k >= R;
+    const float c = p[idx];
+    const float vxp = p[hx ? idx + R * sx : idx], vxm = p[lx ? idx - R * sx : idx];
+    const float vyp = p[hy ? idx + R * sy : idx], vym = p[ly ? idx - R * sy : idx];
+    const float vzp = p[hz ? idx + R : idx], vzm = p[lz ? idx - R : idx];
+    pc = c;
+    return cx * dtd_axis<W>(c, vxm, vxp, i > 0, lx, i + 1 < d.x, hx) +
+           cy * dtd_axis<W>(c, vym, vyp, j > 0, ly, j + 1 < d.y, hy) +
+           cz * dtd_axis<W>(c, vzm, vzp, k > 0, lz, k + 1 < d.z, hz);
+  }
   const bool hx = i + 1 < d.x, lx = i > 0, hy = j + 1 < d.y, ly = j > 0, hz = k + 1 < d.z,
              lz = k > 0;
   const float c = p[idx];

@@ -24,8 +24,27 @@ __global__ void __launch_bounds__(kBlock)
   f[idx] = v;
 }
 
-int fftpre_setup(FftPre &F, Dim3i d) {
-  if (F.have_plans && F.d.x == d.x && F.d.y == d.y && F.d.z == d.z) return 0;
+// per-axis eigenvalues of the periodic Dt D: 2 - 2 cos(2 pi k / n) for forward and backward differences (the same
+// second difference), sin^2(2 pi k / n) for central ones (c_d stays c / vx_d^2: the 1 / 4 is in the symbol)
+static int fill_symbols(FftPre &F, int which) {
+  const int n[3] = {F.d.x, F.d.y, F.d.z};
+  for (int a = 0; a < 3; ++a) {
+    std::vector<float> h((size_t)n[a]);
+    for (int k = 0; k < n[a]; ++k) {
+      const double th = 2.0 * M_PI * (double)k / (double)n[a];
+      h[k] = which == kDiffCentral ? (float)(sin(th) * sin(th)) : (float)(2.0 - 2.0 * cos(th));
+    }
+    if (!F.lam[a] && hipMalloc((void **)&F.lam[a], h.size() * sizeof(float)) != hipSuccess) return 2;
+    if (hipMemcpy(F.lam[a], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      return 2;
+  }
+  F.which = which;
+  return 0;
+}
+
+int fftpre_setup(FftPre &F, Dim3i d, int which) {
+  if (F.have_plans && F.d.x == d.x && F.d.y == d.y && F.d.z == d.z)
+    return F.which == which ? 0 : fill_symbols(F, which);  // (the caller has waited for the plan's last use)
   fftpre_destroy(F);
   F.d = d;
   const int nzh = d.z / 2 + 1;
@@ -34,15 +53,7 @@ int fftpre_setup(FftPre &F, Dim3i d) {
   F.have_plans = true;
   if (hipMalloc((void **)&F.freq, (size_t)d.x * d.y * nzh * sizeof(float2)) != hipSuccess) return 2;
   if (hipMalloc((void **)&F.z, d.numel() * sizeof(float)) != hipSuccess) return 2;
-  const int n[3] = {d.x, d.y, d.z};
-  for (int a = 0; a < 3; ++a) {
-    std::vector<float> h((size_t)n[a]);
-    for (int k = 0; k < n[a]; ++k) h[k] = (float)(2.0 - 2.0 * cos(2.0 * M_PI * (double)k / (double)n[a]));
-    if (hipMalloc((void **)&F.lam[a], h.size() * sizeof(float)) != hipSuccess) return 2;
-    if (hipMemcpy(F.lam[a], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      return 2;
-  }
-  return 0;
+  return fill_symbols(F, which);
 }
 
 void fftpre_destroy(FftPre &F) {

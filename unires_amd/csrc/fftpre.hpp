@@ -18,11 +18,13 @@ struct FftPre {
   float2 *freq = nullptr;  // (X, Y, Z/2+1) complex
   float *z = nullptr;      // (X, Y, Z) preconditioned residual
   float *lam[3] = {nullptr, nullptr, nullptr};  // per-axis eigenvalues 2 - 2 cos(2 pi k / n)
+  int which = kDiffForward;  // the difference the eigenvalues are of (central: sin^2(2 pi k / n))
   float a = 0.f, c[3] = {0.f, 0.f, 0.f};
 };
 
-// Allocates plans and buffers for volumes of size d (idempotent).  Returns 0 / hipfft or hip error.
-int fftpre_setup(FftPre &F, Dim3i d);
+// Allocates plans and buffers for volumes of size d and fills the eigenvalues of `which` (idempotent; a change of
+// `which` alone rewrites the tables in place).  Returns 0 / hipfft or hip error.
+int fftpre_setup(FftPre &F, Dim3i d, int which = kDiffForward);
 void fftpre_destroy(FftPre &F);
 // out = M^-1 in (in is preserved; out may be F.z).  Returns 0 or an error code.
 int fftpre_apply(FftPre &F, const float *in, float *out, hipStream_t st);

@@ -17,10 +17,11 @@ void launch_conv_down(const float *src, Dim3i gd, const Taps &T, const Scaling &
                       Dim3i xd, const int *done, hipStream_t st);
 void launch_conv_up(const float *xs, Dim3i xd, const Taps &T, const Scaling &S, float *dst,
                     Dim3i gd, hipStream_t st);
-void launch_grad(const float *src, Dim3i d, const float vx[3], float *dst3, hipStream_t st);
+// `which`: the difference of D (kDiffForward / kDiffBackward / kDiffCentral, common.hpp), here and below
+void launch_grad(const float *src, Dim3i d, const float vx[3], float *dst3, hipStream_t st, int which = kDiffForward);
 // dst = [add +] scale * Dt(ca*ua + cb*ub)   (ub, add may be NULL)
 void launch_div(const float *ua, const float *ub, float ca, float cb, Dim3i d, const float vx[3],
-                float scale, const float *add, float *dst, hipStream_t st);
+                float scale, const float *add, float *dst, hipStream_t st, int which = kDiffForward);
 void launch_pull_grad(const float *src, Dim3i sd, const Affine &A, float *dst, Dim3i gd, float tol,
                       hipStream_t st);
 // separable (one 1-D pass per axis) forms of conv_down / conv_up for profiles with many taps;
@@ -41,7 +42,9 @@ int launch_conv_ydown_xdownup2(const float *src, Dim3i sd, const Taps &T, const 
 int dtd_num_blocks(Dim3i d);
 // dst = a*src + c*DtD(src); partials (nullable, dtd_num_blocks doubles) gets sum(src*dst) pieces;
 // with objb (needs partials): partials = sum (dst - 2 objb) * src and dst is not stored.
+// accumulate: dst += c*DtD(src) instead (a unused); the partials are then of the accumulated dst.
 void launch_dtd(const float *src, Dim3i d, const float vx[3], float a, float c, float *dst,
-                double *partials, const float *objb, const int *done, hipStream_t st);
+                double *partials, const float *objb, const int *done, hipStream_t st, int which = kDiffForward,
+                bool accumulate = false);
 
 }  // namespace unires

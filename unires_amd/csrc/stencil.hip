@@ -231,6 +231,136 @@ __global__ void __launch_bounds__(kBlock) k_dtd_flat(FlatArgs A, const int *__re
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// k_dtd_flat_w: the same streaming pass for backward and central differences (W, common.hpp), and in two forms:
+//   ACC = false   q  = a0 p + c DtD_W p     regime A = I, the whole matvec
+//   ACC = true    q += c DtD_W p            the pass that closes a non-forward matvec of the projected regimes: every
+//                                            AtA ran on its usual kernel without a stencil epilogue and left q
+// with k_dtd_flat's epilogues (float64 partials of sum p q; the objective sum (q - 2 b) p without a store) and its
+// `done` exit.  What carries over: a lane owns four consecutive voxels of the flat array, 16-byte loads at flat
+// offsets 0, -+R nz, -+R ny nz (R = 1, central: 2), aligned 16-byte stores, the z neighbours by DPP wave shifts (R
+// per side; lanes 0 and 63 load R dwords each), one contiguous chunk range per XCD.  What does not: the reach of 2
+// makes "no face inside the chunk" a rarer and longer test, so there is ONE form per vector - faces tested per voxel
+// from one position per lane, loads element-wise only where a vector sticks out of the array.  Every neighbour is
+// taken through a select on its face flag, so what a masked load returned never reaches the result.
+struct FlatVecW {
+  f4 cc, xm, xp, ym, yp, ob, qv;
+  float edge[2];  // lane 0: the voxels 1, 2 below its first; lane 63: the voxels 1, 2 above its last
+};
+
+template <int W, bool ACC, bool DOT, bool OBJ>
+__device__ __forceinline__ void flat_vec_w(const FlatArgs &A, const FlatVecW &L, unsigned lane, unsigned idx0,
+                                           unsigned k0, unsigned j0, bool valid, __amdgpu_buffer_rsrc_t rq,
+                                           double &dot) {
+  constexpr unsigned R = (unsigned)diff_reach(W);
+  const unsigned nz = A.nz, ny = A.ny, nynz = A.nynz, n = A.n;
+  const bool first = lane == 0u, last = lane == (unsigned)kWave - 1u;
+  float b1 = dpp_from_lower_lane(L.cc.w), a1 = dpp_from_upper_lane(L.cc.x), b2 = 0.f, a2 = 0.f;
+  b1 = first ? L.edge[0] : b1, a1 = last ? L.edge[0] : a1;
+  if (R == 2u) {
+    b2 = dpp_from_lower_lane(L.cc.z), a2 = dpp_from_upper_lane(L.cc.y);
+    b2 = first ? L.edge[1] : b2, a2 = last ? L.edge[1] : a2;
+  }
+  const float zs[8] = {b2, b1, L.cc.x, L.cc.y, L.cc.z, L.cc.w, a1, a2};  // voxels idx0 - 2 .. idx0 + 5
+  const float xm4[4] = {L.xm.x, L.xm.y, L.xm.z, L.xm.w}, xp4[4] = {L.xp.x, L.xp.y, L.xp.z, L.xp.w};
+  const float ym4[4] = {L.ym.x, L.ym.y, L.ym.z, L.ym.w}, yp4[4] = {L.yp.x, L.yp.y, L.yp.z, L.yp.w};
+  const float ob4[4] = {L.ob.x, L.ob.y, L.ob.z, L.ob.w}, qv4[4] = {L.qv.x, L.qv.y, L.qv.z, L.qv.w};
+  float out[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float ce = zs[e + 2];
+    // position of voxel e: a line ends at most once inside the lane's four voxels (nz >= 4)
+    const bool wrapped = k0 + (unsigned)e >= nz;
+    const unsigned ke = wrapped ? k0 + (unsigned)e - nz : k0 + (unsigned)e;
+    const unsigned je = wrapped ? (j0 + 1u == ny ? 0u : j0 + 1u) : j0;
+    const unsigned idx = idx0 + (unsigned)e;
+    const float sx = dtd_axis<W>(ce, xm4[e], xp4[e], idx >= nynz, idx >= R * nynz, idx + nynz < n, idx + R * nynz < n);
+    const float sy = dtd_axis<W>(ce, ym4[e], yp4[e], je >= 1u, je >= R, je + 1u < ny, je + R < ny);
+    const float sz = dtd_axis<W>(ce, zs[e + 2 - (int)R], zs[e + 2 + (int)R], ke >= 1u, ke >= R, ke + 1u < nz, ke + R < nz);
+    const float st = A.cx * sx + A.cy * sy + A.cz * sz;
+    const float o = ACC ? qv4[e] + st : A.a0 * ce + st;
+    out[e] = o;
+    if (valid) {
+      if (OBJ)
+        dot += (double)obj_term(o, ob4[e], ce);
+      else if (DOT)
+        dot += dot_term(ce, o);
+    }
+  }
+  if (!OBJ && valid)
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, f4{out[0], out[1], out[2], out[3]}), rq, 4u * idx0, 0, kAuxNt);
+}
+
+template <int W, bool ACC, bool DOT, bool OBJ>
+__global__ void __launch_bounds__(kBlock) k_dtd_flat_w(FlatArgs A, const int *__restrict__ done) {
+  if (done && *done) return;
+  constexpr unsigned R = (unsigned)diff_reach(W);
+  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1);
+  const unsigned n = A.n, nz = A.nz, ny = A.ny, nynz = A.nynz;
+  const __amdgpu_buffer_rsrc_t rp = make_rsrc(A.p, (size_t)n * 4);
+  const __amdgpu_buffer_rsrc_t rb = make_rsrc(OBJ ? A.objb : A.p, (size_t)n * 4);
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(A.q, (size_t)n * 4);
+  double dot = 0.0;
+  const unsigned xcd = A.nx == 8u ? blockIdx.x & 7u : 0u, slot = A.nx == 8u ? blockIdx.x >> 3 : blockIdx.x;
+  const unsigned cnt = A.per_xcd + (xcd < A.rem ? 1u : 0u);
+  const unsigned c_lo = A.cb[xcd], c_hi = A.cb[xcd + 1u];
+  for (unsigned c = c_lo + slot; c < c_hi; c += cnt) {
+    const unsigned e0 = A.head + c * (unsigned)kFlatChunk;
+    const unsigned line0 = e0 / nz, kb = e0 - line0 * nz, jb = line0 % ny;
+#pragma unroll
+    for (int v = 0; v < kFlatVecs; ++v) {
+      const unsigned t = (unsigned)v * kBlock + tid;
+      const unsigned vi = c * (unsigned)(kFlatChunk / 4) + t;
+      const bool valid = vi < A.nvec;
+      const unsigned idx0 = e0 + 4u * t, bo = 4u * idx0;
+      const unsigned u = kb + 4u * t, ql = div_small(u, nz, A.inv_nz), k0 = u - __umul24(ql, nz);
+      const unsigned lj = jb + ql, qj = div_small(lj, ny, A.inv_ny), j0 = lj - __umul24(qj, ny);
+      // all five vectors of every lane wholly inside the array?  (false in the first / last R x slabs and in the
+      // last, partial wave: those take the element-wise loads)
+      const bool inner = valid && idx0 >= R * nynz && idx0 + R * nynz + 4u <= n;
+      FlatVecW L;
+      L.ob = f4{0.f, 0.f, 0.f, 0.f}, L.qv = f4{0.f, 0.f, 0.f, 0.f};
+      if (__builtin_amdgcn_ballot_w64(!inner) == 0ull) {
+        L.cc = ld4_fast(rp, bo), L.ym = ld4_fast(rp, bo - 4u * R * nz), L.yp = ld4_fast(rp, bo + 4u * R * nz);
+        L.xm = ld4_fast(rp, bo - 4u * R * nynz), L.xp = ld4_fast(rp, bo + 4u * R * nynz);
+        if (OBJ) L.ob = ld4_fast(rb, bo);
+        if (ACC) L.qv = ld4_fast(rq, bo);
+      } else {
+        const int i0 = (int)idx0, in = (int)n, rz = (int)(R * nz), rx = (int)(R * nynz);
+        L.cc = ld4_safe(rp, i0, in), L.ym = ld4_safe(rp, i0 - rz, in), L.yp = ld4_safe(rp, i0 + rz, in);
+        L.xm = ld4_safe(rp, i0 - rx, in), L.xp = ld4_safe(rp, i0 + rx, in);
+        if (OBJ) L.ob = ld4_safe(rb, i0, in);
+        if (ACC) L.qv = ld4_safe(rq, i0, in);
+      }
+      L.edge[0] = L.edge[1] = 0.f;
+      if (lane == 0u || lane == (unsigned)kWave - 1u) {
+#pragma unroll
+        for (int r = 0; r < (int)R; ++r) {
+          const int ie = lane == 0u ? (int)idx0 - 1 - r : (int)idx0 + 4 + r;
+          L.edge[r] = buf_load(rp, (ie >= 0 && ie < (int)n) ? 4u * (unsigned)ie : 0x80000000u, 0);
+        }
+      }
+      flat_vec_w<W, ACC, DOT, OBJ>(A, L, lane, idx0, k0, j0, valid, rq, dot);
+    }
+  }
+  // the few voxels in front of the first and behind the last vector
+  if (blockIdx.x == 0) {
+    const unsigned tail0 = A.head + 4u * A.nvec, nedge = A.head + (n - tail0);
+    if (tid < nedge) {
+      const unsigned idx = tid < A.head ? tid : tail0 + (tid - A.head);
+      const unsigned line = idx / nz, k = idx - line * nz, i = line / ny, j = line - i * ny;
+      const Dim3i dd{(int)(n / nynz), (int)ny, (int)nz};
+      float pc;
+      const float st = dtd_at<W>(A.p, idx, (int)i, (int)j, (int)k, dd, A.cx, A.cy, A.cz, pc);
+      matvec_emit_w(A.q, idx, ACC ? A.q[idx] + st : A.a0 * pc + st, pc, OBJ ? A.objb : nullptr, DOT, dot);
+    }
+  }
+  if (DOT || OBJ) {
+    const double tot = block_sum(dot);
+    if (tid == 0) A.partials[blockIdx.x] = tot;
+  }
+}
+
 // x-marching form (round 4).  The five 16-byte loads per vector of k_dtd_flat are cache hits but still pass the
 // L2 -> L1 path (tools/mb_stream.hip: 16.9 us for that pattern at 181 x 217 x 181 where a copy takes 8.9).  Here a
 // lane owns four consecutive voxels of a PLANE and walks along x: the x neighbours are the previous / next
@@ -385,13 +515,12 @@ int dtd_flat_blocks(Dim3i dd) {
   return flat_grid((unsigned)((n / 4 * 4 + kFlatChunk - 1) / kFlatChunk));
 }
 
-// Non-zero return: outside the kernel's domain (tiny or huge volumes), nothing launched.
-int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
-                    double *partials, const float *objb, const int *done, hipStream_t st) {
+// The flat kernels' domain and the launch geometry that does not depend on the kernel.  false: outside the domain.
+static bool flat_args(const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz, double *partials,
+                      const float *objb, FlatArgs &A) {
   const size_t n = dd.numel();
-  if (dd.z < 4 || n >= (1ull << 29) || n < 64 || (objb && !partials)) return 1;
-  if ((size_t)dd.z + kFlatChunk >= (1u << 24) || (size_t)dd.y + kFlatChunk >= (1u << 24)) return 1;
-  FlatArgs A;
+  if (dd.z < 4 || n >= (1ull << 29) || n < 64 || (objb && !partials)) return false;
+  if ((size_t)dd.z + kFlatChunk >= (1u << 24) || (size_t)dd.y + kFlatChunk >= (1u << 24)) return false;
   A.p = p, A.q = q, A.objb = objb, A.partials = partials;
   A.n = (unsigned)n, A.nz = (unsigned)dd.z, A.ny = (unsigned)dd.y, A.nynz = (unsigned)dd.y * (unsigned)dd.z;
   A.inv_nz = 1.f / (float)dd.z, A.inv_ny = 1.f / (float)dd.y;
@@ -399,6 +528,23 @@ int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, floa
   A.nvec = (A.n - A.head) / 4u;
   A.nchunk = (A.nvec * 4u + kFlatChunk - 1u) / (unsigned)kFlatChunk;
   A.a0 = a0, A.cx = cx, A.cy = cy, A.cz = cz;
+  return true;
+}
+
+// chunk ranges of the XCDs for a grid of G workgroups
+static void flat_ranges(FlatArgs &A, unsigned G) {
+  A.nx = G >= 8u ? 8u : 1u, A.per_xcd = G / A.nx, A.rem = G % A.nx;
+  for (unsigned x = 0, before = 0; x <= A.nx; ++x) {
+    A.cb[x] = (unsigned)((unsigned long long)A.nchunk * before / G);
+    before += A.per_xcd + (x < A.rem ? 1u : 0u);
+  }
+}
+
+// Non-zero return: outside the kernel's domain (tiny or huge volumes), nothing launched.
+int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
+                    double *partials, const float *objb, const int *done, hipStream_t st) {
+  FlatArgs A;
+  if (!flat_args(p, q, dd, a0, cx, cy, cz, partials, objb, A)) return 1;
   FlatMArgs M;
   if (flat_m_geometry(dd, M)) {
     M.F = A;
@@ -414,11 +560,7 @@ int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, floa
     return 0;
   }
   const unsigned G = (unsigned)dtd_flat_blocks(dd);
-  A.nx = G >= 8u ? 8u : 1u, A.per_xcd = G / A.nx, A.rem = G % A.nx;
-  for (unsigned x = 0, before = 0; x <= A.nx; ++x) {
-    A.cb[x] = (unsigned)((unsigned long long)A.nchunk * before / G);
-    before += A.per_xcd + (x < A.rem ? 1u : 0u);
-  }
+  flat_ranges(A, G);
   // the number of partials must not depend on q's alignment: callers size their reduction with
   // dtd_flat_blocks(dd)
   const dim3 grid(G), block(kBlock);
@@ -428,6 +570,39 @@ int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, floa
     hipLaunchKernelGGL((k_dtd_flat<true, false>), grid, block, 0, st, A, done);
   else
     hipLaunchKernelGGL((k_dtd_flat<false, false>), grid, block, 0, st, A, done);
+  return 0;
+}
+
+int dtd_flat_w_blocks(Dim3i dd) {
+  const size_t n = dd.numel();
+  return flat_grid((unsigned)((n / 4 * 4 + kFlatChunk - 1) / kFlatChunk));
+}
+
+template <int W, bool ACC>
+static void launch_flat_w(const FlatArgs &A, unsigned G, const int *done, hipStream_t st) {
+  const dim3 grid(G), block(kBlock);
+  if (A.objb)
+    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, true, true>), grid, block, 0, st, A, done);
+  else if (A.partials)
+    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, true, false>), grid, block, 0, st, A, done);
+  else
+    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, false, false>), grid, block, 0, st, A, done);
+}
+
+int launch_dtd_flat_w(int which, const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
+                      bool accumulate, double *partials, const float *objb, const int *done, hipStream_t st) {
+  if (which != kDiffBackward && which != kDiffCentral) return 1;
+  FlatArgs A;
+  if (!flat_args(p, q, dd, a0, cx, cy, cz, partials, objb, A)) return 1;
+  const unsigned G = (unsigned)dtd_flat_w_blocks(dd);
+  flat_ranges(A, G);
+  if (which == kDiffBackward) {
+    if (accumulate) launch_flat_w<kDiffBackward, true>(A, G, done, st);
+    else launch_flat_w<kDiffBackward, false>(A, G, done, st);
+  } else {
+    if (accumulate) launch_flat_w<kDiffCentral, true>(A, G, done, st);
+    else launch_flat_w<kDiffCentral, false>(A, G, done, st);
+  }
   return 0;
 }
 

@@ -222,13 +222,15 @@ def grid_push(input, mat, shape, interpolation='linear', bound='zero', extrapola
 
 
 def im_gradient(dat, vx=None, which='forward', bound='zero'):
-    _only_forward_zero(which, bound)
-    return _ops.grad_fwd_zero(dat, vx)
+    """nitorch im_gradient, zero bound: ``which`` = 'forward' | 'backward' | 'central'  (diff1d  [recalled])."""
+    _only_zero_bound(which, bound)
+    return _ops.grad(dat, vx, which)
 
 
 def im_divergence(dat, vx=None, which='forward', bound='zero'):
-    _only_forward_zero(which, bound)
-    return _ops.div_fwd_zero(dat, vx)
+    """nitorch im_divergence: the positive transpose of :func:`im_gradient` (div1d  [recalled])."""
+    _only_zero_bound(which, bound)
+    return _ops.div(dat, vx, which)
 
 
 def _is_nearest(interpolation):
@@ -242,7 +244,9 @@ def _only_linear_zero(interpolation, bound, extrapolate):
                                   '(unires/struct.py:64,85; unires/_project.py:162,181)')
 
 
-def _only_forward_zero(which, bound):
-    if which != 'forward' or bound != 'zero':
-        raise NotImplementedError("unires_amd builds the reference defaults only: "
-                                  "diff='forward', bound='zero' (unires/struct.py:64,74)")
+def _only_zero_bound(which, bound):
+    from ._lib import diff_code
+    diff_code(which, 'which')  # ValueError for a name that is none of the three
+    if bound != 'zero':
+        raise NotImplementedError("unires_amd builds the reference default only: "
+                                  "bound='zero' (unires/struct.py:64)")
