@@ -56,6 +56,10 @@ c_M(A)      = C_TAP + C_SCALE + C_PULL + C_STORE + N_TAPS
 c_M(At)     = C_TAP + C_SCALE + C_STORE + N_TAPS + C_PUSH
 c_M(AtA)    = c_M(A) + c_M(At)           (the forward error, carried by |A|^T, plus the push's own)
 c_M(matvec) = c_M(AtA) + C_DTD
+
+sett.diff = 'backward' / 'central': ``bound_matvec(..., which)`` takes D^T D and |D|^T |D| from tests/diff64.py with the
+same constants (the count is in its docstring); ``bound_matvec_reps`` is the same bound over several repeats (+ 1
+per accumulating store) and ``bound_rhs`` the bound of b = sum tau A^T x - lam D^T (w - rho z).
 """
 import math
 
@@ -330,8 +334,19 @@ class Operator64:
         ref, M, G, D = self.parts_AtA(p)
         return ref, (U + U64) * self.c_AtA * M + G + D
 
-    def bound_matvec(self, p, tau, rho, lam, vx):
-        """q = tau A^T A p + rho lam^2 D^T D p with the float32 tau, rho, lam, vx the kernels see, upcast."""
+    def bound_matvec(self, p, tau, rho, lam, vx, which='forward'):
+        """q = tau A^T A p + rho lam^2 D^T D p with the float32 tau, rho, lam, vx the kernels see, upcast.
+
+        ``which`` = 'backward' / 'central' (sett.diff): D^T D from tests/diff64.py, Md = c |D|^T |D| |p| with the same
+        difference, and the same form of bound, (u + 2^-53) (c_AtA + C_DTD) (tau M + Md) + tau (G + D).  The count
+        carries over: a non-forward plan runs A^T A on its usual kernel without a stencil epilogue - that chain,
+        c_AtA, already ends in the float32 store of tau A^T A p - and a second pass loads the stored value where a
+        forward epilogue forms a0 p, and adds c D^T D p to it once: the load is exact, and the add is the "final add"
+        of C_DTD, which also counts a product (a x p) that this pass does not form.  The stencil's own chain (c, 1 /
+        vx^2, their product, the six differences and the seven-term sum) is forward's term for term: central's 1/4 is
+        a power of two.  See ``bound_matvec_reps`` (this is its one-repeat case)."""
+        if which != 'forward':
+            return bound_matvec_reps([self], [tau], p, rho, lam, vx, which)
         tau, rho, lam = (float(torch.tensor(float(v), dtype=torch.float32)) for v in (tau, rho, lam))
         vx = torch.as_tensor(vx, dtype=torch.float32).double()
         ref, M, G, D = self.parts_AtA(p)
@@ -357,6 +372,82 @@ class Operator64:
         gx = F.conv_transpose3d(mx.double()[None, None], ones, stride=self.ratio)[0, 0]
         myy = my | reach_push(gx, self.grid, self.dim_y, self.eta)
         return mx, my, myy, int(near.sum())
+
+
+def _f32(v):
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def bound_matvec_reps(ops, taus, p, rho, lam, vx, which='forward', parts=None):
+    """(ref, tol) of q = sum_n tau_n A_n^T A_n p + rho lam^2 D^T D p over the repeats ``ops`` of one channel, D taking
+    the difference ``which`` (tests/diff64.py).
+
+        tol = (u + 2^-53) (c_AtA + C_DTD + nrep - 1) (sum_n tau_n M_n + Md) + sum_n tau_n (G_n + D_n)
+
+    ``Operator64.bound_matvec``'s form with M, G and D summed over the repeats with their tau, and c_AtA the longest of
+    the repeats' chains.  The stencil goes in once (a forward plan adds it in the first repeat's epilogue, a
+    non-forward one in the closing pass), so Md = c |D|^T |D| |p| appears once.  Every repeat after the first adds its
+    term to the stored q: one more rounding of the running sum per accumulating store, nrep - 1 in all.  With one
+    repeat this is ``Operator64.bound_matvec``'s bound.  Voxels to leave out: the union of the repeats' ``myy``
+    (``tie_masks``).
+    ``parts``: the repeats' ``parts_AtA(p)`` where the caller has them already (they do not depend on ``which``)."""
+    from tests import diff64
+    rho, lam = _f32(rho), _f32(lam)
+    taus = [_f32(t) for t in taus]
+    vx = [float(v) for v in torch.as_tensor(vx, dtype=torch.float32).double()]
+    if parts is None:
+        parts = [op.parts_AtA(p) for op in ops]
+    c_m = max(op.c_AtA for op in ops) + C_DTD + len(ops) - 1
+    c = rho * lam * lam
+    p64 = p.double().numpy()
+    ref = c * torch.from_numpy(diff64.dtd(p64, vx, which))
+    mag = c * torch.from_numpy(diff64.dtd_abs(p64, vx, which))  # Md, then + sum tau M
+    rest = torch.zeros_like(mag)
+    for tau, (r, M, G, D) in zip(taus, parts):
+        ref = ref + tau * r
+        mag = mag + tau * M
+        rest = rest + tau * G + tau * D
+    return ref, (U + U64) * c_m * mag + rest
+
+
+C_RHS = 3  # on top of diff64.C_DIV: the product rho z, the subtraction w - rho z, the product with lam
+
+
+def bound_rhs(ops, taus, x_list, w, z, rho, lam, vx, which='forward', at=None):
+    """(ref, tol) of b = sum_n tau_n A_n^T x_n - lam D^T (w - rho z) (unires_rhs_assemble), D^T the transpose of the
+    difference ``which``; w, z: (3, *dim_y).  An entry None of ``ops`` is A = I.
+
+    The chain, counted: g = w - rho z costs a product and a subtraction (2 u on |w| + rho |z|); the divergence of g
+    is diff64's chain (C_DIV = 5 on |D|^T (|w| + rho |z|)); the product with lam 1 more; then every repeat adds
+    tau_n A_n^T x_n to the stored b, nrep roundings of the running sum:
+
+        tol = (u + 2^-53) (C_DIV + 3 + nrep) lam |D|^T (|w| + rho |z|)
+              + sum_n tau_n tol_n + (u + 2^-53) (1 + nrep) tau_n (|ref_n| + tol_n)
+
+    with (ref_n, tol_n) = ``Operator64.bound_At(x_n)``: the push's own chain, then the product with tau_n (1) and at
+    most nrep accumulating adds, on the magnitude of the value those act on, at most |ref_n| + tol_n.  Voxels to
+    leave out: the union of the repeats' ``my`` (``tie_masks``).
+    ``at``: the repeats' (ref_n, tol_n) where the caller has them already (they do not depend on ``which``)."""
+    from tests import diff64
+    rho, lam = _f32(rho), _f32(lam)
+    taus = [_f32(t) for t in taus]
+    vx = [float(v) for v in torch.as_tensor(vx, dtype=torch.float32).double()]
+    nrep = len(ops)
+    if at is None:
+        at = [(x.double(), torch.zeros(tuple(x.shape), dtype=torch.float64)) if op is None else op.bound_At(x)
+              for op, x in zip(ops, x_list)]
+    w64, z64 = w.double().numpy(), z.double().numpy()
+    s = diff64.inv_vx(vx)
+    g = w64 - rho * z64
+    ga = abs(w64) + rho * abs(z64)
+    div = sum(diff64._apply(g[d], d, which, True, False) * s[d] for d in range(3))
+    mag = sum(diff64._apply(ga[d], d, which, True, True) * s[d] for d in range(3))
+    ref = -lam * torch.from_numpy(div)
+    tol = (U + U64) * (diff64.C_DIV + C_RHS + nrep) * lam * torch.from_numpy(mag)
+    for tau, (r, t) in zip(taus, at):
+        ref = ref + tau * r
+        tol = tol + tau * t + (U + U64) * (1 + nrep) * tau * (r.abs() + t)
+    return ref, tol
 
 
 def dtd_abs(pa, vx):

@@ -35,6 +35,8 @@ repeat_info can show it, and relies on the switch otherwise:
 | int_shift          | 41x38x61, thick 6 along z, shift (2, -1, 3)     |                    | k_ata_aligned* (matvec; the shift   |
 |                    |                                                 |                    | kernel declines: z not 4k)          |
 | int_shift_noalign  | the same                                        | UNIRES_NO_ALIGNED=1| two-kernel matvec                   |
+| int_shift_z60      | 41x38x60, thick 6 along z, shift (2, -1, 3)     |                    | k_ata_aligned*, 16-byte form (z 4k; |
+|                    |                                                 |                    | the shift tables exist too)         |
 | identity           | 37x41x53 (not a multiple of the 2048 chunk)     |                    | k_dtd_flat (regime id)              |
 | identity_noflat    | the same                                        | UNIRES_NO_FLAT=1   | the line stencil kernel             |
 | orient_9 / _22     | 41x38x61, thick 4, stored as SIGNED_PERMS 9/22  |                    | canonicalised, pull2 + splat2       |
@@ -70,12 +72,50 @@ Observed on an MI355X (largest err / tol over every check of the case; voxels ex
 / 300, z_thick_conc3 0.350 / 300, x_thick 0.288 / 0, y_thick 0.296 / 0, iso2_rect 0.394 / 0, iso2_rect_z4 0.335 / 0,
 iso2_rect_nohyb 0.394 / 0, iso2_gauss 1.000 / 0 (voxels only the dropped taps reach: the kernel returns 0, err = D),
 denoise 0.400 / 0, denoise_noata1 0.400 / 0, translate 0.038 / 0, translate_noshift 0.035 / 0, int_shift 0.025 / 0,
-int_shift_noalign 0.025 / 0, identity 0.151 / 0, identity_noflat 0.156 / 0, orient_9 0.141 / 0, orient_22 0.158 / 0,
+int_shift_noalign 0.025 / 0, int_shift_z60 0.030 / 0, identity 0.151 / 0, identity_noflat 0.156 / 0, orient_9 0.141
+/ 0, orient_22 0.158 / 0,
 z_nosplat2, z_pushtile, z_nopull2 0.257 / 0, dn_nopull2 0.400 / 0, ctab_1266 0.403 / 2144, ctab_1272 0.229 / 3187,
 rowcode_724 0.284 / 22442 (of 6.3M), rowcode_725 0.271 / 24686, ax0_gdy511 0.237 / 662, ax0_gdy512 0.247 / 602,
 ax1_gdy509 0.237 / 386, ax1_gdy513 0.374 / 657, the sweep 0.111 - 0.376 / 0; the 256^3 matvec 0.156 / 3302.  The
 most instructions in one tile: 23 - 26 below 0.3 rad, 33 - 48 in the two-pass sweep cases.  No case failed: the
 suite found no kernel bug.
+
+The table with a non-forward D (``DIFF_CASES``, ``test_every_form_per_voxel_with_backward_and_central_differences``).
+A plan with sett.diff = 'backward' / 'central' composes its matvec differently (api_operator.hip matvec_nonforward):
+every AtA kernel runs without its stencil epilogue, and one pass - k_dtd_flat_w<W, ACC>, or k_dtd<W, ACC> where the
+flat kernel declines the shape - adds c DtD_W p to the stored q and closes the matvec with the dot or the objective.
+One child per case sets each difference in turn on the same plan and writes q with its float64 dot, the right-hand
+side b (k_div<W>, then the accumulating A^T of every repeat) and the objectives of two one-iteration solves from
+x0 = p; the parent checks q per voxel against ref64.bound_matvec_reps, the dot against the float64 dot of the stored
+vectors, b per voxel against ref64.bound_rhs, and the objectives (``_check_diff``).  The cases are the forms above by
+name (z_thick and z_thick_conc3 at 41x38x61; no table limits, no sweep: those exercise the schedule) and:
+
+| case               | geometry                                        | what it is there for                                |
+|--------------------|-------------------------------------------------|-----------------------------------------------------|
+| z_aniso, dn_aniso  | z_thick's / denoise's, voxels 0.8x1.25x2.0 mm   | cx != cy != cz in the closing pass                  |
+| sr_2rep            | 41x38x61, thick 4, two repeats (thick z, y)     | accumulating stores, the stencil added once         |
+| dn_2rep            | 21x19x33, denoising, two repeats                | the same on k_ata1                                  |
+| dn_under64         | 3x2x5 (30 voxels)                               | k_dtd<W, ACC>: fewer than 64 voxels                 |
+| dn_nz3             | 12x10x3                                         | k_dtd<W, ACC>: lines shorter than 4                 |
+| translate_z256,    | 12x10x256 fractional shift, 10x12x256 shift     | the shift kernel's fast form (256-voxel lines       |
+| int_shift_z256     | (2, -1, 3); thick 6 along z                     | only), tried first by a one-repeat plan             |
+| z_unaligned,       | z_thick's / denoise's, out= a view 1, 2, 3      | head, the per-voxel tail and ld4_safe(rq) of the    |
+| dn_unaligned       | floats into a sentinel-padded buffer            | ACC pass; pads unchanged, every voxel written       |
+
+int_shift_z60 does not reach the shift kernel's fast form (shift_fast wants 256-voxel lines): at z = 60 an integer
+shift runs aligned.hip's 16-byte form; the two z256 cases are there for that branch.
+
+Observed on an MI355X (err / tol, backward / central; no voxel excluded in any case): the matvec q 0.047 / 0.091
+(z_thick, z_thick_conc3, z_nosplat2, z_pushtile, z_nopull2, z_unaligned at all three offsets), 0.084 / 0.108 (x_thick),
+0.066 / 0.129 (y_thick), 0.039 / 0.074 (iso2_rect), 0.039 / 0.065 (iso2_rect_nohyb), 0.014 / 0.025 (iso2_gauss),
+0.170 / 0.258 (denoise, denoise_noata1, dn_nopull2, dn_unaligned), 0.038 / 0.033 (translate), 0.037 / 0.033
+(translate_noshift), 0.024 / 0.025 (int_shift, int_shift_noalign), 0.029 / 0.029 (int_shift_z60), 0.114 / 0.123
+(identity), 0.040 / 0.073 (orient_9), 0.083 / 0.089 (z_aniso), 0.094 / 0.134 (dn_aniso), 0.104 / 0.223 (sr_2rep),
+0.119 / 0.176 (dn_2rep), 0.009 / 0.010 (dn_under64), 0.045 / 0.079 (dn_nz3), 0.031 / 0.024
+(translate_z256), 0.024 / 0.024 (int_shift_z256); the right-hand side b 0.014 - 0.563
+(largest: iso2_gauss 0.530 / 0.563, identity 0.454 / 0.478, z_aniso 0.406 / 0.409); the objectives at most 0.022 of
+their bound (dn_under64, central; 0.005 and below elsewhere); every dot inside the float64 summation's slack.  No
+case failed: the table found no kernel bug.
 """
 import json
 import os
@@ -90,10 +130,12 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = (8, 4, 30)
+SENT = -7.75e37  # sentinel of the pads around an unaligned output
+NONFWD = ('backward', 'central')
 
 
-def _c(kw, env=None, conc=1, expect=None, light=False):
-    return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light)
+def _c(kw, env=None, conc=1, expect=None, light=False, seed=11, unaligned=False):
+    return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light, seed=seed, unaligned=unaligned)
 
 
 _Z = dict(dim_y=(41, 38, 61), thick=6, thick_axes=[2], rot=0.1, trans=2.0, scl=0.1)
@@ -124,6 +166,9 @@ CASES = {
     'int_shift': _c(dict(_Z, shift=(2.0, -1.0, 3.0)), expect=lambda i: not i['shift'] and i['splat2_axis'] == 2),
     'int_shift_noalign': _c(dict(_Z, shift=(2.0, -1.0, 3.0)), {'UNIRES_NO_ALIGNED': '1'},
                             expect=lambda i: not i['shift']),
+    # (z a multiple of 4: the shift kernel's tables are built for the integer shift too, and the 16-byte aligned forms
+    # of the one-kernel matvecs are open to it)
+    'int_shift_z60': _c(dict(_Z, dim_y=(41, 38, 60), shift=(2.0, -1.0, 3.0)), expect=lambda i: i['shift']),
     'identity': _c(dict(dim_y=(37, 41, 53), regime='id'), expect=lambda i: i['regime'] == 'identity'),
     'identity_noflat': _c(dict(dim_y=(37, 41, 53), regime='id'), {'UNIRES_NO_FLAT': '1'},
                           expect=lambda i: i['regime'] == 'identity'),
@@ -180,6 +225,42 @@ for _n in CASES:
     if not _n.startswith('sweep_'):
         CASES[_n]['one_pass'] = True
 
+# The table with a non-forward D (sett.diff = 'backward' / 'central'): the smallest shapes that still select each form
+# the matvec of such a plan chooses between (api_operator.hip, matvec_nonforward), by name from the table above where
+# it has them, and the shapes where the closing stencil pass turns: anisotropic voxels (cx != cy != cz), two repeats
+# (the accumulating stores), the k_dtd fallback of the flat kernel (fewer than 64 voxels; nz < 4) and an output 4, 8
+# and 12 bytes off a 16-byte boundary.  No conv-table / row-code / grid limits and no sweep: those exercise the
+# schedule, not the epilogue.
+_ANISO = (0.8, 1.25, 2.0)
+_z_form = lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable']
+DIFF_CASES = {
+    'z_thick': _c(_Z, expect=_z_form),
+    'z_thick_conc3': _c(_Z, conc=3, expect=_z_form),
+}
+for _n in ('x_thick', 'y_thick', 'iso2_rect', 'iso2_rect_nohyb', 'iso2_gauss', 'denoise', 'denoise_noata1',
+           'translate', 'translate_noshift', 'int_shift', 'int_shift_noalign', 'int_shift_z60', 'identity', 'orient_9',
+           'z_nosplat2', 'z_pushtile', 'z_nopull2', 'dn_nopull2'):
+    DIFF_CASES[_n] = CASES[_n]
+DIFF_CASES.update({
+    'z_aniso': _c(dict(_Z, aniso=_ANISO), expect=_z_form),
+    'dn_aniso': _c(dict(_DN, aniso=_ANISO), expect=lambda i: i['fused']),
+    'sr_2rep': _c(dict(dim_y=(41, 38, 61), thick=4, n_repeats=2, rot=0.1, trans=2.0, scl=0.1),
+                  expect=lambda i: i['pull2'] and i['splat2_axis'] is not None),
+    'dn_2rep': _c(dict(dim_y=(21, 19, 33), regime='dn', n_repeats=2, rot=0.1, trans=2.0)),
+    # (tests/test_gpu_ata1.py's dn_thin: 30 voxels, below the flat kernel's 64: k_dtd<ACC> closes the matvec)
+    'dn_under64': _c(dict(dim_y=(3, 2, 5), regime='dn', rot=0.05, trans=0.3), seed=5),
+    'dn_nz3': _c(dict(dim_y=(12, 10, 3), regime='dn', rot=0.1, trans=1.0)),  # (nz < 4: the same fallback)
+    # 256-voxel lines: the x-marching shift kernel's fast form (shift.hip shift_fast: only there), which a one-repeat
+    # plan tries first - a fractional and an integer shift (tests/test_gpu_path.py's sr_shift_z256 / sr_aligned_z256
+    # geometries).  repeat_info shows that the shift tables exist, not which form of the kernel runs.
+    'translate_z256': _c(dict(dim_y=(12, 10, 256), thick=6, thick_axes=[2], rot=0.0, trans=2.3, scl=0.1),
+                         expect=lambda i: i['shift']),
+    'int_shift_z256': _c(dict(dim_y=(10, 12, 256), thick=6, thick_axes=[2], shift=(2.0, -1.0, 3.0), scl=0.05),
+                         expect=lambda i: i['shift']),
+    'z_unaligned': _c(_Z, expect=_z_form, unaligned=True),
+    'dn_unaligned': _c(_DN, expect=lambda i: i['fused'], unaligned=True),
+})
+
 _CHILD = r'''
 import json, sys
 import numpy as np, torch
@@ -189,9 +270,10 @@ from tests.test_gpu_voxelwise import comb, inputs, spacings
 from oracle import nitorch_restated as N
 from unires_amd._project import _channel_plan
 kw, conc, light, out = %(kw)r, %(conc)r, %(light)r, sys.argv[1]
+seed, diffs, unaligned = %(seed)r, %(diffs)r, %(unaligned)r
 if 'orient' in kw:
     kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
-prob = make_problem(seed=11, **kw)
+prob = make_problem(seed=seed, **kw)
 xg, yg, sett = gpu_structs(prob, 'cuda:0')
 vx = N.voxel_size(prob['mat_y']).float()
 plan = _channel_plan(xg[0], yg[0], prob['method'], prob['do_proj'], vx)
@@ -201,7 +283,7 @@ info['regime'] = 'identity' if not prob['do_proj'] else prob['method']
 p, v = inputs(prob['dim_y'], plan.dims_x[0])
 res = dict(info=json.dumps(info))
 d = lambda t: t.to('cuda:0')
-if prob['do_proj']:
+if prob['do_proj'] and 'forward' in diffs:
     sy, sx = spacings(kw)
     res['Ap'] = plan.proj_apply(0, 'A', d(p)).cpu().numpy()
     res['AtAp'] = plan.proj_apply(0, 'AtA', d(p)).cpu().numpy()
@@ -214,12 +296,47 @@ if prob['do_proj']:
             res['A_comb%%d' %% ph] = plan.proj_apply(0, 'A', d(pc)).cpu().numpy()
             vc = comb(plan.dims_x[0], None, sx, ph)
             res['At_comb%%d' %% ph] = plan.proj_apply(0, 'At', d(vc)).cpu().numpy()
-dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
-res['q'] = plan.matvec(d(p), prob['rho'], yg[0].lam, dot=dot).cpu().numpy()
-torch.cuda.synchronize()
-res['dot'] = np.array(dot.item())
+rho, lam, n = prob['rho'], yg[0].lam, p.numel()
+if 'forward' in diffs:
+    dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
+    res['q'] = plan.matvec(d(p), rho, lam, dot=dot).cpu().numpy()
+    torch.cuda.synchronize()
+    res['dot'] = np.array(dot.item())
+for which in diffs:
+    if which == 'forward':
+        continue
+    plan.set_diff(which)
+    # out=: a view 1, 2, 3 floats into a sentinel-padded buffer (q 4, 8, 12 bytes off a 16-byte boundary), else None
+    for off in ((1, 2, 3) if unaligned else (0,)):
+        tag = '%%s_off%%d' %% (which, off) if unaligned else which
+        dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
+        buf = torch.full((n + 8,), SENT, dtype=torch.float32, device='cuda:0')
+        view = buf[off:off + n].view(prob['dim_y'])
+        q = plan.matvec(d(p), rho, lam, out=view if unaligned else None, dot=dot)
+        torch.cuda.synchronize()
+        res['q_' + tag] = q.cpu().numpy()
+        res['dot_' + tag] = np.array(dot.item())
+        if unaligned:
+            res['pads_' + tag] = np.array(bool((buf[:off] == SENT).all()) and bool((buf[off + n:] == SENT).all()))
+    b = plan.rhs([xn.dat for xn in xg[0]], d(prob['w'][0]), d(prob['z'][0]), rho, lam)
+    res['b_' + which] = b.cpu().numpy()
+    if prob['do_proj']:
+        # a 'max_gain' solve of one iteration from x0 = p: trace[0] is the objective at p.  'max_gain' takes iteration
+        # 1's objective from the recurred residual (unires_amd/_lib.py STOP); 'max_gain_fresh' evaluates it by the
+        # matvec's objective epilogue, on the iterate the solve leaves in x: trace[1] of a second such solve
+        x = d(p).clone()
+        it, trace = plan.cg(b, x, rho, lam, max_iter=1, tolerance=1e-3, stop='max_gain')
+        torch.cuda.synchronize()
+        res['obj0_' + which] = np.array(trace[0])
+        x = d(p).clone()
+        it, trace = plan.cg(b, x, rho, lam, max_iter=1, tolerance=1e-3, stop='max_gain_fresh')
+        torch.cuda.synchronize()
+        if it >= 1:
+            res['obj1_' + which] = np.array(trace[1])
+            res['x1_' + which] = x.cpu().numpy()
+            res['q1_' + which] = plan.matvec(x, rho, lam).cpu().numpy()  # (stored: for the error in tied voxels)
 np.savez(out, **res)
-'''.replace('TILE_Y', repr(TILE))
+'''.replace('TILE_Y', repr(TILE)).replace('SENT', repr(SENT))
 
 
 def inputs(dim_y, dim_x):
@@ -266,14 +383,17 @@ def comb(dim, tile, spacing, phase):
     return out
 
 
-def _run_child(tmp_path, name, case):
+def _run_child(tmp_path, name, case, diffs=('forward',), timeout=300):
+    """One child process for the case; ``diffs``: the differences whose matvec it runs (non-forward ones also the
+    right-hand side and a one-iteration solve)."""
     path = str(tmp_path / ('%s.npz' % name))
     env = dict(os.environ)
     env.update(case['env'])
     env['UNIRES_SPLAT2_VERBOSE'] = '1'
     r = subprocess.run([sys.executable, '-c', _CHILD % dict(root=ROOT, kw=case['kw'], conc=case['conc'],
-                                                            light=case['light']), path],
-                       env=env, capture_output=True, text=True, timeout=300)
+                                                            light=case['light'], seed=case['seed'],
+                                                            diffs=tuple(diffs), unaligned=case['unaligned']), path],
+                       env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])
     res = dict(np.load(path))
     builds = re.findall(r'\[splat2\].*build (\S+), max instructions per tile (\d+)', r.stderr)
@@ -288,7 +408,7 @@ def _check(name, case, res):
     kw = case['kw']
     if 'orient' in kw:
         kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
-    prob = make_problem(seed=11, **kw)
+    prob = make_problem(seed=case['seed'], **kw)
     xs, ys = oracle_structs(prob)
     xc, yc = xs[0], ys[0]
     info = json.loads(str(res['info']))
@@ -382,6 +502,158 @@ def test_every_form_per_voxel_against_float64(tmp_path):
         print('%-20s %s build %s max err/tol %.3f excluded %d R %.0f'
               % (name, info, build, max(rep.values()), excluded, R), flush=True)
     assert not drift, drift
+
+
+def diff_reference(case):
+    """The float64 side of a case of DIFF_CASES, everything that does not depend on the difference: the problem, one
+    Operator64 per repeat (None with A = I), the unions of the repeats' tie masks (``my`` for the right-hand side,
+    ``myy`` for the matvec), the inputs, and the repeats' A^T A parts of p and A^T bounds of their observations."""
+    from oracle import nitorch_restated as N
+    from oracle import unires_restated as O
+    from tests import ref64
+    from tests.helpers import SIGNED_PERMS, make_problem, oracle_structs
+    kw = case['kw']
+    if 'orient' in kw:
+        kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
+    prob = make_problem(seed=case['seed'], **kw)
+    xs, ys = oracle_structs(prob)
+    xc, yc = xs[0], ys[0]
+    R = dict(prob=prob, xc=xc, yc=yc, vx=N.voxel_size(prob['mat_y']).float(), taus=[xn.tau for xn in xc],
+             rho=torch.tensor(prob['rho'], dtype=torch.float32))
+    R['p'] = inputs(prob['dim_y'], prob['dim_y'])[0]
+    n = R['p'].numel()
+    R['my'] = torch.zeros(prob['dim_y'], dtype=torch.bool)
+    R['myy'] = R['my'].clone()
+    if not prob['do_proj']:
+        R['ops'] = [None] * len(xc)
+        return R
+    R['ops'], R['orient'] = [], []
+    for xn in xc:
+        mat, _ = O.proj_matrix(xn.po, prob['method'])
+        perm, flip, oriented = ref64.orientation_of(mat.float().double())
+        op = ref64.Operator64(xn.po, prob['method'], oriented=oriented)
+        _, my, myy, _ = op.tie_masks(xn.po)
+        R['ops'].append(op)
+        R['orient'].append((perm, flip))
+        R['my'] |= my
+        R['myy'] |= myy
+    return R
+
+
+def tie_cap_ok(R):
+    """The cap on excluded voxels: fewer than 1 % of the volume (none in a volume below 100 voxels)."""
+    n = R['p'].numel()
+    return int(R['myy'].sum()) < 0.01 * n and int(R['my'].sum()) < 0.01 * n
+
+
+def _check_diff(name, case, res, R):
+    """Matvec, dot, right-hand side and the objectives of one-iteration solves, for both non-forward differences of
+    one case.
+
+    The objective (cg.hip): entry k of the trace is 0.5 sum_v obj_term(q_v, b_v, x_v) over the iterate x of iteration
+    k, q = A(x) the plan's matvec of it, with obj_term = fl(fl(q - fl(2 b)) x): three float32 operations, of which the
+    doubling is exact; each of the other two is off by at most u times its result, at most u (|q| + 2 |b|) |x|; the
+    bound below counts all three.  Entry 0 (obj0, of a 'max_gain' solve) is formed by k_residual_init from the q the
+    start's matvec stored (the closing pass in its ACC form without an epilogue).  Entry 1 of a 'max_gain' solve is
+    taken from the recurred residual, not from a matvec; obj1 is entry 1 of a 'max_gain_fresh' solve, formed by the
+    objective epilogue of the closing pass (ACC and OBJ: the data term read from q, nothing stored), on the iterate
+    x1 that solve leaves in x.  So for x = p
+    (entry 0) and x = x1 (entry 1), with (refq, tolq) the float64 matvec of the stored x and b the stored
+    right-hand side:
+
+        |obj - 0.5 sum (refq - 2 b) x| <= 0.5 sum |x| (tolq + 3 u (|refq| + 2 |b|)) + 0.5 sum_ties |x| |q - refq|
+
+    where the last term is the actual error of the kernel's q in tied voxels (entry 1: of the q a stored matvec of x1
+    returns - the same kernels on the same coordinates, so the same FOV decisions)."""
+    from tests import diff64, ref64
+    prob, ops, taus, rho, lam, vx = R['prob'], R['ops'], R['taus'], R['rho'], R['yc'].lam, R['vx']
+    p, my, myy = R['p'], R['my'], R['myy']
+    p64 = p.double()
+    proj = prob['do_proj']
+    assert tie_cap_ok(R), (name, int(myy.sum()), int(my.sum()))
+    if proj and 'parts' not in R:
+        R['parts'] = [op.parts_AtA(p) for op in ops]
+        R['at'] = [op.bound_At(xn.dat) for op, xn in zip(ops, R['xc'])]
+    offs = (1, 2, 3) if case['unaligned'] else (0,)
+    rep, qs = {}, {}
+    for which in NONFWD:
+        if proj:
+            refq, tolq = ref64.bound_matvec_reps(ops, taus, p, rho, lam, vx, which, parts=R['parts'])
+        else:  # A = I: q = (sum tau) p + rho lam^2 DtD p, tests/diff64.py's bound for it
+            a0 = np.float32(0.0)
+            for t in taus:
+                a0 = a0 + np.float32(float(t))
+            c = np.float32(float(rho)) * (np.float32(float(lam)) * np.float32(float(lam)))
+            refq, tolq = (torch.from_numpy(a) for a in diff64.a_plus_c_dtd(p.numpy(), vx.tolist(), which, a0, c))
+        for off in offs:
+            tag = '%s_off%d' % (which, off) if case['unaligned'] else which
+            q = torch.from_numpy(res['q_' + tag])
+            r = ref64.compare(q, refq, tolq, myy)
+            assert r['ok'], (name, 'matvec', tag, r)  # (a voxel left at the sentinel is off by 7.75e37)
+            assert torch.isfinite(q).all() and float(q.abs().max()) < 1e30, (name, 'unwritten voxel', tag)
+            rep['q ' + tag] = r['max_ratio']
+            if case['unaligned']:
+                assert bool(res['pads_' + tag]), (name, 'pads', tag)
+            # the dot's terms are exact products of the stored float32 values: the float64 dot of p and q as stored,
+            # within the float64 summation's own slack
+            want = float((p64 * q.double()).sum())
+            slack = (p.numel() + 32) * 2.0 ** -53 * float((p64 * q.double()).abs().sum())
+            assert abs(float(res['dot_' + tag]) - want) <= slack, (name, 'dot', tag, float(res['dot_' + tag]), want)
+        qs[which] = q
+        b = torch.from_numpy(res['b_' + which])
+        refb, tolb = ref64.bound_rhs(ops, taus, [xn.dat for xn in R['xc']], prob['w'][0], prob['z'][0], rho, lam, vx,
+                                     which, at=R.get('at'))
+        r = ref64.compare(b, refb, tolb, my)
+        assert r['ok'], (name, 'rhs', which, r)
+        rep['b ' + which] = r['max_ratio']
+        if not proj:
+            continue
+        b64 = b.double()
+
+        def obj_check(key, x, q_ref, q_tol, q_err_ties):
+            x64 = x.double().abs()
+            want = 0.5 * float(((q_ref - 2 * b64) * x.double()).sum())
+            tol = 0.5 * float((x64 * (q_tol + 3 * ref64.U * (q_ref.abs() + 2 * b64.abs()))).sum()) + 0.5 * q_err_ties
+            got = float(res[key])
+            assert abs(got - want) <= tol, (name, key, got, want, tol)
+            return abs(got - want) / tol
+
+        ties = float((p64.abs() * (q.double() - refq).abs())[myy].sum())
+        rep['obj0 ' + which] = obj_check('obj0_' + which, p, refq, tolq, ties)
+        assert 'obj1_' + which in res, (name, 'the solve ran no iteration', which)
+        x1 = torch.from_numpy(res['x1_' + which])
+        ref1, tol1 = ref64.bound_matvec_reps(ops, taus, x1, rho, lam, vx, which)
+        tie1 = float((x1.double().abs() * (torch.from_numpy(res['q1_' + which]).double() - ref1).abs())[myy].sum())
+        rep['obj1 ' + which] = obj_check('obj1_' + which, x1, ref1, tol1, tie1)
+    assert not torch.equal(qs['backward'], qs['central']), name
+    return rep, int(myy.sum()), int(my.sum())
+
+
+_DIFF_DEAD = []  # set by the first child that exits non-zero or times out: nothing more runs on the GPU after it
+
+
+@pytest.mark.parametrize('name', list(DIFF_CASES))
+def test_every_form_per_voxel_with_backward_and_central_differences(tmp_path, name):
+    """Every form of DIFF_CASES with sett.diff = 'backward' and 'central': the matvec q per voxel against
+    ref64.bound_matvec_reps, its dot, the right-hand side b per voxel against ref64.bound_rhs, and the first two
+    objectives of a 'max_gain' solve (``_check_diff``).  One child per case, both differences in it."""
+    assert not _DIFF_DEAD, ('an earlier case\'s child died: not started', _DIFF_DEAD)
+    case = DIFF_CASES[name]
+    try:
+        res, build = _run_child(tmp_path, name, case, diffs=NONFWD, timeout=120)
+    except (AssertionError, subprocess.TimeoutExpired) as e:
+        _DIFF_DEAD.append((name, repr(e)[:300]))
+        raise
+    info = json.loads(str(res['info']))
+    info['perm'], info['flip'] = tuple(info['perm']), tuple(info['flip'])
+    R = diff_reference(case)
+    if R['prob']['do_proj']:  # the bound's orientation is restated, and must be the plan's
+        assert (info['perm'], info['flip']) == R['orient'][0], (name, info, R['orient'][0])
+    rep, n_yy, n_y = _check_diff(name, case, res, R)
+    print('diff %-18s %s build %s max err/tol: %s; excluded %d (matvec) %d (rhs)'
+          % (name, info, build, ', '.join('%s %.3f' % kv for kv in rep.items()), n_yy, n_y), flush=True)
+    assert case['expect'] is None or case['expect'](info), (name, info)
+    assert not (case.get('one_pass') and build is not None and build[0] != 'one-pass'), (name, build)
 
 
 @pytest.mark.slow

@@ -9,6 +9,7 @@ from oracle import nitorch_restated as N
 from oracle import unires_restated as O
 from tests import ref64
 from tests.helpers import make_problem, oracle_structs, rel_err
+from tests.test_gpu_voxelwise import DIFF_CASES, diff_reference, tie_cap_ok
 
 PROBLEMS = {
     'small_thick3': dict(dim_y=(16, 14, 12), thick=3, rot=0.1, trans=0.7),
@@ -93,3 +94,170 @@ def test_comparator_demands_exact_zero_outside_the_support():
     bad[far] = 1e-30  # (d) a single non-zero value outside the support
     r = ref64.compare(bad, ref, tol)
     assert not r['ok'] and r['first'] == far
+
+
+# ---- sett.diff = 'backward' / 'central': the matvec and right-hand side bounds with a `which` ------------------------
+NONFWD = ('backward', 'central')
+ANISO = (0.8, 1.25, 2.0)
+NF_PROBLEMS = {
+    'mid_thick6z_scl': PROBLEMS['mid_thick6z_scl'],
+    'mid_denoise': PROBLEMS['mid_denoise'],
+    'sr_2rep': dict(dim_y=(41, 38, 61), thick=4, n_repeats=2, rot=0.1, trans=2.0, scl=0.1),
+    'dn_aniso': dict(PROBLEMS['mid_denoise'], aniso=ANISO),
+}
+_NF_CACHE = {}
+
+
+def _nf_setup(name, seed=3):
+    """The problem, one Operator64 per repeat with the unions of their tie masks, the input p, and what does not
+    depend on the difference (the repeats' A^T A parts of p, the A^T bounds of their observations): built once."""
+    if name not in _NF_CACHE:
+        prob = make_problem(seed=seed, **NF_PROBLEMS[name])
+        xs, ys = oracle_structs(prob)
+        xc, yc = xs[0], ys[0]
+        ops = [ref64.Operator64(xn.po, prob['method']) for xn in xc]
+        my = torch.zeros(prob['dim_y'], dtype=torch.bool)
+        myy = my.clone()
+        for op, xn in zip(ops, xc):
+            _, a, b, _ = op.tie_masks(xn.po)
+            my |= a
+            myy |= b
+        gen = torch.Generator().manual_seed(seed + 1)
+        p = (torch.rand(prob['dim_y'], generator=gen) * 10 - 2).float()
+        _NF_CACHE[name] = dict(
+            prob=prob, xc=xc, yc=yc, ops=ops, my=my, myy=myy, p=p, taus=[xn.tau for xn in xc],
+            rho=torch.tensor(prob['rho'], dtype=torch.float32), vx=N.voxel_size(prob['mat_y']).float(),
+            parts=[op.parts_AtA(p) for op in ops], at=[op.bound_At(xn.dat) for op, xn in zip(ops, xc)])
+    return _NF_CACHE[name]
+
+
+def _nf_bounds(S, which):
+    q = ref64.bound_matvec_reps(S['ops'], S['taus'], S['p'], S['rho'], S['yc'].lam, S['vx'], which, parts=S['parts'])
+    b = ref64.bound_rhs(S['ops'], S['taus'], [xn.dat for xn in S['xc']], S['prob']['w'][0], S['prob']['z'][0],
+                        S['rho'], S['yc'].lam, S['vx'], which, at=S['at'])
+    return q, b
+
+
+@pytest.mark.parametrize('which', NONFWD)
+@pytest.mark.parametrize('name', list(NF_PROBLEMS))
+def test_float32_composition_passes_the_backward_and_central_bounds(monkeypatch, name, which):
+    """Sound: the float32 oracle with its gradient / divergence replaced by `which`'s (tests/test_gpu_diff.py
+    ``_patch_oracle``) - a correct float32 implementation of the matvec and of the right-hand side - passes
+    ``bound_matvec(which)`` / ``bound_matvec_reps`` and ``bound_rhs`` outside ties, and really differs from float64."""
+    from tests.test_gpu_diff import _patch_oracle
+    S = _nf_setup(name)
+    prob, xc, yc = S['prob'], S['xc'], S['yc']
+    assert int(S['myy'].sum()) < 0.01 * S['p'].numel()
+    (refq, tolq), (refb, tolb) = _nf_bounds(S, which)
+    if len(xc) == 1:  # the method of one repeat is the same bound
+        r1, t1 = S['ops'][0].bound_matvec(S['p'], xc[0].tau, S['rho'], yc.lam, S['vx'], which)
+        assert torch.equal(r1, refq) and torch.equal(t1, tolq)
+    _patch_oracle(monkeypatch, which)
+    q32 = O.proj('AtA', S['p'], xc, yc, method=prob['method'], do=True, rho=S['rho'], vx_y=S['vx'], diff=which)
+    r = ref64.compare(q32, refq, tolq, S['myy'])
+    assert r['ok'] and r['max_ratio'] > 0.0, ('matvec', r)
+    b32 = O.y_rhs(xc, yc, prob['z'][0], prob['w'][0], S['rho'], S['vx'], prob['method'], True)
+    rb = ref64.compare(b32, refb, tolb, S['my'])
+    assert rb['ok'] and rb['max_ratio'] > 0.0, ('rhs', rb)
+    print('sound %s %s: matvec %.3f, rhs %.3f of the bound' % (name, which, r['max_ratio'], rb['max_ratio']))
+
+
+def test_forward_matvec_bound_is_the_parent_formula_bit_for_bit():
+    """``bound_matvec`` without a `which` (and with 'forward') returns what it returned before it had one: compared
+    with a copy of that formula."""
+    prob, xc, yc, po, op, p, v = _setup(PROBLEMS['small_thick3'])
+    rho = torch.tensor(prob['rho'], dtype=torch.float32)
+    vx = N.voxel_size(prob['mat_y']).float()
+
+    def parent(self, p, tau, rho, lam, vx):
+        tau, rho, lam = (float(torch.tensor(float(v), dtype=torch.float32)) for v in (tau, rho, lam))
+        vx = torch.as_tensor(vx, dtype=torch.float32).double()
+        ref, M, G, D = self.parts_AtA(p)
+        c = rho * lam * lam
+        p64 = p.double()
+        ref = tau * ref + c * O.DtD(p64, vx)
+        Md = c * ref64.dtd_abs(p64.abs(), vx)
+        tol = (ref64.U + ref64.U64) * (self.c_AtA + ref64.C_DTD) * (tau * M + Md) + tau * G + tau * D
+        return ref, tol
+
+    want = parent(op, p, xc[0].tau, rho, yc.lam, vx)
+    args = (p, xc[0].tau, rho, yc.lam, vx)
+    for got in (op.bound_matvec(*args), op.bound_matvec(*args, 'forward')):
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    # ... and the `which`-general form states the same operator for 'forward' (its own rounding apart)
+    ref2, tol2 = ref64.bound_matvec_reps([op], [xc[0].tau], p, rho, yc.lam, vx, 'forward')
+    assert torch.allclose(ref2, want[0], rtol=1e-12, atol=0) and torch.allclose(tol2, want[1], rtol=1e-12, atol=0)
+
+
+def _stencil(S, which, vx=None, axis_scale=(1.0, 1.0, 1.0)):
+    """c DtD_which p in float64 with per-axis factors on the weights (a plant's handle)."""
+    from tests import diff64
+    c = ref64._f32(S['rho']) * ref64._f32(S['yc'].lam) ** 2
+    vx = [float(v) for v in (S['vx'] if vx is None else vx)]
+    p = S['p'].double().numpy()
+    out = 0.0
+    for d in range(3):
+        dtd_d = diff64._apply(diff64._apply(p, d, which, False, False), d, which, True, False)
+        out = out + axis_scale[d] * dtd_d / vx[d] ** 2
+    return c * torch.from_numpy(out)
+
+
+def _plants(name, which):
+    """(label, planted float64 matvec) pairs for the case: each a wrong closing pass a kernel could plausibly run."""
+    S = _nf_setup(name)
+    (refq, _), _ = _nf_bounds(S, which)
+    data = refq - _stencil(S, which)  # sum tau AtA p
+    nz = S['p'].shape[2]
+    out = [('other stencil', data + _stencil(S, 'forward' if which == 'backward' else 'backward'))]
+    if which == 'central':
+        out.append(('no 1/4 on y', data + _stencil(S, which, axis_scale=(1.0, 4.0, 1.0))))
+        # k = nz - 2 treated as a face: the (p[k + 2] (= 0) - p[k]) / 4 term is dropped there
+        vz = float(S['vx'][2])
+        c = ref64._f32(S['rho']) * ref64._f32(S['yc'].lam) ** 2
+        off = refq.clone()
+        off[:, :, nz - 2] -= c * 0.25 / vz ** 2 * S['p'].double()[:, :, nz - 2]
+        out.append(('plane nz - 2 a face', off))
+    if name == 'dn_aniso':
+        out.append(('cx, cz swapped', data + _stencil(S, which, vx=[S['vx'][2], S['vx'][1], S['vx'][0]])))
+    if name == 'sr_2rep':
+        out.append(('stencil twice', data + 2 * _stencil(S, which)))
+        out.append(('no stencil', data))
+    ends = refq.clone()  # head and tail of an unaligned q: the first / last 3 voxels of the flat array not closed
+    ends.view(-1)[:3] = data.reshape(-1)[:3]
+    ends.view(-1)[-3:] = data.reshape(-1)[-3:]
+    out.append(('3 + 3 end voxels left at the data term', ends))
+    return S, out
+
+
+@pytest.mark.parametrize('which', NONFWD)
+@pytest.mark.parametrize('name', ['mid_denoise', 'dn_aniso', 'sr_2rep'])
+def test_comparator_catches_wrong_closing_passes(name, which):
+    """Sharp: each planted error, cast to float32, fails ``bound_matvec(which)`` outside ties, in at least as many
+    voxels as it touches.  Whether the relative-L2 gate of tests/test_gpu_diff.py (1e-4) would have passed it is
+    printed.  Observed: none passes it at these sizes against this reference - the smallest are the six end voxels
+    (rel_err 3.4e-3 - 7.2e-3, six voxels at 1.6e5 - 2.4e5 times their tolerance) and central's plane nz - 2 (4.9e-3 -
+    2.4e-2); what let such errors through in that test was not the gate's width but its cases (isotropic voxels:
+    cx = cy = cz, so swapped weights are the same weights) and its reference (the GPU's own op-level kernels)."""
+    S, plants = _plants(name, which)
+    (refq, tolq), _ = _nf_bounds(S, which)
+    assert ref64.compare(refq.float(), refq, tolq, S['myy'])['ok']  # (the unplanted reference, cast, passes)
+    for label, bad in plants:
+        bad32 = bad.float()
+        r = ref64.compare(bad32, refq, tolq, S['myy'])
+        l2 = rel_err(bad32, refq)
+        print('plant %s %s %-40s n_bad %6d max err/tol %9.3g rel_err %.3g (%s the 1e-4 gate)'
+              % (name, which, label, r['n_bad'], r['max_ratio'], l2, 'passes' if l2 < 1e-4 else 'fails'))
+        assert not r['ok'] and r['n_bad'] >= 3, (label, r)
+
+
+@pytest.mark.parametrize('name', list(DIFF_CASES))
+def test_tie_cap_of_the_nonforward_table(name):
+    """A condition on the cases of tests/test_gpu_voxelwise.py's DIFF_CASES, met by the reference alone: fewer than
+    1 % of the voxels are excluded as FOV ties (none in a volume below 100 voxels), for the matvec and the
+    right-hand side."""
+    R = diff_reference(DIFF_CASES[name])
+    n = R['p'].numel()
+    print('ties %s: %d (matvec) %d (rhs) of %d' % (name, int(R['myy'].sum()), int(R['my'].sum()), n))
+    assert tie_cap_ok(R), (name, int(R['myy'].sum()), int(R['my'].sum()), n)
+    if n < 100:
+        assert int(R['myy'].sum()) == 0
