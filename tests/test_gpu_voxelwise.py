@@ -81,7 +81,7 @@ most instructions in one tile: 23 - 26 below 0.3 rad, 33 - 48 in the two-pass sw
 suite found no kernel bug.
 
 The table with a non-forward D (``DIFF_CASES``, ``test_every_form_per_voxel_with_backward_and_central_differences``).
-A plan with sett.diff = 'backward' / 'central' composes its matvec differently (api_operator.hip matvec_nonforward):
+A plan with sett.diff = 'backward' / 'central' composes its matvec differently (api_operator.hip, matvec):
 every AtA kernel runs without its stencil epilogue, and one pass - k_dtd_flat_w<W, ACC>, or k_dtd<W, ACC> where the
 flat kernel declines the shape - adds c DtD_W p to the stored q and closes the matvec with the dot or the objective.
 One child per case sets each difference in turn on the same plan and writes q with its float64 dot, the right-hand
@@ -226,7 +226,7 @@ for _n in CASES:
         CASES[_n]['one_pass'] = True
 
 # The table with a non-forward D (sett.diff = 'backward' / 'central'): the smallest shapes that still select each form
-# the matvec of such a plan chooses between (api_operator.hip, matvec_nonforward), by name from the table above where
+# the matvec of such a plan chooses between (api_operator.hip, matvec), by name from the table above where
 # it has them, and the shapes where the closing stencil pass turns: anisotropic voxels (cx != cy != cz), two repeats
 # (the accumulating stores), the k_dtd fallback of the flat kernel (fewer than 64 voxels; nz < 4) and an output 4, 8
 # and 12 bytes off a 16-byte boundary.  No conv-table / row-code / grid limits and no sweep: those exercise the

@@ -177,16 +177,11 @@ def _vx3(vx):
 
 @on_device
 def grad(dat, vx=None, which='forward'):
-    """D dat -> (3,X,Y,Z), zero bound, ``which`` = 'forward' | 'backward' | 'central'.  'forward' takes the entry
-    point it always took."""
+    """D dat -> (3,X,Y,Z), zero bound, ``which`` = 'forward' | 'backward' | 'central'."""
     w = _lib.diff_code(which, 'which')
     s, _ = _vol(dat)
     out = torch.empty((3,) + tuple(s.shape), dtype=torch.float32, device=s.device)
-    if w == 0:
-        check(_lib.load().unires_grad_fwd_zero(_ptr(s), i3(s.shape), f3(_vx3(vx)), _ptr(out),
-                                               _stream()))
-    else:
-        check(_lib.load().unires_grad_which(_ptr(s), i3(s.shape), f3(_vx3(vx)), w, _ptr(out), _stream()))
+    check(_lib.load().unires_grad_which(_ptr(s), i3(s.shape), f3(_vx3(vx)), w, _ptr(out), _stream()))
     return out
 
 
@@ -204,11 +199,7 @@ def div(dat3, vx=None, which='forward'):
         raise RuntimeError('unires_amd: divergence input must be a float32 CUDA/HIP tensor')
     s = dat3.contiguous()
     out = torch.empty(tuple(s.shape[1:]), dtype=torch.float32, device=s.device)
-    if w == 0:
-        check(_lib.load().unires_div_fwd_zero(_ptr(s), i3(s.shape[1:]), f3(_vx3(vx)), _ptr(out),
-                                              _stream()))
-    else:
-        check(_lib.load().unires_div_which(_ptr(s), i3(s.shape[1:]), f3(_vx3(vx)), w, _ptr(out), _stream()))
+    check(_lib.load().unires_div_which(_ptr(s), i3(s.shape[1:]), f3(_vx3(vx)), w, _ptr(out), _stream()))
     return out
 
 
@@ -222,10 +213,6 @@ def dtd(dat, vx=None, a=0.0, c=1.0, which='forward'):
     w = _lib.diff_code(which, 'diff')
     s, lead = _vol(dat)
     out = torch.empty_like(s)
-    if w == 0:
-        check(_lib.load().unires_dtd(_ptr(s), i3(s.shape), f3(_vx3(vx)), float(a), float(c),
-                                     _ptr(out), _stream()))
-    else:
-        check(_lib.load().unires_dtd_which(_ptr(s), i3(s.shape), f3(_vx3(vx)), w, float(a), float(c),
-                                           _ptr(out), _stream()))
+    check(_lib.load().unires_dtd_which(_ptr(s), i3(s.shape), f3(_vx3(vx)), w, float(a), float(c),
+                                       _ptr(out), _stream()))
     return out.reshape(lead + tuple(s.shape))

@@ -185,12 +185,8 @@ def _update_zw(y, z, w, rho, tmp, sett):
     vx = [float(v) for v in voxel_size(y[0].mat).tolist()]
     ptrs, lams = _chan_args(y)
     diff = _lib.diff_code(_diff(sett), 'sett.diff')
-    if diff == 0:
-        check(_lib.load().unires_zw_update(ptrs, lams, len(y), i3(y[0].dim), f3(vx), float(rho),
-                                           float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
-    else:
-        check(_lib.load().unires_zw_update_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, float(rho),
-                                                 float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
+    check(_lib.load().unires_zw_update_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, float(rho),
+                                             float(sett.alpha), _ptr(z), _ptr(w), _ptr(tmp), _stream()))
     return z, w, tmp
 
 
@@ -212,10 +208,7 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64):
     ptrs, lams = _chan_args(y)
     nll_y = torch.zeros((), dtype=torch.float64, device=dev)
     diff = _lib.diff_code(_diff(sett), 'sett.diff')
-    if diff == 0:
-        check(lib.unires_nll_prior(ptrs, lams, len(y), i3(y[0].dim), f3(vx), _ptr(nll_y), _stream()))
-    else:
-        check(lib.unires_nll_prior_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, _ptr(nll_y), _stream()))
+    check(lib.unires_nll_prior_which(ptrs, lams, len(y), i3(y[0].dim), f3(vx), diff, _ptr(nll_y), _stream()))
     return nll_xy + nll_y, nll_xy, nll_y
 
 

@@ -330,15 +330,11 @@ int launch_jtv_scale(const float *const *y, const float *lam, int nc, const floa
     C.n = nc - c0 < 8 ? nc - c0 : 8;
     C.c0 = c0, C.first = c0 == 0, C.last = c0 + 8 >= nc;
     for (int c = 0; c < 8; ++c) C.y[c] = y[c0 + (c < C.n ? c : 0)], C.lam[c] = lam[c0 + (c < C.n ? c : 0)];
-#define JTV_LAUNCH_W(NCV, WV)                                                                            \
-  hipLaunchKernelGGL((k_jtv_scale<NCV, WV>), grid, vblock(), 0, st, C, w, z_old, d, ivx, ivy, ivz, rho, alpha, \
-                     scale, partials, norm_only)
-#define JTV_LAUNCH(NCV)                                      \
-  switch (which) {                                           \
-    case kDiffBackward: JTV_LAUNCH_W(NCV, kDiffBackward); break; \
-    case kDiffCentral: JTV_LAUNCH_W(NCV, kDiffCentral); break;   \
-    default: JTV_LAUNCH_W(NCV, kDiffForward); break;         \
-  }
+#define JTV_LAUNCH(NCV)                                                                                             \
+  by_diff(which, [&](auto W) {                                                                                      \
+    hipLaunchKernelGGL((k_jtv_scale<NCV, W()>), grid, vblock(), 0, st, C, w, z_old, d, ivx, ivy, ivz, rho, alpha, \
+                       scale, partials, norm_only);                                                                 \
+  })
     switch (C.n) {
       case 1: JTV_LAUNCH(1); break;
       case 2: JTV_LAUNCH(2); break;
@@ -347,7 +343,6 @@ int launch_jtv_scale(const float *const *y, const float *lam, int nc, const floa
       default: JTV_LAUNCH(0); break;
     }
 #undef JTV_LAUNCH
-#undef JTV_LAUNCH_W
   }
   if (out) launch_sum_cols(part, g, 1, out, st);
   return g;
@@ -358,14 +353,9 @@ void launch_zw_update(const float *y, float lam, const float *scale, float *z, f
   const dim3 grid((d.z + kWave - 1) / kWave, (d.y + 3) / 4, d.x);
   const float h = diff_grad_scale(which);
   const float ivx = 1.f / vx[0] * h, ivy = 1.f / vx[1] * h, ivz = 1.f / vx[2] * h;
-#define ZW_LAUNCH(WV) \
-  hipLaunchKernelGGL(k_zw_update<WV>, grid, vblock(), 0, st, y, lam, scale, z, w, d, ivx, ivy, ivz, rho, alpha)
-  switch (which) {
-    case kDiffBackward: ZW_LAUNCH(kDiffBackward); break;
-    case kDiffCentral: ZW_LAUNCH(kDiffCentral); break;
-    default: ZW_LAUNCH(kDiffForward); break;
-  }
-#undef ZW_LAUNCH
+  by_diff(which, [&](auto W) {
+    hipLaunchKernelGGL(k_zw_update<W()>, grid, vblock(), 0, st, y, lam, scale, z, w, d, ivx, ivy, ivz, rho, alpha);
+  });
 }
 
 int masked_sse_blocks(size_t n) {

@@ -309,7 +309,9 @@ extern "C" int unires_conv_up3d(const float *src, const int32_t sdim[3],
   return UNIRES_OK;
 }
 
-static int grad_impl(const float *src, const int32_t dim[3], const float vx[3], int which, float *dst3, void *stream) {
+// (each forward-only name is its _which sibling with UNIRES_DIFF_FORWARD)
+extern "C" int unires_grad_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
+                                 float *dst3, void *stream) {
   if (!src || !dst3 || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
@@ -318,8 +320,13 @@ static int grad_impl(const float *src, const int32_t dim[3], const float vx[3], 
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
+extern "C" int unires_grad_fwd_zero(const float *src, const int32_t dim[3], const float vx[3],
+                                    float *dst3, void *stream) {
+  return unires_grad_which(src, dim, vx, UNIRES_DIFF_FORWARD, dst3, stream);
+}
 
-static int div_impl(const float *src3, const int32_t dim[3], const float vx[3], int which, float *dst, void *stream) {
+extern "C" int unires_div_which(const float *src3, const int32_t dim[3], const float vx[3], int32_t which,
+                                float *dst, void *stream) {
   if (!src3 || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
@@ -328,9 +335,13 @@ static int div_impl(const float *src3, const int32_t dim[3], const float vx[3], 
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
+extern "C" int unires_div_fwd_zero(const float *src3, const int32_t dim[3], const float vx[3],
+                                   float *dst, void *stream) {
+  return unires_div_which(src3, dim, vx, UNIRES_DIFF_FORWARD, dst, stream);
+}
 
-static int dtd_impl(const float *src, const int32_t dim[3], const float vx[3], int which, float a, float c, float *dst,
-                    void *stream) {
+extern "C" int unires_dtd_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
+                                float a, float c, float *dst, void *stream) {
   if (!src || !dst || !dim) return fail(UNIRES_ERR_NULL, "null argument");
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
   if (!vx_ok(vx)) return fail(UNIRES_ERR_ARG, "voxel size must be positive");
@@ -340,32 +351,9 @@ static int dtd_impl(const float *src, const int32_t dim[3], const float vx[3], i
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
-
-extern "C" int unires_grad_fwd_zero(const float *src, const int32_t dim[3], const float vx[3],
-                                    float *dst3, void *stream) {
-  return grad_impl(src, dim, vx, kDiffForward, dst3, stream);
-}
-extern "C" int unires_grad_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
-                                 float *dst3, void *stream) {
-  return grad_impl(src, dim, vx, which, dst3, stream);
-}
-
-extern "C" int unires_div_fwd_zero(const float *src3, const int32_t dim[3], const float vx[3],
-                                   float *dst, void *stream) {
-  return div_impl(src3, dim, vx, kDiffForward, dst, stream);
-}
-extern "C" int unires_div_which(const float *src3, const int32_t dim[3], const float vx[3], int32_t which,
-                                float *dst, void *stream) {
-  return div_impl(src3, dim, vx, which, dst, stream);
-}
-
 extern "C" int unires_dtd(const float *src, const int32_t dim[3], const float vx[3], float a,
                           float c, float *dst, void *stream) {
-  return dtd_impl(src, dim, vx, kDiffForward, a, c, dst, stream);
-}
-extern "C" int unires_dtd_which(const float *src, const int32_t dim[3], const float vx[3], int32_t which,
-                                float a, float c, float *dst, void *stream) {
-  return dtd_impl(src, dim, vx, which, a, c, dst, stream);
+  return unires_dtd_which(src, dim, vx, UNIRES_DIFF_FORWARD, a, c, dst, stream);
 }
 
 // --------------------------------------------------------------------------
@@ -379,8 +367,9 @@ static int check_channels(const float *const *y_ptrs, const float *lam, int32_t 
   return UNIRES_OK;
 }
 
-static int zw_impl(const float *const *y_ptrs, const float *lam, int32_t n_channels, const int32_t dim[3],
-                   const float vx[3], int which, float rho, float alpha, float *z, float *w, float *jtv, void *stream) {
+extern "C" int unires_zw_update_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                      const int32_t dim[3], const float vx[3], int32_t which, float rho,
+                                      float alpha, float *z, float *w, float *jtv, void *stream) {
   int rc = check_channels(y_ptrs, lam, n_channels);
   if (rc) return rc;
   if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
@@ -402,16 +391,12 @@ static int zw_impl(const float *const *y_ptrs, const float *lam, int32_t n_chann
 extern "C" int unires_zw_update(const float *const *y_ptrs, const float *lam, int32_t n_channels,
                                 const int32_t dim[3], const float vx[3], float rho, float alpha,
                                 float *z, float *w, float *jtv, void *stream) {
-  return zw_impl(y_ptrs, lam, n_channels, dim, vx, kDiffForward, rho, alpha, z, w, jtv, stream);
-}
-extern "C" int unires_zw_update_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
-                                      const int32_t dim[3], const float vx[3], int32_t which, float rho,
-                                      float alpha, float *z, float *w, float *jtv, void *stream) {
-  return zw_impl(y_ptrs, lam, n_channels, dim, vx, which, rho, alpha, z, w, jtv, stream);
+  return unires_zw_update_which(y_ptrs, lam, n_channels, dim, vx, UNIRES_DIFF_FORWARD, rho, alpha, z, w, jtv, stream);
 }
 
-static int nll_prior_impl(const float *const *y_ptrs, const float *lam, int32_t n_channels, const int32_t dim[3],
-                          const float vx[3], int which, double *out_dev, void *stream) {
+extern "C" int unires_nll_prior_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
+                                      const int32_t dim[3], const float vx[3], int32_t which, double *out_dev,
+                                      void *stream) {
   int rc = check_channels(y_ptrs, lam, n_channels);
   if (rc) return rc;
   if (!diff_ok(which)) return fail(UNIRES_ERR_ARG, "which: forward (0), backward (1) or central (2)");
@@ -453,12 +438,7 @@ static int nll_prior_impl(const float *const *y_ptrs, const float *lam, int32_t 
 extern "C" int unires_nll_prior(const float *const *y_ptrs, const float *lam, int32_t n_channels,
                                 const int32_t dim[3], const float vx[3], double *out_dev,
                                 void *stream) {
-  return nll_prior_impl(y_ptrs, lam, n_channels, dim, vx, kDiffForward, out_dev, stream);
-}
-extern "C" int unires_nll_prior_which(const float *const *y_ptrs, const float *lam, int32_t n_channels,
-                                      const int32_t dim[3], const float vx[3], int32_t which, double *out_dev,
-                                      void *stream) {
-  return nll_prior_impl(y_ptrs, lam, n_channels, dim, vx, which, out_dev, stream);
+  return unires_nll_prior_which(y_ptrs, lam, n_channels, dim, vx, UNIRES_DIFF_FORWARD, out_dev, stream);
 }
 
 extern "C" int unires_scaling_sums(const float *x, const float *ay, const int32_t dim[3],

@@ -231,50 +231,36 @@ extern "C" int unires_proj_apply(unires_plan_t *plan, int32_t n, int32_t op, con
   return UNIRES_OK;
 }
 
-// q (+)= c DtD_W p for a backward / central plan: the flat streaming kernel (stencil.hip), the general one where the
-// shape is outside its domain (lines shorter than 4, tiny volumes).  wr: c (1 / vx_d^2).  accumulate: q holds the data
-// term already.  Returns the number of partials written.
-static int stencil_close(unires_plan *pl, float c, const float wr[3], float a0, bool accumulate, const float *p, float *q,
-                         double *part, const int *done, hipStream_t st, const float *objb) {
+static bool no_aligned() {
+  static const bool v = getenv("UNIRES_NO_ALIGNED") != nullptr;
+  return v;
+}
+
+// The stencil pass of the matvec: q = a0 p + c DtD p (regime A = I: the whole matvec), or with `accumulate`
+// q += c DtD p on a q that holds the data term (the pass that closes a backward / central matvec).  One flat
+// streaming pass (stencil.hip); where the shape is outside its domain (lines shorter than 4, tiny volumes) the line
+// kernel (forward only), then the general one.  wr, wq: c / vx_d^2 in matvec()'s two roundings.  Returns the number of
+// partials written.
+static int stencil_close(unires_plan *pl, float c, const float wr[3], const float wq[3], float a0, bool accumulate,
+                         const float *p, float *q, double *part, const int *done, hipStream_t st, const float *objb) {
+  static const bool no_flat = getenv("UNIRES_NO_FLAT") != nullptr;  // (a switch of forward's line kernel)
+  const bool fwd = !diff_nonforward(pl->diff);
   const float h = diff_dtd_scale(pl->diff);
-  if (!launch_dtd_flat_w(pl->diff, p, q, pl->dy, a0, wr[0] * h, wr[1] * h, wr[2] * h, accumulate, part, objb, done, st))
-    return part ? dtd_flat_w_blocks(pl->dy) : 0;
+  if (!(fwd && no_flat) && !launch_dtd_flat(pl->diff, accumulate, p, q, pl->dy, a0, wr[0] * h, wr[1] * h, wr[2] * h, part,
+                                            objb, done, st))
+    return part ? dtd_flat_blocks(pl->dy, pl->diff) : 0;
+  if (fwd && !no_aligned() && !launch_dtd_lines(p, q, pl->dy, a0, wq[0], wq[1], wq[2], part, objb, done, st))
+    return part ? aligned_blocks(pl->dy) : 0;
   launch_dtd(p, pl->dy, pl->vx, a0, c, q, part, objb, done, st, pl->diff, accumulate);
   return part ? dtd_num_blocks(pl->dy) : 0;
 }
 
-// The matvec of a plan whose D is not forward's.  Every AtA runs on the kernel it runs on in a forward plan, with no
-// stencil epilogue (zero weights) and no partials; one stencil pass then adds c DtD_W p and closes the matvec with
-// the dot or the objective.  A = I is that pass alone.
-static int matvec_nonforward(unires_plan *pl, float c, const float wr[3], const float *p, float *q, double *part,
-                             const int *done, hipStream_t st, const float *objb) {
-  static const bool no_aligned = getenv("UNIRES_NO_ALIGNED") != nullptr;
-  if (pl->regime == UNIRES_REGIME_IDENTITY) {
-    float a0 = 0.f;
-    for (const Repeat &R : pl->reps) a0 += R.tau;
-    return stencil_close(pl, c, wr, a0, false, p, q, part, done, st, objb);
-  }
-  const size_t nrep = pl->reps.size();
-  bool have = false;
-  if (nrep == 1 && !no_aligned) {  // (the one-kernel forms, chosen as matvec() chooses them)
-    const Repeat &R = pl->reps[0];
-    have = (shift_fast(R.shift, pl->dy) &&
-            !launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st)) ||
-           !launch_ata_aligned(p, q, pl->dy, R.dim_gf, R.dim_x, R.Tf, make_scaling(2.f * R.scl, R.dim_thick), R.Af, R.tau,
-                               0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st) ||
-           !launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, done, st);
-  }
-  for (size_t n = 0; !have && n < nrep; ++n) {
-    PushEpilogue ep;
-    ep.accumulate = n > 0;
-    ata_apply(pl, pl->reps[n], p, pl->reps[n].tau, ep, true, q, done, st);
-  }
-  return stencil_close(pl, c, wr, 0.f, true, p, q, part, done, st, objb);
-}
-
+// One chain for every difference of D: A = I is the stencil pass alone; one repeat tries the one-kernel forms; else
+// one or two kernels per repeat.  The difference decides what the AtA kernels are given.  Forward's carry the
+// stencil term (wr / wq) and close the matvec with the dot or the objective.  Backward's and central's run on the same
+// kernels with zero weights and no partials, and stencil_close() then adds c DtD_W p and closes the matvec.
 int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float *q, double *part, const int *done,
                    hipStream_t st, const float *objb) {
-  static const bool no_aligned = getenv("UNIRES_NO_ALIGNED") != nullptr;
   // stencil weights rho lam^2 / vx_d^2, in the two roundings the kernels were validated with bit for bit:
   // wr = c * (1 / vx^2) (flat stencil, shift and aligned kernels), wq = c / vx^2 (line stencil, push epilogue)
   const float c = rho * (lam * lam);
@@ -283,47 +269,53 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
     const float v2 = pl->vx[d] * pl->vx[d];
     wr[d] = c * (1.f / v2), wq[d] = c / v2;
   }
-  if (pl->diff != kDiffForward) return matvec_nonforward(pl, c, wr, p, q, part, done, st, objb);
   if (pl->regime == UNIRES_REGIME_IDENTITY) {
     float a0 = 0.f;
     for (const Repeat &R : pl->reps) a0 += R.tau;
-    static const bool no_flat = getenv("UNIRES_NO_FLAT") != nullptr;
-    // one flat streaming pass (stencil.hip); the line kernel and the generic one are its fallbacks
-    if (!no_flat && !launch_dtd_flat(p, q, pl->dy, a0, wr[0], wr[1], wr[2], part, objb, done, st))
-      return part ? dtd_flat_blocks(pl->dy) : 0;
-    if (!no_aligned && !launch_dtd_lines(p, q, pl->dy, a0, wq[0], wq[1], wq[2], part, objb, done, st))
-      return part ? aligned_blocks(pl->dy) : 0;
-    launch_dtd(p, pl->dy, pl->vx, a0, c, q, part, objb, done, st);
-    return part ? dtd_num_blocks(pl->dy) : 0;
+    return stencil_close(pl, c, wr, wq, a0, false, p, q, part, done, st, objb);
   }
+  const bool fwd = !diff_nonforward(pl->diff);
+  const float zero[3] = {0.f, 0.f, 0.f};
+  const float *kw = fwd ? wr : zero;  // what the one-kernel forms receive
+  double *kpart = fwd ? part : nullptr;
+  const float *kobjb = fwd ? objb : nullptr;
   const size_t nrep = pl->reps.size();
-  if (nrep == 1 && !no_aligned) {
-    // grid-aligned observation (identity + integer shift, z slice profile): one streaming kernel
+  // the one-kernel forms of a one-repeat plan: the partials written, or -1 where none applies
+  const auto one_kernel = [&]() -> int {
+    if (nrep != 1 || no_aligned()) return -1;
     const Repeat &R = pl->reps[0];
-    // where the x-marching kernel's fast form applies it serves integer shifts too (31.5 us against
-    // k_ata_aligned4x2's 36 - 37 at 256^3)
-    if (shift_fast(R.shift, pl->dy) &&
-        !launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, wr[0], wr[1], wr[2], part, objb, done, st))
-      return part ? shift_blocks(pl->dy) : 0;
-    if (!launch_ata_aligned(p, q, pl->dy, R.dim_gf, R.dim_x, R.Tf, make_scaling(2.f * R.scl, R.dim_thick), R.Af,
-                            R.tau, 0.f, wr[0], wr[1], wr[2], part, objb, done, st))
-      return part ? aligned_blocks(pl->dy) : 0;
-    // ... or translated by a fraction of a voxel (no rotation): the factorised one-kernel matvec
-    if (!launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, wr[0], wr[1], wr[2], part, objb, done, st))
-      return part ? shift_blocks(pl->dy) : 0;
+    // translated by a fraction of a voxel (no rotation): the factorised one-kernel matvec.  Where the x-marching
+    // kernel's fast form applies it serves integer shifts too (31.5 us against k_ata_aligned4x2's 36 - 37 at 256^3)
+    // and is tried first
+    const auto shift = [&] {
+      return launch_ata_shift(R.shift, p, q, pl->dy, R.Af, R.tau, 0.f, kw[0], kw[1], kw[2], kpart, kobjb, done, st);
+    };
+    if (shift_fast(R.shift, pl->dy) && !shift()) return kpart ? shift_blocks(pl->dy) : 0;
+    // grid-aligned observation (identity + integer shift, z slice profile): one streaming kernel
+    if (!launch_ata_aligned(p, q, pl->dy, R.dim_gf, R.dim_x, R.Tf, make_scaling(2.f * R.scl, R.dim_thick), R.Af, R.tau,
+                            0.f, kw[0], kw[1], kw[2], kpart, kobjb, done, st))
+      return kpart ? aligned_blocks(pl->dy) : 0;
+    if (!shift()) return kpart ? shift_blocks(pl->dy) : 0;
+    return -1;
+  };
+  int npart = one_kernel();
+  if (npart < 0) {
+    // regimes 1/2: one or two kernels per repeat; forward's last one also adds c DtD p and the dot
+    npart = 0;
+    for (size_t n = 0; n < nrep; ++n) {
+      const Repeat &R = pl->reps[n];
+      PushEpilogue ep;
+      ep.accumulate = n > 0;
+      if (fwd) {
+        // (ep.p stays unset otherwise: the push kernels take their stencil branch, and read p, wherever it is set)
+        ep.p = p;
+        if (n == 0) ep.cx = wq[0], ep.cy = wq[1], ep.cz = wq[2];  // the stencil term goes in once
+        if (n + 1 == nrep) ep.partials = part, ep.objb = objb;
+      }
+      npart = ata_apply(pl, R, p, R.tau, ep, true, q, done, st);
+    }
   }
-  // regimes 1/2: one or two kernels per repeat; the last one also adds c DtD p and the dot
-  int npart = 0;
-  for (size_t n = 0; n < nrep; ++n) {
-    const Repeat &R = pl->reps[n];
-    PushEpilogue ep;
-    ep.p = p;
-    ep.accumulate = n > 0;
-    if (n == 0) ep.cx = wq[0], ep.cy = wq[1], ep.cz = wq[2];  // the stencil term goes in once
-    if (n + 1 == nrep) ep.partials = part, ep.objb = objb;
-    npart = ata_apply(pl, R, p, R.tau, ep, true, q, done, st);
-  }
-  return npart;
+  return fwd ? npart : stencil_close(pl, c, wr, wq, 0.f, true, p, q, part, done, st, objb);
 }
 
 extern "C" int unires_ata_matvec(unires_plan_t *plan, float rho, float lam, const float *p,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/unires_hip.h"
 
 namespace unires {
@@ -301,6 +303,17 @@ __host__ __device__ constexpr int diff_reach(int which) { return which == kDiffC
 __host__ __device__ constexpr float diff_dtd_scale(int which) { return which == kDiffCentral ? 0.25f : 1.f; }
 __host__ __device__ constexpr float diff_grad_scale(int which) { return which == kDiffCentral ? 0.5f : 1.f; }
 inline bool diff_ok(int which) { return which == kDiffForward || which == kDiffBackward || which == kDiffCentral; }
+inline bool diff_nonforward(int which) { return which == kDiffBackward || which == kDiffCentral; }
+// Runtime difference -> template parameter: f(std::integral_constant<int, kDiff...>()), forward for anything else.
+// Every launcher that instantiates a kernel per difference goes through here.
+template <class F>
+inline void by_diff(int which, F &&f) {
+  switch (which) {
+    case kDiffBackward: f(std::integral_constant<int, kDiffBackward>()); break;
+    case kDiffCentral: f(std::integral_constant<int, kDiffCentral>()); break;
+    default: f(std::integral_constant<int, kDiffForward>()); break;
+  }
+}
 
 // One axis of DtD in difference form, tb - tf with tb = (D p)[i-1 side] and tf = (D p)[i+1 side], unscaled.  c: the
 // centre; lo / hi: the values R = diff_reach(W) voxels below / above it; l1, h1: voxel i -+ 1 exists; lr, hr: voxel

@@ -1528,28 +1528,19 @@ void launch_conv_up(const float *xs, Dim3i xd, const Taps &T, const Scaling &S, 
   hipLaunchKernelGGL(k_conv_up, vol_grid(gd), vol_block(), 0, st, xs, xd, T, S, dst, gd);
 }
 
-// (one instantiation per difference; forward's is the code it always was)
-#define UNIRES_BY_DIFF(which, CALL)          \
-  switch (which) {                           \
-    case kDiffBackward: { CALL(kDiffBackward); } break; \
-    case kDiffCentral: { CALL(kDiffCentral); } break;   \
-    default: { CALL(kDiffForward); } break;  \
-  }
-
+// (one instantiation per difference, by_diff(): forward's is the code it always was)
 void launch_grad(const float *src, Dim3i d, const float vx[3], float *dst3, hipStream_t st, int which) {
-#define GRAD_CALL(WV) \
-  hipLaunchKernelGGL(k_grad<WV>, vol_grid(d), vol_block(), 0, st, src, d, 1.f / vx[0], 1.f / vx[1], 1.f / vx[2], dst3)
-  UNIRES_BY_DIFF(which, GRAD_CALL)
-#undef GRAD_CALL
+  by_diff(which, [&](auto W) {
+    hipLaunchKernelGGL(k_grad<W()>, vol_grid(d), vol_block(), 0, st, src, d, 1.f / vx[0], 1.f / vx[1], 1.f / vx[2], dst3);
+  });
 }
 
 void launch_div(const float *ua, const float *ub, float ca, float cb, Dim3i d, const float vx[3],
                 float scale, const float *add, float *dst, hipStream_t st, int which) {
-#define DIV_CALL(WV)                                                                                         \
-  hipLaunchKernelGGL(k_div<WV>, vol_grid(d), vol_block(), 0, st, ua, ub, ca, cb, d, 1.f / vx[0], 1.f / vx[1], \
-                     1.f / vx[2], scale, add, dst)
-  UNIRES_BY_DIFF(which, DIV_CALL)
-#undef DIV_CALL
+  by_diff(which, [&](auto W) {
+    hipLaunchKernelGGL(k_div<W()>, vol_grid(d), vol_block(), 0, st, ua, ub, ca, cb, d, 1.f / vx[0], 1.f / vx[1],
+                       1.f / vx[2], scale, add, dst);
+  });
 }
 
 int dtd_num_blocks(Dim3i d) {
@@ -1563,17 +1554,16 @@ void launch_dtd(const float *src, Dim3i d, const float vx[3], float a, float c, 
   const float h = diff_dtd_scale(which);
   const float cx = c / (vx[0] * vx[0]) * h, cy = c / (vx[1] * vx[1]) * h, cz = c / (vx[2] * vx[2]) * h;
   const dim3 grid(dtd_num_blocks(d));
-#define DTD_CALL(WV)                                                                                           \
-  if (accumulate && partials)                                                                                  \
-    hipLaunchKernelGGL((k_dtd<true, WV, true>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, objb, done); \
-  else if (accumulate)                                                                                         \
-    hipLaunchKernelGGL((k_dtd<false, WV, true>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, nullptr, done); \
-  else if (partials)                                                                                           \
-    hipLaunchKernelGGL((k_dtd<true, WV, false>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, objb, done); \
-  else                                                                                                         \
-    hipLaunchKernelGGL((k_dtd<false, WV, false>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, nullptr, done);
-  UNIRES_BY_DIFF(which, DTD_CALL)
-#undef DTD_CALL
+  by_diff(which, [&](auto W) {
+    if (accumulate && partials)
+      hipLaunchKernelGGL((k_dtd<true, W(), true>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, objb, done);
+    else if (accumulate)
+      hipLaunchKernelGGL((k_dtd<false, W(), true>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, nullptr, done);
+    else if (partials)
+      hipLaunchKernelGGL((k_dtd<true, W(), false>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, objb, done);
+    else
+      hipLaunchKernelGGL((k_dtd<false, W(), false>), grid, vol_block(), 0, st, src, d, cx, cy, cz, a, dst, partials, nullptr, done);
+  });
 }
 
 }  // namespace unires

@@ -508,9 +508,9 @@ static int flat_grid(unsigned nchunk) {
   return (int)((nchunk + per - 1) / per);
 }
 
-int dtd_flat_blocks(Dim3i dd) {
+int dtd_flat_blocks(Dim3i dd, int which) {
   FlatMArgs M;
-  if (flat_m_geometry(dd, M)) return flat_m_blocks(M);
+  if (!diff_nonforward(which) && flat_m_geometry(dd, M)) return flat_m_blocks(M);
   const size_t n = dd.numel();
   return flat_grid((unsigned)((n / 4 * 4 + kFlatChunk - 1) / kFlatChunk));
 }
@@ -540,69 +540,59 @@ static void flat_ranges(FlatArgs &A, unsigned G) {
   }
 }
 
-// Non-zero return: outside the kernel's domain (tiny or huge volumes), nothing launched.
-int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
-                    double *partials, const float *objb, const int *done, hipStream_t st) {
+// The epilogue a launch asks for, as the kernels' <DOT, OBJ>: launch(DOT, OBJ) with std::bool_constant arguments.
+template <class L>
+static void by_epilogue(const double *partials, const float *objb, L &&launch) {
+  if (objb)
+    launch(std::true_type(), std::true_type());
+  else if (partials)
+    launch(std::true_type(), std::false_type());
+  else
+    launch(std::false_type(), std::false_type());
+}
+
+// Non-zero return: outside the kernels' domain (tiny or huge volumes; forward with `accumulate`), nothing launched.
+int launch_dtd_flat(int which, bool accumulate, const float *p, float *q, Dim3i dd, float a0, float cx, float cy,
+                    float cz, double *partials, const float *objb, const int *done, hipStream_t st) {
+  const bool fwd = !diff_nonforward(which);
   FlatArgs A;
-  if (!flat_args(p, q, dd, a0, cx, cy, cz, partials, objb, A)) return 1;
+  if (!flat_args(p, q, dd, a0, cx, cy, cz, partials, objb, A) || (fwd && accumulate)) return 1;
+  const dim3 block(kBlock);
   FlatMArgs M;
-  if (flat_m_geometry(dd, M)) {
+  if (fwd && flat_m_geometry(dd, M)) {
     M.F = A;
     static const int fdbg = getenv("UNIRES_FLAT_DBG") ? atoi(getenv("UNIRES_FLAT_DBG")) : 0;
     M.dbg = fdbg;
-    const dim3 grid(flat_m_blocks(M)), block(kBlock);
-    if (objb)
-      hipLaunchKernelGGL((k_dtd_flat_m<true, true>), grid, block, 0, st, M, done);
-    else if (partials)
-      hipLaunchKernelGGL((k_dtd_flat_m<true, false>), grid, block, 0, st, M, done);
-    else
-      hipLaunchKernelGGL((k_dtd_flat_m<false, false>), grid, block, 0, st, M, done);
+    const dim3 grid(flat_m_blocks(M));
+    by_epilogue(partials, objb, [&](auto DOT, auto OBJ) {
+      hipLaunchKernelGGL((k_dtd_flat_m<DOT(), OBJ()>), grid, block, 0, st, M, done);
+    });
     return 0;
   }
-  const unsigned G = (unsigned)dtd_flat_blocks(dd);
-  flat_ranges(A, G);
   // the number of partials must not depend on q's alignment: callers size their reduction with
-  // dtd_flat_blocks(dd)
-  const dim3 grid(G), block(kBlock);
-  if (objb)
-    hipLaunchKernelGGL((k_dtd_flat<true, true>), grid, block, 0, st, A, done);
-  else if (partials)
-    hipLaunchKernelGGL((k_dtd_flat<true, false>), grid, block, 0, st, A, done);
-  else
-    hipLaunchKernelGGL((k_dtd_flat<false, false>), grid, block, 0, st, A, done);
-  return 0;
-}
-
-int dtd_flat_w_blocks(Dim3i dd) {
-  const size_t n = dd.numel();
-  return flat_grid((unsigned)((n / 4 * 4 + kFlatChunk - 1) / kFlatChunk));
-}
-
-template <int W, bool ACC>
-static void launch_flat_w(const FlatArgs &A, unsigned G, const int *done, hipStream_t st) {
-  const dim3 grid(G), block(kBlock);
-  if (A.objb)
-    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, true, true>), grid, block, 0, st, A, done);
-  else if (A.partials)
-    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, true, false>), grid, block, 0, st, A, done);
-  else
-    hipLaunchKernelGGL((k_dtd_flat_w<W, ACC, false, false>), grid, block, 0, st, A, done);
-}
-
-int launch_dtd_flat_w(int which, const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
-                      bool accumulate, double *partials, const float *objb, const int *done, hipStream_t st) {
-  if (which != kDiffBackward && which != kDiffCentral) return 1;
-  FlatArgs A;
-  if (!flat_args(p, q, dd, a0, cx, cy, cz, partials, objb, A)) return 1;
-  const unsigned G = (unsigned)dtd_flat_w_blocks(dd);
+  // dtd_flat_blocks(dd, which)
+  const unsigned G = (unsigned)dtd_flat_blocks(dd, which);
   flat_ranges(A, G);
-  if (which == kDiffBackward) {
-    if (accumulate) launch_flat_w<kDiffBackward, true>(A, G, done, st);
-    else launch_flat_w<kDiffBackward, false>(A, G, done, st);
-  } else {
-    if (accumulate) launch_flat_w<kDiffCentral, true>(A, G, done, st);
-    else launch_flat_w<kDiffCentral, false>(A, G, done, st);
+  const dim3 grid(G);
+  if (fwd) {
+    by_epilogue(partials, objb, [&](auto DOT, auto OBJ) {
+      hipLaunchKernelGGL((k_dtd_flat<DOT(), OBJ()>), grid, block, 0, st, A, done);
+    });
+    return 0;
   }
+  by_diff(which, [&](auto Wc) {
+    constexpr int W = decltype(Wc)::value;
+    if constexpr (W != kDiffForward) {  // (forward went above: k_dtd_flat_w has no forward instantiation)
+      if (accumulate)
+        by_epilogue(partials, objb, [&](auto DOT, auto OBJ) {
+          hipLaunchKernelGGL((k_dtd_flat_w<W, true, DOT(), OBJ()>), grid, block, 0, st, A, done);
+        });
+      else
+        by_epilogue(partials, objb, [&](auto DOT, auto OBJ) {
+          hipLaunchKernelGGL((k_dtd_flat_w<W, false, DOT(), OBJ()>), grid, block, 0, st, A, done);
+        });
+    }
+  });
   return 0;
 }
 

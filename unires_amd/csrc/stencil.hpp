@@ -4,18 +4,14 @@
 
 namespace unires {
 
-int dtd_flat_blocks(Dim3i dd);  // partial sums written per launch
-// q = a0 p + c DtD p with per-axis weights cx, cy, cz = c / vx^2 (+ partials of sum p*q, or of the
-// objective sum (q - 2 objb) p without storing q).  Non-zero return: volume outside the kernel's
-// domain, nothing launched.
-int launch_dtd_flat(const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
-                    double *partials, const float *objb, const int *done, hipStream_t st);
-
-// The same pass for backward / central differences (`which`: kDiffBackward or kDiffCentral; weights already times
-// diff_dtd_scale(which)).  accumulate: q += c DtD p (a0 unused; the partials are of the accumulated q) - the pass that
-// closes a non-forward matvec.  Non-zero return: outside the domain (or which == forward), nothing launched.
-int dtd_flat_w_blocks(Dim3i dd);
-int launch_dtd_flat_w(int which, const float *p, float *q, Dim3i dd, float a0, float cx, float cy, float cz,
-                      bool accumulate, double *partials, const float *objb, const int *done, hipStream_t st);
+// `which`: the difference of D (common.hpp).  Forward runs k_dtd_flat (or its marching form), backward / central
+// k_dtd_flat_w; their grids, and so the partial counts, differ only where the marching form is on.
+int dtd_flat_blocks(Dim3i dd, int which);  // partial sums written per launch
+// q = a0 p + c DtD p with per-axis weights cx, cy, cz = c / vx^2, already times diff_dtd_scale(which) (+ partials of
+// sum p*q, or of the objective sum (q - 2 objb) p without storing q).  accumulate: q += c DtD p (a0 unused; the
+// partials are of the accumulated q) - the pass that closes a non-forward matvec; forward has no such form.
+// Non-zero return: outside the kernels' domain, nothing launched.
+int launch_dtd_flat(int which, bool accumulate, const float *p, float *q, Dim3i dd, float a0, float cx, float cy,
+                    float cz, double *partials, const float *objb, const int *done, hipStream_t st);
 
 }  // namespace unires
