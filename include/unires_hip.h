@@ -253,6 +253,24 @@ int unires_plan_set_concurrency(unires_plan_t *plan, int32_t n_concurrent);
  * kernels a forward plan uses, without their stencil epilogue, and closes the matvec with one streaming stencil
  * pass (stencil.hip: k_dtd_flat_w).  Changing it drops the captured CG graphs and the built preconditioner. */
 int unires_plan_set_diff(unires_plan_t *plan, int32_t which);
+/* Missing data (no counterpart in the reference, whose y-update treats a zero-filled voxel as an observed 0):
+ * x = repeat n's observation, dim_x float32 in the caller's voxel layout, on the device.  The plan builds the mask
+ * m(v) = [x(v) != 0] on `stream` (one byte per voxel, owned by the plan, stored in its canonical layout) and from then
+ * on applies A_n^T diag(m) A_n wherever it applied A_n^T A_n: in the matvec of unires_ata_matvec and of the CG solves,
+ * in unires_proj_apply's UNIRES_OP_ATA, in the Jacobi diagonal and in the mean diagonal of the FFT preconditioner's
+ * symbol (the symbol's form is unchanged).  A, A^T and the right-hand side are unchanged: A_n^T x_n carries the
+ * zeros already.  A masked repeat runs forward -> mask -> push: the one-kernel matvecs, the single-pass AtA kernel and
+ * the hybrid forms are not taken (unires_plan_repeat_info shows it); unmasked repeats of the plan keep their forms.
+ * x == NULL clears the mask.  Call again when the observation's values change; unires_plan_set_repeat keeps the mask
+ * (the new descriptor must have the same dim_x).  Setting, changing or clearing a mask drops the captured CG graphs
+ * and the built preconditioner.  The mask is written by kernels on `stream` and not waited for: work that uses the
+ * plan on ANOTHER stream must be ordered after this call by the caller (an event recorded on `stream` afterwards).
+ * A one-repeat plan whose observation is all zero has an empty data term: its system is still positive definite
+ * (the zero-bound D^T D is), CG and the Jacobi diagonal work, but UNIRES_PRECOND_FFT returns UNIRES_ERR_ARG ("data
+ * term has an empty diagonal") as it does for any operator with a zero mean diagonal - the symbol's constant would
+ * be 0.  UNIRES_REGIME_IDENTITY has no x-space intermediate: UNIRES_ERR_UNSUPPORTED (build
+ * the plan as UNIRES_REGIME_DENOISE with the identity affine instead). */
+int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const float *x, void *stream);
 /* Bytes of device workspace the plan owns. */
 int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
 /* Which kernels repeat n's operator runs on (no counterpart in the reference, whose _proj_apply
@@ -261,7 +279,8 @@ int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
  * info[0..2] = caller's voxel axis behind canonical axis 0..2, info[3] = bit j set where canonical axis
  * j is reversed, info[4] = 1 if the LDS-window pull serves it, info[5] = 0 if the schedule-driven
  * splat does not serve it, else 2 + its conv_up axis (1: grid-space source, 2..4: along x / y / z, 5: all), info[6] bit 0 = the translation-only one-kernel
- * matvec serves it, bit 1 = the single-pass AtA kernel of the denoising regime does (ata1.hip), info[7] = 1 if the convolutions run as separable passes. */
+ * matvec serves it, bit 1 = the single-pass AtA kernel of the denoising regime does (ata1.hip), bit 2 = the repeat is masked (unires_plan_set_missing:
+ * bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
 int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int32_t info[8]);
 /* The relabelling a plan applies to an operator with grid -> output affine M (host arithmetic only, no device
  * call): perm[j] = caller's voxel axis behind canonical axis j, flip[j] = 1 where it is reversed, chosen so that

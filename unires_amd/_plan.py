@@ -77,6 +77,8 @@ class ChannelPlan:
         self._h = C.c_void_p()
         self._concurrency = 1
         self.diff = 'forward'
+        self._missing = [None] * len(repeats)  # per repeat: (weak reference, version) of the tensor its mask was built from, or None
+        self.mask_zeros = False  # the setting the plan was last fetched with (_project._channel_plan)
         check(self.lib.unires_plan_create(C.byref(self._h), i3(self.dim_y), f3(vx_y), self.regime,
                                           len(repeats), arr, fov_tol))
         self.dims_x = [self.dim_y if self.regime == REGIME_IDENTITY else tuple(po.dim_x)
@@ -107,14 +109,15 @@ class ChannelPlan:
 
     def repeat_info(self, n):
         """Which kernels repeat n runs on and how its voxel axes were relabelled
-        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused);
-        ``fused``: the single-pass AtA kernel (denoising regime, ata1.hip) serves the CG matvec."""
+        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused, masked);
+        ``fused``: the single-pass AtA kernel (denoising regime, ata1.hip) serves the CG matvec; ``masked``: the
+        repeat has a validity mask (:meth:`set_missing`) - ``shift`` and ``fused`` are then False."""
         info = (C.c_int32 * 8)()
         check(self.lib.unires_plan_repeat_info(self._h, int(n), info))
         v = list(info)
         return dict(perm=tuple(v[:3]), flip=tuple((v[3] >> j) & 1 for j in range(3)), pull2=bool(v[4]),
                     splat2_axis=None if v[5] == 0 else v[5] - 2, shift=bool(v[6] & 1), separable=bool(v[7]),
-                    fused=bool(v[6] & 2))
+                    fused=bool(v[6] & 2), masked=bool(v[6] & 4))
 
     @on_device
     def time_matvecs(self, on=True):
@@ -143,6 +146,39 @@ class ChannelPlan:
         keep = []
         r = _repeat_desc(po, tau, self.method, self.regime, keep)
         check(self.lib.unires_plan_set_repeat(self._h, n, C.byref(r)))
+
+    @on_device
+    def set_missing(self, n, dat):
+        """Voxels of repeat n's observation ``dat`` that are exactly 0 are missing data (``unires_plan_set_missing``):
+        the plan's AtA_n becomes A_n^T diag(dat != 0) A_n in the matvec, the CG solves and the preconditioners; A, At
+        and the right-hand side are unchanged.  ``dat=None`` clears the mask.  Call again when the values of the
+        observation change; a change drops the captured solve and the built preconditioner."""
+        import weakref
+        self._missing[n] = None
+        if dat is None:
+            check(self.lib.unires_plan_set_missing(self._h, int(n), None, _stream()))
+            return
+        d = _vol(dat, 'x')[0]
+        if tuple(d.shape) != tuple(self.dims_x[n]):
+            raise ValueError('unires_amd: observation shape mismatch')
+        check(self.lib.unires_plan_set_missing(self._h, int(n), _ptr(d), _stream()))
+        self._missing[n] = (weakref.ref(dat), dat._version)
+
+    def sync_missing(self, x_dats):
+        """:meth:`set_missing` for every repeat whose observation is not the tensor, at the version, its mask was
+        built from (the key of :meth:`rhs_cached`: the tensor OBJECT and its version counter); ``x_dats=None``
+        clears every mask.  Free when nothing changed.  The masks are built on the current stream: a caller that
+        uses the plan on another stream orders that stream after this call (``_update_y`` fetches its plans before it
+        records the event its channel streams wait for)."""
+        for n in range(self.n_repeats):
+            if x_dats is None:
+                if self._missing[n] is not None:
+                    self.set_missing(n, None)
+                continue
+            t, key = x_dats[n], self._missing[n]
+            if key is not None and key[0]() is t and key[1] == t._version:
+                continue
+            self.set_missing(n, t)
 
     def set_concurrency(self, n):
         """Tell the plan that ``n`` solves run on the device at once (the channels of a y-update on streams of their

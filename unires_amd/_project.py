@@ -137,8 +137,44 @@ def _proj_apply(operator, dat, po, method='super-resolution', bound='zero',
     return _ops.push_affine(_ops.pull_affine(dat, M, dim_g), M, po.dim_y)
 
 
-def _plan_signature(x, y, method, do):
-    sig = [method, bool(do), tuple(y.dim)]
+def _plan_regime(method, do, mask_zeros=False):
+    """(method, do) a channel's plan is built with.  The user's, but for regime A = I (``do`` false) under
+    ``sett.mask_zeros``: that regime's matvec is the flat stencil alone and has no x-space intermediate to mask, so
+    the plan is built in the denoising regime with the identity affine and runs pull -> mask -> push."""
+    if method not in ('denoising', 'super-resolution'):
+        raise ValueError('Undefined method')
+    if mask_zeros and not do:
+        return 'denoising', True
+    return method, bool(do)
+
+
+_IDENTITY_PO = {}
+
+
+def _identity_po(y):
+    """The descriptor of an observation on the output's own grid: A = I as a denoising-regime operator (one per
+    output shape, kept)."""
+    dim = tuple(int(d) for d in y.dim)
+    po = _IDENTITY_PO.get(dim)
+    if po is None:
+        po = _IDENTITY_PO[dim] = _proj_op()
+        po.mat_y = po.mat_x = po.rigid = torch.eye(4, dtype=_F64)
+        po.dim_x = po.dim_y = dim
+    return po
+
+
+def _plan_repeats(x, y, do, mask_zeros):
+    """(po, tau) per repeat, as the plan takes them (``_plan_regime``)."""
+    if mask_zeros and not do:
+        po = _identity_po(y)
+        return [(po, xn.tau) for xn in x]
+    return [(xn.po, xn.tau) for xn in x]
+
+
+def _plan_signature(x, y, method, do, mask_zeros=False):
+    """What identifies a cached plan.  The setting is part of it where it decides the plan's regime (A = I); a plan
+    with projection serves both values, its masks set or cleared in place."""
+    sig = [method, (bool(do), bool(mask_zeros) and not do), tuple(y.dim)]
     for xn in x:
         po = xn.po
         if do:
@@ -152,18 +188,28 @@ def _plan_signature(x, y, method, do):
     return tuple(sig)
 
 
-def _channel_plan(x, y, method, do, vx_y=None, diff=None):
+def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None):
     """Fused per-channel plan, cached on the output struct and rebuilt when any
     operator parameter (rigid, scl, tau, dims) changed.  ``diff``: the difference of the plan's D
-    ('forward' | 'backward' | 'central'); None leaves the plan's as it is (callers that do not involve D)."""
-    plan = _channel_plan_any(x, y, method, do, vx_y)
+    ('forward' | 'backward' | 'central'); None leaves the plan's as it is (callers that do not involve D).
+    ``mask_zeros``: ``sett.mask_zeros`` - the plan's A^T A treats the zero voxels of each observation as missing
+    (``ChannelPlan.set_missing``; the masks follow the observation tensors and their versions); None leaves the plan
+    as it is (callers that apply A or A^T only, which no mask changes)."""
+    cached = getattr(y, '_plan', None)
+    if mask_zeros is None:
+        mask_zeros = cached[1].mask_zeros if cached is not None else False
+    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros))
     if diff is not None:
         plan.set_diff(diff)
+    plan.sync_missing([xn.dat for xn in x] if mask_zeros else None)
+    plan.mask_zeros = bool(mask_zeros)
     return plan
 
 
-def _channel_plan_any(x, y, method, do, vx_y=None):
-    sig = _plan_signature(x, y, method, do)
+def _channel_plan_any(x, y, method, do, vx_y=None, mask_zeros=False):
+    sig = _plan_signature(x, y, method, do, mask_zeros)
+    repeats = _plan_repeats(x, y, do, mask_zeros)
+    method, do = _plan_regime(method, do, mask_zeros)
     cached = getattr(y, '_plan', None)
     if cached is not None and cached[0] == sig:
         return cached[1]
@@ -174,8 +220,8 @@ def _channel_plan_any(x, y, method, do, vx_y=None):
         try:
             for n, (old, new) in enumerate(zip(cached[0][3:], sig[3:])):
                 if old != new:
-                    plan.set_repeat(n, x[n].po, x[n].tau)
-            plan.dims_x = [tuple(xn.po.dim_x) for xn in x] if do else plan.dims_x
+                    plan.set_repeat(n, *repeats[n])
+            plan.dims_x = [tuple(po.dim_x) for po, _ in repeats] if do else plan.dims_x
             plan._atx = None  # cached sum tau At x belongs to the old operator
             y._plan = (sig, plan)
             return plan
@@ -188,7 +234,7 @@ def _channel_plan_any(x, y, method, do, vx_y=None):
     if vx_y is None:
         vx_y = voxel_size(y.mat)
     vx = [float(v) for v in torch.as_tensor(vx_y).detach().cpu().tolist()]
-    plan = ChannelPlan(y.dim, vx, [(xn.po, xn.tau) for xn in x], method, do, device=y.dat.device, diff=old_diff)
+    plan = ChannelPlan(y.dim, vx, repeats, method, do, device=y.dat.device, diff=old_diff)
     y._plan = (sig, plan)
     return plan
 
@@ -201,7 +247,9 @@ def _proj(operator, dat, x, y, method='super-resolution', do=True, rho=1, n=0, v
     _lib.diff_code(diff, 'diff')
     if bound != 'zero' or interpolation not in ('linear', 1):
         raise NotImplementedError("only bound='zero', linear are built")
-    plan = _channel_plan(x, y, method, do, vx_y, diff=diff if operator == 'AtA' else None)
+    # (the facade's AtA is the reference's, which has no mask; A and At take the plan as it is)
+    plan = _channel_plan(x, y, method, do, vx_y, diff=diff if operator == 'AtA' else None,
+                         mask_zeros=False if operator == 'AtA' else None)
     if operator == 'AtA':
         return plan.matvec(dat, float(rho), float(y.lam))
     if operator not in ('A', 'At'):

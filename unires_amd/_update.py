@@ -44,6 +44,12 @@ def _diff(sett):
     return diff
 
 
+def _mask_zeros(sett):
+    """sett.mask_zeros (False where the settings object has none): zero voxels of an observation are missing data in
+    the y-update's system, as they are in every other consumer of an observation."""
+    return bool(getattr(sett, 'mask_zeros', False))
+
+
 class _Precond:
     """Callable x -> x / M like the lambda unires/_update.py:100 returns; carries the plan
     that holds the device copy of M so cg() can run the preconditioned iteration on device."""
@@ -61,7 +67,8 @@ def _precond(x, y, rho, sett):
     M = tau AtA(1) + 2 rho lam^2 sum(1/vx^2) for one channel (x = x[c], y = y[c])."""
     if len(x) != 1:
         raise ValueError('CG pre-conditioning only supports one repeat per contrast.')
-    plan = _channel_plan(x, y, sett.method, sett.do_proj, voxel_size(y.mat).float(), diff=_diff(sett))
+    plan = _channel_plan(x, y, sett.method, sett.do_proj, voxel_size(y.mat).float(), diff=_diff(sett),
+                         mask_zeros=_mask_zeros(sett))
     M = torch.empty(tuple(y.dim), dtype=torch.float32, device=y.dat.device)
     plan.precond_build(float(rho), float(y.lam), mode='jacobi', out=M)
     return _Precond(plan, M, 'jacobi')
@@ -93,7 +100,8 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
     pre = getattr(sett, 'cgs_precond', 'none')
     if not concurrent:
         for c in range(C):
-            plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett))
+            plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett),
+                                 mask_zeros=_mask_zeros(sett))
             plan.set_concurrency(1)
             lam = float(y[c].lam)
             if getattr(sett, 'cache_atx', True) and not sync:
@@ -108,12 +116,16 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
                 info.append(res)
         return y
     main = torch.cuda.current_stream()
+    # the plans first: fetching one may enqueue work on the main stream (the masks of sett.mask_zeros are built there),
+    # and the channel streams wait for `ready` only
+    fetched = [_channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett),
+                             mask_zeros=_mask_zeros(sett)) for c in range(C)]
     ready = torch.cuda.Event()
     ready.record(main)
     streams = _side_streams(y[0].dat.device, C)
     plans, bs = [], []
     for c in range(C):
-        plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett))
+        plan = fetched[c]
         plan.set_concurrency(C)  # (its persistent kernels leave the other channels' kernels room on the CUs)
         lam = float(y[c].lam)
         b = tmp if c == 0 else plan.rhs_buffer(tmp)

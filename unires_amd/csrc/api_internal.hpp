@@ -18,6 +18,7 @@
 #include "cg.hpp"
 #include "fftpre.hpp"
 #include "fused.hpp"
+#include "mask.hpp"
 #include "orient.hpp"
 #include "pull2.hpp"
 #include "shift.hpp"
@@ -148,7 +149,20 @@ struct RepeatTables {
   F1Sched f1;       // denoising regime: schedule of the single-pass AtA kernel (ata1.hip)
 };
 
-struct Repeat : RepeatDesc, RepeatTables {};
+// sett.mask_zeros (unires_plan_set_missing): the validity mask of the repeat's observation, one byte per x-space voxel
+// (mask.hip).  mask_u is in the caller's layout and kept so that a new orientation (unires_plan_set_repeat) can be
+// served without the observation; mask_c, only where the plan relabels the observation, is its canonical-layout copy.
+// The allocations stay until the plan goes; `masked` says whether they count.
+struct RepeatMask {
+  bool masked = false;
+  uint8_t *mask_u = nullptr, *mask_c = nullptr;
+  size_t mask_cap = 0;  // entries of either allocation
+};
+
+struct Repeat : RepeatDesc, RepeatTables, RepeatMask {
+  // the mask in the layout the x-space intermediate of A^T A has
+  const uint8_t *mask() const { return oriented ? mask_c : mask_u; }
+};
 
 // --------------------------------------------------------------------------
 // one CG solve: what the caller asked for, what follows from it, and how it is enqueued.  The parameter of the

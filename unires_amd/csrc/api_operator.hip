@@ -60,11 +60,15 @@ static void forward(unires_plan *pl, const Repeat &R, const float *in, const Sca
 }
 
 // x-space intermediate of AtA: xbuf = S(2 scl) conv_down pull(in)  (regime 2) or
-// gbuf = pull(in) (regime 1); returns the push source that finishes the operator.
+// gbuf = pull(in) (regime 1); returns the push source that finishes the operator.  A masked repeat
+// (unires_plan_set_missing) has its intermediate materialised - fill_repeat gave it no hybrid form, so the branch
+// below that fuses conv_down with conv_up is not its - and zeroed where the observation is: A^T diag(m) A.  The mask
+// is 0 / 1 in observation space, where it commutes with the even / odd scaling S.
 static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, const int *done,
                            hipStream_t st) {
   if (pl->regime == UNIRES_REGIME_DENOISE) {
     forward(pl, R, in, kNoScaling, pl->gbuf, done, st);
+    if (R.masked) launch_mask_apply(pl->gbuf, R.mask(), R.dim_x.numel(), done, st);
     return push_src(R, pl->gbuf, false, 0.f);
   }
   // S(2 scl) once between conv and conv^T  (unires/_project.py:175-177)
@@ -75,7 +79,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
   // grid-source splat) or x- and y-complete (hybrid: the z-profile splat takes it as it is)
   const bool fwd_only = R.hybf && !R.hyb && R.sep && !(R.sched.valid && R.sched.axis >= 0);
   const bool both = R.hyb && R.sched.valid && R.sched.axis == 2 && R.Tf.s[1] == 2;
-  if (push_mode() == PushMode::kDefault && (fwd_only || both) && pl->gbuf2 && R.pplan.valid && R.Tf.s[0] == 2 &&
+  if (!R.masked && push_mode() == PushMode::kDefault && (fwd_only || both) && pl->gbuf2 && R.pplan.valid && R.Tf.s[0] == 2 &&
       !(R.Tf.n[0] == 1)) {
     // (x taps = Dirac for what follows the x pair; y taps too where conv_up_y went in)
     Taps Ty = R.Txy;
@@ -115,6 +119,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
     }
   }
   forward(pl, R, in, S2, pl->xbuf, done, st);
+  if (R.masked) launch_mask_apply(pl->xbuf, R.mask(), R.dim_x.numel(), done, st);
   return push_src(R, pl->xbuf, true, 0.f);
 }
 
@@ -191,12 +196,12 @@ static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, floa
 }
 
 // out (+)= alpha AtA_n(in) [+ epilogue]: pull, push, stencil and dot in ONE pass over `in` where the plan has it
-// (denoising regime, ata1.hip), else forward + push.  `share`: the persistent kernels' grids leave room for the
+// (denoising regime, ata1.hip; not a masked repeat, whose intermediate has to exist), else forward + push.  `share`: the persistent kernels' grids leave room for the
 // other channels' solves (unires_plan_set_concurrency).  Returns the number of partials written.
 static int ata_apply(unires_plan *pl, const Repeat &R, const float *in, float alpha, PushEpilogue ep, bool share,
                      float *out, const int *done, hipStream_t st) {
   ep.grid_cap = share ? pl->cap_f1 : 0;
-  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !launch_ata1(R.f1, in, R.Af, alpha, ep, out, pl->dy, done, st))
+  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !R.masked && !launch_ata1(R.f1, in, R.Af, alpha, ep, out, pl->dy, done, st))
     return ep.partials ? ata1_blocks(pl->dy, ep.grid_cap) : 0;
   ep.grid_cap = share ? pl->cap_s2 : 0;
   const PushSrc src = ata_forward(pl, R, in, done, st);
@@ -282,8 +287,8 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
   const size_t nrep = pl->reps.size();
   // the one-kernel forms of a one-repeat plan: the partials written, or -1 where none applies
   const auto one_kernel = [&]() -> int {
-    if (nrep != 1 || no_aligned()) return -1;
     const Repeat &R = pl->reps[0];
+    if (nrep != 1 || no_aligned() || R.masked) return -1;  // (masked: no intermediate to multiply in one kernel)
     // translated by a fraction of a voxel (no rotation): the factorised one-kernel matvec.  Where the x-marching
     // kernel's fast form applies it serves integer shifts too (31.5 us against k_ata_aligned4x2's 36 - 37 at 256^3)
     // and is tried first

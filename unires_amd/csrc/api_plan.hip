@@ -171,7 +171,39 @@ static void trim_taps(const Taps &T, const Affine &A, const Dim3i &gd, Taps &Tt,
   gdt = Dim3i{g[0], g[1], g[2]};
 }
 
-static int fill_repeat(const unires_plan *pl, const unires_repeat_t *in, RepeatDesc &out) {
+// Which family of kernels the trimmed taps select: separable passes, the hybrid forms.  A masked repeat
+// (unires_plan_set_missing) takes no hybrid form - what UNIRES_NO_HYBRID selects: its A^T A multiplies a materialised
+// x-space intermediate, which the forms that run conv_down and conv_up as one kernel never have.
+static void choose_family(const unires_plan *pl, RepeatDesc &out, bool masked) {
+  // many taps (e.g. a Gaussian in-plane profile on top of the slice profile): the fused kernels'
+  // direct 3-D sum (prod n_d taps per output, fan-in^3 gathers per grid voxel) loses to one
+  // 1-D pass per axis through grid-space scratch
+  out.sep = (long long)out.Tf.n[0] * out.Tf.n[1] * out.Tf.n[2] > 64;
+  for (int d = 0; d < 3; ++d)
+    if (fan_in(out.Tf, d) > 2) out.sep = true;
+  out.sep0 = out.sep;
+  out.hyb = out.hybf = false;
+  if (pl->regime == UNIRES_REGIME_SUPERRES) {
+    static const bool env_no_hyb = getenv("UNIRES_NO_HYBRID") != nullptr;
+    const bool no_hyb = env_no_hyb || masked;
+    const bool xy = !is_dirac(out.Tf, 0) || !is_dirac(out.Tf, 1);
+    const bool z_ok = fan_in(out.Tf, 2) <= 2 && out.dim_x.z >= 2;
+    int nconv = 0;
+    for (int d = 0; d < 3; ++d) nconv += !is_dirac(out.Tf, d);
+    const bool both = !no_hyb && xy && nconv > 1 && z_ok;
+    const bool fwd_only = !no_hyb && !both && out.sep && xy && !is_dirac(out.Tf, 2) && out.dim_x.z >= 2;
+    if (both || fwd_only) {
+      out.hyb = both, out.hybf = fwd_only;
+      if (both) out.sep = false;
+      out.Tz = out.Tf, out.Txy = out.Tf;
+      set_dirac(out.Tz, 0), set_dirac(out.Tz, 1);
+      set_dirac(out.Txy, 2);
+      out.dim_h = Dim3i{out.dim_gf.x, out.dim_gf.y, out.dim_x.z};
+    }
+  }
+}
+
+static int fill_repeat(const unires_plan *pl, const unires_repeat_t *in, RepeatDesc &out, bool masked = false) {
   if (!in) return fail(UNIRES_ERR_NULL, "null repeat descriptor");
   if (!(in->tau > 0.f)) return fail(UNIRES_ERR_ARG, "tau must be positive");
   out = RepeatDesc();
@@ -203,31 +235,7 @@ static int fill_repeat(const unires_plan *pl, const unires_repeat_t *in, RepeatD
   out.dim_xu = out.dim_x;
   canonicalise(out);
   trim_taps(out.T, out.A, out.dim_g, out.Tf, out.Af, out.dim_gf);
-  // many taps (e.g. a Gaussian in-plane profile on top of the slice profile): the fused kernels'
-  // direct 3-D sum (prod n_d taps per output, fan-in^3 gathers per grid voxel) loses to one
-  // 1-D pass per axis through grid-space scratch
-  out.sep = (long long)out.Tf.n[0] * out.Tf.n[1] * out.Tf.n[2] > 64;
-  for (int d = 0; d < 3; ++d)
-    if (fan_in(out.Tf, d) > 2) out.sep = true;
-  out.sep0 = out.sep;
-  out.hyb = out.hybf = false;
-  if (pl->regime == UNIRES_REGIME_SUPERRES) {
-    static const bool no_hyb = getenv("UNIRES_NO_HYBRID") != nullptr;
-    const bool xy = !is_dirac(out.Tf, 0) || !is_dirac(out.Tf, 1);
-    const bool z_ok = fan_in(out.Tf, 2) <= 2 && out.dim_x.z >= 2;
-    int nconv = 0;
-    for (int d = 0; d < 3; ++d) nconv += !is_dirac(out.Tf, d);
-    const bool both = !no_hyb && xy && nconv > 1 && z_ok;
-    const bool fwd_only = !no_hyb && !both && out.sep && xy && !is_dirac(out.Tf, 2) && out.dim_x.z >= 2;
-    if (both || fwd_only) {
-      out.hyb = both, out.hybf = fwd_only;
-      if (both) out.sep = false;
-      out.Tz = out.Tf, out.Txy = out.Tf;
-      set_dirac(out.Tz, 0), set_dirac(out.Tz, 1);
-      set_dirac(out.Txy, 2);
-      out.dim_h = Dim3i{out.dim_gf.x, out.dim_gf.y, out.dim_x.z};
-    }
-  }
+  choose_family(pl, out, masked);
   if (!invert_affine(out.Af, out.Afinv)) return fail(UNIRES_ERR_ARG, "singular affine");
   splat_safety(out.Af, out.safe.row_sep, out.safe.use_atomics);
   return UNIRES_OK;
@@ -382,6 +390,24 @@ static void free_tables(RepeatTables &R) {
   R.ctab_n = R.ctab_cap = 0;
 }
 
+static void free_mask(RepeatMask &R) {
+  if (R.mask_u) (void)hipFree(R.mask_u);
+  if (R.mask_c) (void)hipFree(R.mask_c);
+  R.mask_u = R.mask_c = nullptr;
+  R.mask_cap = 0, R.masked = false;
+}
+
+// the canonical-layout copy of a masked, relabelled repeat's mask, for the orientation the repeat has now
+static int canonical_mask(Repeat &R, hipStream_t st) {
+  if (!R.masked || !R.oriented) return UNIRES_OK;
+  if (!R.mask_c && hipMalloc((void **)&R.mask_c, R.mask_cap) != hipSuccess) {
+    R.mask_c = nullptr;
+    return fail(UNIRES_ERR_ALLOC, "hipMalloc mask");
+  }
+  launch_mask_permute(R.mask_u, R.orient, R.dim_xu, R.mask_c, st);
+  return UNIRES_OK;
+}
+
 // --------------------------------------------------------------------------
 // entry points
 // --------------------------------------------------------------------------
@@ -471,7 +497,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->last_use) (void)hipEventDestroy(plan->last_use);
   drop_timing(plan);
   fftpre_destroy(plan->fft);
-  for (Repeat &R : plan->reps) free_tables(R);
+  for (Repeat &R : plan->reps) free_tables(R), free_mask(R);
   delete plan;
   return UNIRES_OK;
 }
@@ -535,8 +561,10 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   if (!plan || !repeat) return fail(UNIRES_ERR_NULL, "null argument");
   if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
   RepeatDesc tmp;
-  int rc = fill_repeat(plan, repeat, tmp);
+  int rc = fill_repeat(plan, repeat, tmp, plan->reps[n].masked);  // (a masked repeat stays masked: no hybrid form)
   if (rc) return rc;
+  if (plan->reps[n].masked && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
+    return fail(UNIRES_ERR_DIM, "a masked repeat keeps its observation's dims (clear the mask first)");
   if (plan->regime != UNIRES_REGIME_IDENTITY &&
       (tmp.dim_g.numel() > plan->cap_g || tmp.dim_x.numel() > plan->cap_x))
     return fail(UNIRES_ERR_DIM, "new repeat exceeds the plan's workspace");
@@ -571,7 +599,81 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   sched_set_thorough(false);  // (an operator changing under a running reconstruction: the quick schedule builds)
   rc = build_repeat_kernels(plan, R);
   sched_set_thorough(true);
+  // the mask stays (same observation, same dims); its canonical copy follows a new orientation - on the NULL stream
+  // and waited for, like the tables above
+  if (!rc && R.masked && R.oriented) {
+    rc = canonical_mask(R, nullptr);
+    if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
+  }
   return rc;
+}
+
+// The family of kernels and the tables of a repeat whose `masked` flag changed (choose_family): rebuilt where the family
+// differs, as unires_plan_set_repeat rebuilds them, but with the thorough schedule builds of unires_plan_create - a mask
+// is set once per observation, and a masked repeat then has the tables of a plan created without hybrid forms.
+static int refamily(unires_plan *pl, Repeat &R) {
+  const bool hyb = R.hyb, hybf = R.hybf, sep = R.sep;
+  choose_family(pl, R, R.masked);
+  // (a hybrid repeat whose kernels had turned out unavailable was rebuilt by build_repeat_kernels as what it is
+  // chosen as now: rebuilding it once more is correct, only not needed)
+  if (hyb == R.hyb && hybf == R.hybf && sep == R.sep) return UNIRES_OK;
+  R.ctab_n = 0;  // (no conv_up table of the new family yet)
+  return build_repeat_kernels(pl, R);
+}
+
+// sett.mask_zeros: voxels of repeat n's observation that are exactly 0 are missing data.  The plan keeps
+// m(v) = [x(v) != 0] and its A^T A becomes A^T diag(m) A - in the CG matvec, in the Jacobi diagonal and in the mean
+// diagonal the FFT preconditioner's symbol is built around, all of which go through ata_forward (api_operator.hip).
+// A and A^T do not change.  Setting or clearing a mask changes which kernels the repeat runs on (choose_family; the
+// one-kernel forms are skipped in api_operator.hip), so the tables are rebuilt where the family changed; the captured
+// solves and the built preconditioner go, like set_diff's.
+extern "C" int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const float *x, void *stream) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null plan");
+  if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
+  if (plan->regime == UNIRES_REGIME_IDENTITY)
+    return fail(UNIRES_ERR_UNSUPPORTED,
+                "regime A = I has no x-space intermediate to mask: build the plan in the denoising regime with the "
+                "identity affine");
+  Repeat &R = plan->reps[n];
+  if (!x && !R.masked) return UNIRES_OK;
+  hipStream_t st = (hipStream_t)stream;
+  await_use(plan);  // (the mask is rewritten: earlier launches may still read it)
+  drop_cg_graph(plan);
+  plan->prec_ready = false;
+  const bool was = R.masked;
+  if (x) {
+    // every allocation first: a failure leaves the repeat as it was
+    const size_t nx = R.dim_xu.numel();
+    if (R.mask_cap < nx) {
+      free_mask(R);
+      if (was) (void)refamily(plan, R);  // (the old mask is gone with its allocation)
+      if (hipMalloc((void **)&R.mask_u, nx) != hipSuccess) {
+        R.mask_u = nullptr;
+        return fail(UNIRES_ERR_ALLOC, "hipMalloc mask");
+      }
+      R.mask_cap = nx;
+    }
+    if (R.oriented && !R.mask_c && hipMalloc((void **)&R.mask_c, R.mask_cap) != hipSuccess) {
+      R.mask_c = nullptr;
+      return fail(UNIRES_ERR_ALLOC, "hipMalloc mask");
+    }
+    mark_use(plan, st);
+    launch_mask_build(x, Orient(), R.dim_xu, R.mask_u, st);
+    R.masked = true;
+    (void)canonical_mask(R, st);  // (its buffer exists: nothing left to fail)
+  } else {
+    R.masked = false;
+  }
+  if (was != R.masked) {
+    if (int rc = refamily(plan, R)) {
+      // the tables of the new family could not be built: back to the state before the call
+      R.masked = was;
+      (void)refamily(plan, R);
+      return rc;
+    }
+  }
+  CHECK_LAUNCH();
+  return UNIRES_OK;
 }
 
 // How many solves of OTHER plans the caller keeps in flight next to this one's (the channels of a y-update, each
@@ -638,7 +740,8 @@ extern "C" int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int
   info[3] = id ? 0 : (R.orient.flip[0] | (R.orient.flip[1] << 1) | (R.orient.flip[2] << 2));
   info[4] = R.pplan.valid ? 1 : 0;
   info[5] = R.sched.valid ? 2 + R.sched.axis : 0;
-  info[6] = (R.shift.valid ? 1 : 0) | (R.f1.valid ? 2 : 0);
+  // (the forms the matvec takes: a masked repeat skips the one-kernel matvec and the single-pass AtA kernel)
+  info[6] = (R.shift.valid && !R.masked ? 1 : 0) | (R.f1.valid && !R.masked ? 2 : 0) | (R.masked ? 4 : 0);
   info[7] = R.sep ? 1 : 0;
   return UNIRES_OK;
 }

@@ -73,6 +73,11 @@ class settings:
         self.device = 'cuda'
         self.diff = 'forward'
         self.do_proj = None
+        # build-side knob: voxels of an observation that are exactly 0 are missing data in the y-update's system too
+        # (they already are in the likelihood, the scaling and rigid updates, the noise estimate and the initial
+        # guess): the solve minimises the data term _compute_nll reports (ChannelPlan.set_missing).  Off: the
+        # reference's system, which pulls the reconstruction towards 0 wherever an observation is zero-filled.
+        self.mask_zeros = False
         self.gap = 0.0
         self.interpolation = 'linear'
         self.method = None
