@@ -32,6 +32,9 @@ CASES = {
     # x-space z extent a multiple of 4: the 16-byte 1-D passes, and the fused x-y pass of the hybrid path
     'sr_iso2_z8': dict(dim_y=(18, 14, 16), n_channels=2, thick=2, regime='sr', iso=True, scl=0.1),
     'sr_iso3_z8': dict(dim_y=(15, 18, 24), n_channels=1, thick=3, regime='sr', iso=True, rot=0.02),
+    # ... and a many-tap profile at ratio 3 there (no marching or wave-shift form takes stride 3): the 16-byte gather passes
+    # along x and y and the LDS-staged conv_up along z (k_conv1d_down<float4>, k_conv1d_up<float4>, k_conv1d_up_z)
+    'sr_iso3_gauss_z8': dict(dim_y=(15, 18, 24), n_channels=1, thick=3, regime='sr', iso=True, prof_ip=2),
     # 6 mm slices along z, 11 and 21 of them: the window pull takes 11 conv windows per chunk instead of
     # the 10 its 64 lanes hold (one chunk instead of two, two instead of three) and samples the three grid
     # points per row beyond the lanes in a pass of their own

@@ -14,9 +14,11 @@
 
 #include "admm.hpp"
 #include "api_internal.hpp"
+#include "conv.hpp"
 #include "coreg.hpp"
 #include "noise.hpp"
-#include "ops.hpp"
+#include "pull.hpp"
+#include "stencil.hpp"
 
 using namespace unires;
 

@@ -68,20 +68,12 @@ int check_conv_dims(const Dim3i &hi, const Dim3i &lo, const Taps &T);  // hi = (
 bool invert_affine(const Affine &A, Affine &out);  // row-major 3x4 float32, computed in double
 
 // --------------------------------------------------------------------------
-// taps and scaling
+// scaling (kNoScaling, is_dirac, set_dirac, fan_in: common.hpp)
 // --------------------------------------------------------------------------
-constexpr Scaling kNoScaling{1.f, 1.f, -1};
-
 inline Scaling make_scaling(float scl, int dim) {
   if (scl == 0.f) return kNoScaling;
   return Scaling{expf(scl), expf(-scl), dim};
 }
-
-// axis d has a Dirac profile: one tap of 1, stride 1 (conv_down / conv_up along it are the identity)
-inline bool is_dirac(const Taps &T, int d) { return T.n[d] == 1 && T.s[d] == 1 && T.t[d][0] == 1.f; }
-inline void set_dirac(Taps &T, int d) { T.n[d] = T.s[d] = 1, T.t[d][0] = 1.f; }
-// x-space voxels a grid voxel of axis d contributes to (what the fused push kernels tabulate up to 2 of)
-inline int fan_in(const Taps &T, int d) { return (T.n[d] + T.s[d] - 1) / T.s[d]; }
 
 // UNIRES_PUSH, read once per process.  Unset: the schedule-driven splat (k_splat2) and ata_forward's one-kernel
 // x / y forms, then the general kernels where an operator is outside their domain.  "tile": the general tile kernel

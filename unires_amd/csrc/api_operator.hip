@@ -4,7 +4,8 @@
 // its tables (api_plan.hip); nothing here builds or frees anything.
 #include "aligned.hpp"
 #include "api_internal.hpp"
-#include "ops.hpp"
+#include "conv.hpp"
+#include "pull.hpp"
 #include "stencil.hpp"
 
 using namespace unires;
@@ -74,7 +75,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
   // S(2 scl) once between conv and conv^T  (unires/_project.py:175-177)
   const Scaling S2 = make_scaling(2.f * R.scl, R.dim_thick);
   // A^T A with stride-2 profiles along x and y: the x-space volume is only a way station, so the passes on either
-  // side of it run as one kernel (ops.hip: k_conv_ydown_xdownup2, k_conv1d_downup2_m) and the push gets a crafted
+  // side of it run as one kernel (conv.hip: k_conv_ydown_xdownup2, k_conv1d_downup2_m) and the push gets a crafted
   // source - a volume that is x-complete (forward-only hybrid: conv_up_y and z follow as one kernel, then the
   // grid-source splat) or x- and y-complete (hybrid: the z-profile splat takes it as it is)
   const bool fwd_only = R.hybf && !R.hyb && R.sep && !(R.sched.valid && R.sched.axis >= 0);
@@ -100,7 +101,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
         if (both) set_dirac(src.T, 1);
         return src;
       }
-      if (both && R.Tf.n[0] * R.Tf.n[1] <= 16) {  // (the fused 2-D kernels of ops.hip serve these taps)
+      if (both && R.Tf.n[0] * R.Tf.n[1] <= 16) {  // (the fused 2-D kernels of conv.hip serve these taps)
         launch_conv_down_sep(pl->gbuf, R.dim_h, R.Txy, scaling_xy(S2), pl->xbuf, R.dim_x, pl->gbuf, pl->gbuf2, done, st);
         return push_src(R, pl->xbuf, true, 0.f);
       }

@@ -32,6 +32,20 @@ struct Scaling {  // _apply_scaling: even slices * e, odd slices * o along dim
   float e, o;
   int dim;  // -1: no scaling
 };
+constexpr Scaling kNoScaling{1.f, 1.f, -1};
+// even / odd slice factors along axis ax (1, 1 where S scales another axis or none)
+inline float even(const Scaling &S, int ax) { return S.dim == ax ? S.e : 1.f; }
+inline float odd(const Scaling &S, int ax) { return S.dim == ax ? S.o : 1.f; }
+
+// axis d has a Dirac profile: one tap of 1, stride 1 (conv_down / conv_up along it are the identity)
+inline bool is_dirac(const Taps &T, int d) { return T.n[d] == 1 && T.s[d] == 1 && T.t[d][0] == 1.f; }
+inline void set_dirac(Taps &T, int d) { T.n[d] = T.s[d] = 1, T.t[d][0] = 1.f; }
+// x-space voxels a grid voxel of axis d contributes to (what the fused push kernels tabulate up to 2 of)
+inline int fan_in(const Taps &T, int d) { return (T.n[d] + T.s[d] - 1) / T.s[d]; }
+
+// launch shape of the one-thread-per-voxel kernels: block (64,4,1) -> grid (ceil(Z/64), ceil(Y/4), X)
+inline dim3 vol_block() { return dim3(kWave, kBlock / kWave, 1); }
+inline dim3 vol_grid(const Dim3i &d) { return dim3((d.z + kWave - 1) / kWave, (d.y + 3) / 4, d.x); }
 
 // ---- wave / block reductions (float64) ----------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
