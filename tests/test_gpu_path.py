@@ -748,7 +748,7 @@ def test_one_kernel_conv_passes_are_bit_identical_to_the_separate_ones():
                            env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append([l for l in r.stdout.splitlines() if l.startswith('CONV ')])
-    assert len(outs[0]) == 8
+    assert len(outs[0]) == 10
     for o in outs[1:]:
         assert o == outs[0]
 

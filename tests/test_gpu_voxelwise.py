@@ -80,6 +80,77 @@ ax1_gdy509 0.237 / 386, ax1_gdy513 0.374 / 657, the sweep 0.111 - 0.376 / 0; the
 most instructions in one tile: 23 - 26 below 0.3 rad, 33 - 48 in the two-pass sweep cases.  No case failed: the
 suite found no kernel bug.
 
+The stride-2 conv passes across their block seams (``SEAM_CASES``; conv.hip).  With UNIRES_CONV_VERBOSE=1 the child
+reports on stderr which kernel each separable pass launched ([conv] lines, one per instantiation); a case's ``conv``
+entry names the kernels that must be among them, those that only A p on its own launches (the table with a non-forward
+D does not run it) and those that must not: a miss is drift, like ``expect``.  The kernels work in blocks and runs,
+read off conv.hip: k_conv_ydown_xdownup2<NY,NX,FX,FY> owns OWN = 32 x-space rows per y block (gy > 0, conv_up_y as
+well: 32 - (FY - 1)), 8 float4 = 32 x-space z per z block, and marches along x in runs of >= 6 x-space steps;
+k_conv_up_yz2 forms 32 grid rows per y block and takes x-space z <= 512; k_conv1d_up_z2 and k_conv_up_yz2 pass
+along z 61 lane pairs = 244 grid z at a time, three halo lanes moved by DPP shifts; the marching passes
+k_conv1d_down2_m / _up2_m / _downup2_m walk runs of 8 outputs / input steps; conv1d_grid gives the gather and z passes
+at most 48 workgroups along x, which loop over the x slabs.  The smaller cases above stay inside the first block of each.
+Here 26x70x72 (x space 13x35x36, grids 27 - 33 x 71 - 77 x 73 - 79) has two y blocks for every tap count, two z
+blocks (9 float4), three x runs (14 - 17 steps of 6), three y blocks of k_conv_up_yz2 and more than 8 marching steps
+along x and y; the long-z shapes cross the 244-voxel passes and stand either side of the 512 limit; 150x18x24 at
+ratio 3 (x space 50x6x8, grid 152x30x36) has more x slabs than workgroups along x.  With all ratios equal the thick
+axis is x: a Gaussian in-plane profile (prof_ip 2) lies along y and z, the through-plane profile (prof_tp; rect: 3
+taps kept, triangle 5, Gaussian 9 of 11) along x.  Every case is thick 2, iso (2, 2, 2), rot 0.1, trans 1.0 unless
+it says otherwise; the seeds are part of the cases (no voxel is excluded as a FOV tie with them, other seeds exclude
+up to half a volume: tests/test_voxelwise_comparator.py holds each case to the cap on the CPU).
+
+``tile``: where ``comb`` puts its deltas, per case the y-space images of the seams (x: 2 run, y: 2 OWN, z: 64 or
+the 244-voxel pass; 16 = 2 x 8 for the marching runs; 144 = 3 x 48 for the x slabs).  At spacing 21 an axis of 26,
+70 or 72 voxels holds two or three deltas: the combs of 26x70x72 land on x 0, 24 / 1, 25 (24: the second run's
+first plane), y 0, 35, 64 / 1, 35, 69 and z 0, 36, 64 / 1, 36, 71 - the first voxel past each seam, whose column
+reaches 10 voxels back across it; the long-z combs on z 0, 244, 516, 976, 1031 / 1, 243, 516, 975, 1031 (z 1032).
+Ratio 3 with the 15-tap Gaussian has a footprint of 33 along y and z: ``spacing`` (27, 33, 33) there.
+
+| case                  | kwargs (besides the above), seed, env      | seam it is there for; tile                | [conv] kernels observed on an MI355X                   |
+|-----------------------|--------------------------------------------|-------------------------------------------|--------------------------------------------------------|
+| sep2_gauss            | prof_ip 2, scl 0.05; seed 9                | k_conv_ydown_xdownup2, gy = 0: y, z       | k_conv_ydown_xdownup2<9,3,2,0>, k_conv_up_yz2<5>,      |
+|                       |                                            | blocks, x runs; k_conv_up_yz2 y blocks;   | k_conv1d_up2_m<2>; A p: k_conv1d_down2_m<9>, <3>       |
+|                       |                                            | (12, 64, 64)                              |                                                        |
+| sep2_gauss_noyx       | the same; UNIRES_CONV_YX=0                 | k_conv1d_downup2_m: runs, warm-up steps;  | k_conv1d_down2_m<9>, k_conv1d_downup2_m<3,2>,          |
+|                       |                                            | (16, 16, 64)                              | k_conv_up_yz2<5>, k_conv1d_up2_m<2>, ..down2_m<3>      |
+| sep2_gauss_march      | the same; UNIRES_CONV_YX=0,                | the three marching passes on their own,   | k_conv1d_down2_m<9>, <3>, k_conv1d_up2_m<2>, <5>,      |
+|                       | UNIRES_CONV_DOWNUP=0, UNIRES_UPYZ_LDS=0    | k_conv1d_up_z2; (16, 16, 64)              | k_conv1d_up_z2                                         |
+| sep2_gauss_tri        | prof_ip 2, prof_tp 1; seed 9               | the 5-tap instantiations beside the       | k_conv_ydown_xdownup2<9,5,3,0>, k_conv_up_yz2<5>,      |
+|                       |                                            | 9-tap ones; (12, 64, 64)                  | k_conv1d_up2_m<3>; A p: k_conv1d_down2_m<9>, <5>       |
+| sep2_allgauss         | prof_ip 2, prof_tp 2, scl 0.05; seed 9     | 9 taps on every axis; (12, 64, 64)        | k_conv_ydown_xdownup2<9,9,5,0>, k_conv_up_yz2<5>,      |
+|                       |                                            |                                           | k_conv1d_up2_m<5>; A p: k_conv1d_down2_m<9>            |
+| sep2_allgauss_nopull2 | the same; UNIRES_NO_PULL2=1                | conv_down along z as a pass of its own;   | k_conv_up_yz2<5>, k_conv1d_up2_m<5>; A p and A^T A:    |
+|                       |                                            | (16, 16, 64)                              | k_conv1d_down_z, k_conv1d_down2_m<9>                   |
+| sep2_rect             | scl 0.1; seed 11                           | the hybrid `both` branch, gy > 0: OWN =   | k_conv_ydown_xdownup2<3,3,2,2>,                        |
+|                       |                                            | 31, two y blocks; (12, 62, 64)            | k_conv2d_up_xy_v4_t<2,2,4>; A p: k_conv2d_down_xy_v4   |
+| sep2_rect_noxy        | the same; UNIRES_CONV_YX=0,                | the 3-tap marching passes instead;        | k_conv1d_down2_m<3>, k_conv1d_up2_m<2>                 |
+|                       | UNIRES_CONV_XY=0                           | (16, 16, 64)                              |                                                        |
+| sep2_tri              | prof_ip 1, prof_tp 1; seed 11              | 5 taps on every axis; (12, 64, 64)        | k_conv_ydown_xdownup2<5,5,3,0>, k_conv_up_yz2<3>,      |
+|                       |                                            |                                           | k_conv2d_up_xy_v4_t<3,3,2>, k_conv1d_up_z2; A p:       |
+|                       |                                            |                                           | k_conv1d_down2_m<5>                                    |
+| sep2_z256             | 24x20x256, prof_ip 2, prof_tp 2, angles    | k_conv1d_up_z2, grid z 263 > 244: a       | k_conv1d_up_z2, k_conv1d_up2_m<5>,                     |
+|                       | (0, 0, 0.04); seed 3; UNIRES_UPYZ_LDS=0    | second pass, its halo; (8, 4, 244)        | k_conv_ydown_xdownup2<9,9,5,0>; A p: ..down2_m<9>      |
+| sep2_z1024            | the same at 24x20x1024 (x-space z 512)     | k_conv_up_yz2 at the last z of its        | k_conv_up_yz2<5>, k_conv1d_up2_m<5>,                   |
+|                       |                                            | domain, five passes; (8, 4, 244)          | k_conv_ydown_xdownup2<9,9,5,0>; A p: ..down2_m<9>      |
+| sep2_z1032            | the same at 24x20x1032 (x-space z 516)     | past it: the two passes; (8, 4, 244)      | k_conv1d_up2_m<5>, k_conv1d_up_z2,                     |
+|                       |                                            |                                           | k_conv_ydown_xdownup2<9,9,5,0>; A p: ..down2_m<9>      |
+| sep3_x150             | 150x18x24, thick 3, iso (3, 3, 3), prof_ip | 50 / 152 x slabs on a grid.z of 48;       | k_conv1d_up<float4>, k_conv1d_up_z; A p and A^T A:     |
+|                       | 2, rot 0.05; seed 1                        | (144, 6, 12)                              | k_conv1d_down<float4>                                  |
+| sep3_x150_nopull2     | the same; UNIRES_NO_PULL2=1                | k_conv1d_down_z over 152 x slabs;         | the same and k_conv1d_down_z                           |
+|                       |                                            | (144, 6, 12)                              |                                                        |
+
+k_conv1d_down_z: a plan with profiles along x or y and along z takes conv_down along z into its window pull
+(k_pull_conv2 on R.Tz, the hybrid and the forward-only hybrid forms of api_plan.hip), so no geometry of these reaches the z pass
+while the window plan exists; it runs where pull2 declines (here: under UNIRES_NO_PULL2, which also
+closes the one-kernel A^T A forms: they start from the window pull).  sep2_allgauss therefore does not run it, and
+the two _nopull2 cases are there for it.
+
+Observed on an MI355X (largest err / tol over every check of the case; no voxel excluded in any of them): sep2_gauss,
+sep2_gauss_noyx, sep2_gauss_march 0.730 (A^T v; A^T A p 0.297 in all three), sep2_gauss_tri 0.683, sep2_allgauss
+0.656, sep2_allgauss_nopull2 0.656, sep2_rect, sep2_rect_noxy 0.404, sep2_tri 0.378, sep2_z256 0.115, sep2_z1024
+0.111, sep2_z1032 0.138, sep3_x150 0.203, sep3_x150_nopull2 0.203.  With a non-forward D: sep2_gauss q 0.026 / 0.050, b
+0.391 / 0.412; sep2_rect q 0.076 / 0.153, b 0.391 / 0.391.  No case failed: no kernel is wrong across a seam.
+
 The table with a non-forward D (``DIFF_CASES``, ``test_every_form_per_voxel_with_backward_and_central_differences``).
 A plan with sett.diff = 'backward' / 'central' composes its matvec differently (api_operator.hip, matvec):
 every AtA kernel runs without its stencil epilogue, and one pass - k_dtd_flat_w<W, ACC>, or k_dtd<W, ACC> where the
@@ -88,7 +159,8 @@ One child per case sets each difference in turn on the same plan and writes q wi
 side b (k_div<W>, then the accumulating A^T of every repeat) and the objectives of two one-iteration solves from
 x0 = p; the parent checks q per voxel against ref64.bound_matvec_reps, the dot against the float64 dot of the stored
 vectors, b per voxel against ref64.bound_rhs, and the objectives (``_check_diff``).  The cases are the forms above by
-name (z_thick and z_thick_conc3 at 41x38x61; no table limits, no sweep: those exercise the schedule) and:
+name (z_thick and z_thick_conc3 at 41x38x61; no table limits, no sweep: those exercise the schedule; of the seam cases
+sep2_gauss and sep2_rect: without the stencil epilogue the accumulating stores behind their passes change) and:
 
 | case               | geometry                                        | what it is there for                                |
 |--------------------|-------------------------------------------------|-----------------------------------------------------|
@@ -134,8 +206,12 @@ SENT = -7.75e37  # sentinel of the pads around an unaligned output
 NONFWD = ('backward', 'central')
 
 
-def _c(kw, env=None, conc=1, expect=None, light=False, seed=11, unaligned=False):
-    return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light, seed=seed, unaligned=unaligned)
+def _c(kw, env=None, conc=1, expect=None, light=False, seed=11, unaligned=False, conv=None, tile=None, spacing=None):
+    """``conv``: (kernels of conv.hip that must launch, those only A p alone launches, those that must not), by name
+    with or without template arguments; ``tile``: where ``comb`` puts its deltas (default: the splat tile);
+    ``spacing``: the y-space comb spacing where ``spacings`` is too narrow for the case's taps."""
+    return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light, seed=seed, unaligned=unaligned,
+                conv=conv, tile=tile, spacing=spacing)
 
 
 _Z = dict(dim_y=(41, 38, 61), thick=6, thick_axes=[2], rot=0.1, trans=2.0, scl=0.1)
@@ -199,6 +275,62 @@ CASES = {
                      expect=lambda i: i['splat2_axis'] is None),
 }
 
+# The stride-2 conv passes across their block seams (the table in the module docstring).  Seeds are part of the case:
+# with them the reference excludes no voxel as a FOV tie (tests/test_voxelwise_comparator.py holds them to that).
+_S2 = dict(dim_y=(26, 70, 72), thick=2, iso=(2, 2, 2), rot=0.1, trans=1.0)
+_S2G = dict(_S2, prof_ip=2, scl=0.05)
+_S2R = dict(_S2, scl=0.1)
+_S2Z = dict(dim_y=(24, 20, 256), thick=2, iso=(2, 2, 2), prof_ip=2, prof_tp=2, angles=(0, 0, 0.04), trans=1.0)
+_sep = lambda i: i['separable']
+_ONE_KERNEL = ['k_conv_ydown_xdownup2', 'k_conv1d_downup2_m', 'k_conv_up_yz2']
+SEAM_CASES = {
+    'sep2_gauss': _c(_S2G, seed=9, expect=_sep, tile=(12, 64, 64),
+                     conv=(['k_conv_ydown_xdownup2<9,3,2,0>', 'k_conv_up_yz2<5>', 'k_conv1d_up2_m<2>'],
+                           ['k_conv1d_down2_m<9>', 'k_conv1d_down2_m<3>'], ['k_conv1d_downup2_m'])),
+    'sep2_gauss_noyx': _c(_S2G, {'UNIRES_CONV_YX': '0'}, seed=9, expect=_sep, tile=(16, 16, 64),
+                          conv=(['k_conv1d_downup2_m<3,2>', 'k_conv1d_down2_m<9>', 'k_conv_up_yz2<5>'], [],
+                                ['k_conv_ydown_xdownup2'])),
+    'sep2_gauss_march': _c(_S2G, {'UNIRES_CONV_YX': '0', 'UNIRES_CONV_DOWNUP': '0', 'UNIRES_UPYZ_LDS': '0'}, seed=9,
+                           expect=_sep, tile=(16, 16, 64),
+                           conv=(['k_conv1d_down2_m<9>', 'k_conv1d_down2_m<3>', 'k_conv1d_up2_m<2>', 'k_conv1d_up2_m<5>',
+                                  'k_conv1d_up_z2'], [], _ONE_KERNEL)),
+    'sep2_gauss_tri': _c(dict(_S2, prof_ip=2, prof_tp=1), seed=9, expect=_sep, tile=(12, 64, 64),
+                         conv=(['k_conv_ydown_xdownup2<9,5,3,0>', 'k_conv1d_up2_m<3>', 'k_conv_up_yz2<5>'],
+                               ['k_conv1d_down2_m<5>', 'k_conv1d_down2_m<9>'], [])),
+    'sep2_allgauss': _c(dict(_S2G, prof_tp=2), seed=9, expect=_sep, tile=(12, 64, 64),
+                        conv=(['k_conv_ydown_xdownup2<9,9,5,0>', 'k_conv1d_up2_m<5>', 'k_conv_up_yz2<5>'],
+                              ['k_conv1d_down2_m<9>'], [])),
+    # (without a switch the z profile of such a plan rides in the window pull; k_conv1d_down_z runs where that declines)
+    'sep2_allgauss_nopull2': _c(dict(_S2G, prof_tp=2), {'UNIRES_NO_PULL2': '1'}, seed=9, tile=(16, 16, 64),
+                                expect=lambda i: i['separable'] and not i['pull2'],
+                                conv=(['k_conv_up_yz2<5>', 'k_conv1d_up2_m<5>'], ['k_conv1d_down_z', 'k_conv1d_down2_m<9>'],
+                                      ['k_conv_ydown_xdownup2', 'k_conv1d_downup2_m'])),
+    'sep2_rect': _c(_S2R, seed=11, expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable'],
+                    tile=(12, 62, 64),
+                    conv=(['k_conv_ydown_xdownup2<3,3,2,2>', 'k_conv2d_up_xy_v4_t<2,2,4>'], ['k_conv2d_down_xy_v4'], [])),
+    'sep2_rect_noxy': _c(_S2R, {'UNIRES_CONV_YX': '0', 'UNIRES_CONV_XY': '0'}, seed=11,
+                         expect=lambda i: i['pull2'] and i['splat2_axis'] == 2 and not i['separable'], tile=(16, 16, 64),
+                         conv=(['k_conv1d_down2_m<3>', 'k_conv1d_up2_m<2>'], [],
+                               ['k_conv_ydown_xdownup2', 'k_conv2d_down_xy_v4', 'k_conv2d_up_xy_v4_t'])),
+    'sep2_tri': _c(dict(_S2, prof_ip=1, prof_tp=1), seed=11, expect=_sep, tile=(12, 64, 64),
+                   conv=(['k_conv_ydown_xdownup2<5,5,3,0>', 'k_conv2d_up_xy_v4_t<3,3,2>'], ['k_conv1d_down2_m<5>'], [])),
+    'sep2_z256': _c(_S2Z, {'UNIRES_UPYZ_LDS': '0'}, seed=3, expect=_sep, tile=(8, 4, 244),
+                    conv=(['k_conv1d_up_z2', 'k_conv1d_up2_m<5>'], [], ['k_conv_up_yz2'])),
+    'sep2_z1024': _c(dict(_S2Z, dim_y=(24, 20, 1024)), seed=3, expect=_sep, tile=(8, 4, 244),
+                     conv=(['k_conv_up_yz2<5>'], [], [])),
+    'sep2_z1032': _c(dict(_S2Z, dim_y=(24, 20, 1032)), seed=3, expect=_sep, tile=(8, 4, 244),
+                     conv=(['k_conv1d_up2_m<5>', 'k_conv1d_up_z2'], [], ['k_conv_up_yz2'])),
+    'sep3_x150': _c(dict(dim_y=(150, 18, 24), thick=3, iso=(3, 3, 3), prof_ip=2, rot=0.05, trans=1.0), seed=1,
+                    expect=_sep, tile=(144, 6, 12), spacing=(27, 33, 33),
+                    conv=(['k_conv1d_up<float4>', 'k_conv1d_up_z'], ['k_conv1d_down<float4>'], [])),
+    'sep3_x150_nopull2': _c(dict(dim_y=(150, 18, 24), thick=3, iso=(3, 3, 3), prof_ip=2, rot=0.05, trans=1.0),
+                            {'UNIRES_NO_PULL2': '1'}, seed=1, expect=lambda i: i['separable'] and not i['pull2'],
+                            tile=(144, 6, 12), spacing=(27, 33, 33),
+                            conv=(['k_conv1d_up<float4>', 'k_conv1d_up_z'], ['k_conv1d_down_z', 'k_conv1d_down<float4>'],
+                                  [])),
+}
+CASES.update(SEAM_CASES)
+
 # The rotation sweep: the form each geometry runs at each angle, as observed on an MI355X: (pull2, splat2 axis,
 # k_ata1, schedule build).  Without any env switch: from 0.3 rad on, a tile overflows its 128-entry staging slot
 # and the schedule takes the two-pass build (up to 48 instructions per tile); at 0.7 rad a tile needs more than
@@ -239,7 +371,7 @@ DIFF_CASES = {
 }
 for _n in ('x_thick', 'y_thick', 'iso2_rect', 'iso2_rect_nohyb', 'iso2_gauss', 'denoise', 'denoise_noata1',
            'translate', 'translate_noshift', 'int_shift', 'int_shift_noalign', 'int_shift_z60', 'identity', 'orient_9',
-           'z_nosplat2', 'z_pushtile', 'z_nopull2', 'dn_nopull2'):
+           'z_nosplat2', 'z_pushtile', 'z_nopull2', 'dn_nopull2', 'sep2_gauss', 'sep2_rect'):
     DIFF_CASES[_n] = CASES[_n]
 DIFF_CASES.update({
     'z_aniso': _c(dict(_Z, aniso=_ANISO), expect=_z_form),
@@ -270,7 +402,7 @@ from tests.test_gpu_voxelwise import comb, inputs, spacings
 from oracle import nitorch_restated as N
 from unires_amd._project import _channel_plan
 kw, conc, light, out = %(kw)r, %(conc)r, %(light)r, sys.argv[1]
-seed, diffs, unaligned = %(seed)r, %(diffs)r, %(unaligned)r
+seed, diffs, unaligned, tile, spacing = %(seed)r, %(diffs)r, %(unaligned)r, %(tile)r, %(spacing)r
 if 'orient' in kw:
     kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
 prob = make_problem(seed=seed, **kw)
@@ -284,13 +416,13 @@ p, v = inputs(prob['dim_y'], plan.dims_x[0])
 res = dict(info=json.dumps(info))
 d = lambda t: t.to('cuda:0')
 if prob['do_proj'] and 'forward' in diffs:
-    sy, sx = spacings(kw)
+    sy, sx = spacings(kw, spacing)
     res['Ap'] = plan.proj_apply(0, 'A', d(p)).cpu().numpy()
     res['AtAp'] = plan.proj_apply(0, 'AtA', d(p)).cpu().numpy()
     if not light:
         res['Atv'] = plan.proj_apply(0, 'At', d(v)).cpu().numpy()
     for ph in (0, 1):
-        pc = comb(prob['dim_y'], TILE_Y, sy, ph)
+        pc = comb(prob['dim_y'], tile, sy, ph)
         res['AtA_comb%%d' %% ph] = plan.proj_apply(0, 'AtA', d(pc)).cpu().numpy()
         if not light:
             res['A_comb%%d' %% ph] = plan.proj_apply(0, 'A', d(pc)).cpu().numpy()
@@ -336,7 +468,7 @@ for which in diffs:
             res['x1_' + which] = x.cpu().numpy()
             res['q1_' + which] = plan.matvec(x, rho, lam).cpu().numpy()  # (stored: for the error in tied voxels)
 np.savez(out, **res)
-'''.replace('TILE_Y', repr(TILE)).replace('SENT', repr(SENT))
+'''.replace('SENT', repr(SENT))
 
 
 def inputs(dim_y, dim_x):
@@ -346,17 +478,18 @@ def inputs(dim_y, dim_x):
     return p, v
 
 
-def spacings(kw):
+def spacings(kw, spacing=None):
     """Comb spacing per axis, wider than the operator's footprint: y space 2 (3 r + 4) + 1 (A^T A reaches the
     conv taps (r + 3 at most for the rect profile, r + 3 + r for the Gaussian at ratio 2) plus a corner either
-    side, twice), x space 8 (rows of A whose y footprints overlap)."""
+    side, twice), x space 8 (rows of A whose y footprints overlap).  ``spacing``: the case's own y-space spacing, for
+    profiles with more taps (2 (taps + 1) + 1 of the taps the plan keeps: the Gaussian at ratio 3 has 15)."""
     r = [1, 1, 1]
     if kw.get('regime', 'sr') == 'sr':
         if kw.get('iso'):
             r = list(kw['iso'])
         else:
             r[kw['thick_axes'][0]] = kw['thick']
-    return tuple(2 * (3 * ri + 4) + 1 for ri in r), (8, 8, 8)
+    return tuple(spacing) if spacing else tuple(2 * (3 * ri + 4) + 1 for ri in r), (8, 8, 8)
 
 
 def comb(dim, tile, spacing, phase):
@@ -390,14 +523,28 @@ def _run_child(tmp_path, name, case, diffs=('forward',), timeout=300):
     env = dict(os.environ)
     env.update(case['env'])
     env['UNIRES_SPLAT2_VERBOSE'] = '1'
+    env['UNIRES_CONV_VERBOSE'] = '1'
     r = subprocess.run([sys.executable, '-c', _CHILD % dict(root=ROOT, kw=case['kw'], conc=case['conc'],
                                                             light=case['light'], seed=case['seed'],
-                                                            diffs=tuple(diffs), unaligned=case['unaligned']), path],
+                                                            diffs=tuple(diffs), unaligned=case['unaligned'],
+                                                            tile=case['tile'] or TILE, spacing=case['spacing']), path],
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])
     res = dict(np.load(path))
     builds = re.findall(r'\[splat2\].*build (\S+), max instructions per tile (\d+)', r.stderr)
-    return res, (builds[-1] if builds else None)
+    convs = set(re.findall(r'^\[conv\] (\S+)', r.stderr, re.M))
+    return res, (builds[-1] if builds else None), convs
+
+
+def conv_drift(case, convs, forward=True):
+    """The case's ``conv`` expectation against the [conv] names of its child: a list of (what, name) misses.  A name
+    without template arguments stands for every instantiation.  ``forward``: the child ran A p on its own."""
+    if case['conv'] is None:
+        return []
+    run, fwd, no = case['conv']
+    hit = lambda name: any(c == name or c.startswith(name + '<') for c in convs)
+    return ([('not run', n) for n in run + (fwd if forward else []) if not hit(n)] +
+            [('run', n) for n in no if hit(n)])
 
 
 def _check(name, case, res):
@@ -470,9 +617,9 @@ def _check(name, case, res):
         assert lhs <= float((tolA * v64.abs()).sum() + (tolAt * p64.abs()).sum()) + slack, (name, 'adjoint')
     # impulse combs against the plan's own taps (D = 0): columns of A and AtA, rows of A via At
     opt = ref64.Operator64(xc[0].po, prob['method'], trimmed=True, oriented=oriented)
-    sy, sx = spacings(case['kw'])
+    sy, sx = spacings(case['kw'], case['spacing'])
     for ph in (0, 1):
-        pc = comb(prob['dim_y'], TILE, sy, ph)
+        pc = comb(prob['dim_y'], case['tile'] or TILE, sy, ph)
         checks = [('AtA_comb%d' % ph, lambda: opt.bound_AtA(pc), myy)]
         if not case['light']:
             vc = comb(tuple(xc[0].po.dim_x), None, sx, ph)
@@ -488,7 +635,7 @@ def _check(name, case, res):
 def test_every_form_per_voxel_against_float64(tmp_path):
     drift = []
     for name, case in CASES.items():
-        res, build = _run_child(tmp_path, name, case)
+        res, build, convs = _run_child(tmp_path, name, case)
         info = json.loads(str(res['info']))
         info['perm'], info['flip'] = tuple(info['perm']), tuple(info['flip'])
         form = (info['pull2'], info['splat2_axis'], info['fused'], build[0] if build else None)
@@ -498,9 +645,11 @@ def test_every_form_per_voxel_against_float64(tmp_path):
             drift.append((name, build))
         if name in SWEEP_FORMS and SWEEP_FORMS[name] != form:
             drift.append((name, form, SWEEP_FORMS[name]))
+        if conv_drift(case, convs):
+            drift.append((name, conv_drift(case, convs), sorted(convs)))
         rep, excluded, R = _check(name, case, res)
-        print('%-20s %s build %s max err/tol %.3f excluded %d R %.0f'
-              % (name, info, build, max(rep.values()), excluded, R), flush=True)
+        print('%-20s %s build %s conv %s max err/tol %.3f excluded %d R %.0f'
+              % (name, info, build, ' '.join(sorted(convs)) or '-', max(rep.values()), excluded, R), flush=True)
     assert not drift, drift
 
 
@@ -640,7 +789,7 @@ def test_every_form_per_voxel_with_backward_and_central_differences(tmp_path, na
     assert not _DIFF_DEAD, ('an earlier case\'s child died: not started', _DIFF_DEAD)
     case = DIFF_CASES[name]
     try:
-        res, build = _run_child(tmp_path, name, case, diffs=NONFWD, timeout=120)
+        res, build, convs = _run_child(tmp_path, name, case, diffs=NONFWD, timeout=120)
     except (AssertionError, subprocess.TimeoutExpired) as e:
         _DIFF_DEAD.append((name, repr(e)[:300]))
         raise
@@ -650,9 +799,11 @@ def test_every_form_per_voxel_with_backward_and_central_differences(tmp_path, na
     if R['prob']['do_proj']:  # the bound's orientation is restated, and must be the plan's
         assert (info['perm'], info['flip']) == R['orient'][0], (name, info, R['orient'][0])
     rep, n_yy, n_y = _check_diff(name, case, res, R)
-    print('diff %-18s %s build %s max err/tol: %s; excluded %d (matvec) %d (rhs)'
-          % (name, info, build, ', '.join('%s %.3f' % kv for kv in rep.items()), n_yy, n_y), flush=True)
+    print('diff %-18s %s build %s conv %s max err/tol: %s; excluded %d (matvec) %d (rhs)'
+          % (name, info, build, ' '.join(sorted(convs)) or '-', ', '.join('%s %.3f' % kv for kv in rep.items()), n_yy,
+             n_y), flush=True)
     assert case['expect'] is None or case['expect'](info), (name, info)
+    assert not conv_drift(case, convs, forward=False), (name, conv_drift(case, convs, forward=False), sorted(convs))
     assert not (case.get('one_pass') and build is not None and build[0] != 'one-pass'), (name, build)
 
 

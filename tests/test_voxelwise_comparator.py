@@ -1,7 +1,9 @@
 """The per-voxel comparator of tests/ref64.py, checked on the CPU: it is sound (the float32 oracle, a correct
 float32 implementation of the same operator, passes it for A, At, AtA and the matvec) and sharp (one voxel off by
 10x its tolerance, one 8x4x30 tile off by 1e-3 and one non-zero value outside the operator's support all fail it,
-while the relative-L2 gates of the GPU parity tests pass the first two)."""
+while the relative-L2 gates of the GPU parity tests pass the first two; one x-space row at a block seam of the
+stride-2 conv kernels off by 1e-3 fails it too).  The cases of tests/test_gpu_voxelwise.py are held to their
+conditions here, on the reference alone: the tie cap, and a comb spacing wider than the footprint of their taps."""
 import pytest
 import torch
 
@@ -9,17 +11,21 @@ from oracle import nitorch_restated as N
 from oracle import unires_restated as O
 from tests import ref64
 from tests.helpers import make_problem, oracle_structs, rel_err
-from tests.test_gpu_voxelwise import DIFF_CASES, diff_reference, tie_cap_ok
+from tests.test_gpu_voxelwise import DIFF_CASES, SEAM_CASES, diff_reference, inputs, spacings, tie_cap_ok
 
 PROBLEMS = {
     'small_thick3': dict(dim_y=(16, 14, 12), thick=3, rot=0.1, trans=0.7),
     'mid_thick6z_scl': dict(dim_y=(41, 38, 61), thick=6, thick_axes=[2], rot=0.12, trans=2.0, scl=0.1),
     'mid_iso2_gauss': dict(dim_y=(34, 30, 36), thick=2, iso=(2, 2, 2), prof_ip=2, rot=0.1, trans=1.0),
     'mid_denoise': dict(dim_y=(33, 29, 40), regime='dn', rot=0.1, trans=2.0),
+    # (the sep2_gauss geometry of tests/test_gpu_voxelwise.py, with its seed: no voxel excluded)
+    'seam_sep2_gauss': dict(SEAM_CASES['sep2_gauss']['kw'], seed=SEAM_CASES['sep2_gauss']['seed']),
 }
 
 
 def _setup(kw, seed=3):
+    kw = dict(kw)
+    seed = kw.pop('seed', seed)
     prob = make_problem(seed=seed, **kw)
     xs, ys = oracle_structs(prob)
     xc, yc = xs[0], ys[0]
@@ -78,6 +84,40 @@ def test_comparator_catches_one_voxel_and_one_tile_that_l2_gates_pass():
     assert rel_err(bad, ref) < 1e-4
     r = ref64.compare(bad, ref, tol)
     assert not r['ok'] and r['n_bad'] > 100
+
+
+def test_comparator_catches_one_row_at_a_block_seam_that_the_l2_gate_passes():
+    """sep2_gauss of tests/test_gpu_voxelwise.py (x space 13 x 35 x 36): k_conv_ydown_xdownup2 owns x-space rows in
+    blocks of 32, so row 32 of the x-space intermediate is the first of its second y block.  That row's contribution
+    to A^T A p, scaled by 1 + 1e-3 before the conv_up half, fails the per-voxel bound - as the whole row and as the share
+    of it that one workgroup forms (x run 1: x-space planes 6 .. 11; z block 0: x-space z 0 .. 31).  The relative-L2
+    gate of the path tests (1e-4) passes the workgroup's share (8.6e-5); the whole row comes to 1.29e-4, which that
+    gate sees at this size: 35 rows are few.  At benchmark size (192 rows, 4 runs and 6 z blocks a row) a row is
+    1 / sqrt(192) of the norm, 7e-5."""
+    case = SEAM_CASES['sep2_gauss']
+    prob = make_problem(seed=case['seed'], **case['kw'])
+    xs, _ = oracle_structs(prob)
+    po = xs[0][0].po
+    assert tuple(po.dim_x) == (13, 35, 36)
+    op = ref64.Operator64(po, prob['method'])
+    _, _, myy, _ = op.tie_masks(po)
+    p = inputs(prob['dim_y'], po.dim_x)[0]
+    ref, tol = op.bound_AtA(p)
+    mid = op.A(p.double())
+    assert ref64.compare(op.At(mid).float(), ref, tol, myy)['ok']  # (the unplanted product, cast, passes)
+    own = 32  # kYXRows of conv.hip with gy = 0
+    row = mid.clone()
+    row[:, own, :] *= 1 + 1e-3
+    share = mid.clone()
+    share[6:12, own, 0:32] *= 1 + 1e-3
+    for label, x, l2_passes in (('row', row, None), ('one workgroup\'s share', share, True)):
+        bad = op.At(x).float()
+        r = ref64.compare(bad, ref, tol, myy)
+        l2 = rel_err(bad, ref)
+        print('seam plant %-22s n_bad %5d max err/tol %.3f rel_err %.3g' % (label, r['n_bad'], r['max_ratio'], l2))
+        assert not r['ok'] and r['n_bad'] > 100, (label, r)
+        if l2_passes:
+            assert l2 < 1e-4, (label, l2)
 
 
 def test_comparator_demands_exact_zero_outside_the_support():
@@ -261,3 +301,23 @@ def test_tie_cap_of_the_nonforward_table(name):
     assert tie_cap_ok(R), (name, int(R['myy'].sum()), int(R['my'].sum()), n)
     if n < 100:
         assert int(R['myy'].sum()) == 0
+
+
+@pytest.mark.parametrize('name', list(SEAM_CASES))
+def test_tie_cap_and_comb_spacing_of_the_seam_cases(name):
+    """Conditions on the seam cases of tests/test_gpu_voxelwise.py, met by the reference alone.  Their seeds are part of
+    the cases: with them fewer than 1 % of the voxels are excluded as FOV ties, in x space (A) and in y space (A^T,
+    A^T A) - other seeds of the same geometries exclude up to half the volume.  And the impulse combs see every column
+    on its own: the y-space spacing is at least the footprint of A^T A along each axis, 2 (taps - 1 + 2) + 1 for the
+    taps the plan keeps."""
+    case = SEAM_CASES[name]
+    prob = make_problem(seed=case['seed'], **case['kw'])
+    xs, _ = oracle_structs(prob)
+    po = xs[0][0].po
+    op = ref64.Operator64(po, prob['method'])
+    mx, my, myy, _ = op.tie_masks(po)
+    print('ties %s: %d (A) %d (At) %d (AtA)' % (name, int(mx.sum()), int(my.sum()), int(myy.sum())))
+    assert int(mx.sum()) < 0.01 * mx.numel() and int(my.sum()) < 0.01 * my.numel() and int(myy.sum()) < 0.01 * myy.numel()
+    kept = [int(k.sum()) for k in ref64.trimmed_taps(po.smo_ker_1d)]
+    sy, _ = spacings(case['kw'], case['spacing'])
+    assert all(s >= 2 * (n - 1 + 2) + 1 for s, n in zip(sy, kept)), (name, sy, kept)

@@ -3,9 +3,14 @@
 // Layout: float32 volumes, (X,Y,Z) C-contiguous, Z fastest.  Every kernel puts
 // the 64 lanes of a wave along Z so that HBM/L2 requests are coalesced.
 // Launch shape: block (64,4,1) -> grid (ceil(Z/64), ceil(Y/4), X).
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <algorithm>
+#include <mutex>
+#include <set>
+#include <string>
 
 #include "conv.hpp"
 
@@ -795,6 +800,38 @@ __global__ void __launch_bounds__(kBlock) k_conv_ydown_xdownup2(const float4 *__
 // --------------------------------------------------------------------------
 // host launchers
 // --------------------------------------------------------------------------
+// UNIRES_CONV_VERBOSE=1: one line on stderr the first time each kernel instantiation of the separable passes is
+// launched in the process (which kernel a pass took is not visible in the plan) - its name with the template
+// arguments, the grid, and the run length where the kernel marches in runs (run 0: none).  "copy": the identity's
+// hipMemcpyAsync (grid.x 0: no grid).  Unset: one branch per launch, nothing else.
+static inline bool conv_verbose() {
+  static const bool v = getenv("UNIRES_CONV_VERBOSE") && atoi(getenv("UNIRES_CONV_VERBOSE")) != 0;
+  return v;
+}
+__attribute__((format(printf, 3, 4))) static void conv_note(dim3 grid, int run, const char *fmt, ...) {
+  static std::mutex mu;
+  static std::set<std::string> seen;
+  char name[96];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(name, sizeof(name), fmt, ap);
+  va_end(ap);
+  std::lock_guard<std::mutex> lock(mu);
+  if (!seen.insert(name).second) return;
+  char g[48], r[24] = "";
+  if (grid.z > 1)
+    snprintf(g, sizeof(g), " grid %ux%ux%u", grid.x, grid.y, grid.z);
+  else
+    snprintf(g, sizeof(g), " grid %ux%u", grid.x, grid.y);
+  if (run > 0) snprintf(r, sizeof(r), " run %d", run);
+  const bool copy = grid.x == 0;  // (no kernel: no grid)
+  fprintf(stderr, "[conv] %s%s%s\n", name, copy ? "" : g, r);
+}
+#define CONV_NOTE(grid, run, ...)                                \
+  do {                                                           \
+    if (conv_verbose()) conv_note(grid, run, __VA_ARGS__);       \
+  } while (0)
+
 static inline bool conv1d_v4_ok(const void *a, const void *b, const Dim3i &sd, const Dim3i &dd) {
   return (sd.z & 3) == 0 && sd.z == dd.z && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
 }
@@ -879,6 +916,7 @@ int launch_conv_downup2(const float *src, Dim3i sd, const Taps &T, const Scaling
   March2 M = march2_args(sd, sd, ax, n, n, (n + 1) / 2, even(S, ax), odd(S, ax));
   taps12(T, ax, M.k);
   by_taps(T.n[ax], [&](auto NT) {
+    CONV_NOTE(march2_grid(M, (n + 1) / 2), M.run, "k_conv1d_downup2_m<%d,%d>", (int)NT(), fan2(NT()));
     hipLaunchKernelGGL((k_conv1d_downup2_m<NT(), fan2(NT())>), march2_grid(M, (n + 1) / 2), vol_block(), 0, st,
                        (const float4 *)src, (float4 *)dst, M, n_mid, done);
   });
@@ -914,12 +952,15 @@ int launch_conv_ydown_xdownup2(const float *src, Dim3i sd, const Taps &T, const 
       // every pair of tap counts but the Gaussian as built (11) with the Gaussian as the plan trims it (9)
       if constexpr ((NY() == 11 && NX() == 9) || (NY() == 9 && NX() == 11))
         err = 1;
-      else if (gy > 0)
+      else if (gy > 0) {
+        CONV_NOTE(grid, A.run, "k_conv_ydown_xdownup2<%d,%d,%d,%d>", (int)NY(), (int)NX(), fan2(NX()), fan2(NY()));
         hipLaunchKernelGGL((k_conv_ydown_xdownup2<NY(), NX(), fan2(NX()), fan2(NY())>), grid, vol_block(), 0, st,
                            (const float4 *)src, (float4 *)dst, A, done);
-      else
+      } else {
+        CONV_NOTE(grid, A.run, "k_conv_ydown_xdownup2<%d,%d,%d,0>", (int)NY(), (int)NX(), fan2(NX()));
         hipLaunchKernelGGL((k_conv_ydown_xdownup2<NY(), NX(), fan2(NX()), 0>), grid, vol_block(), 0, st,
                            (const float4 *)src, (float4 *)dst, A, done);
+      }
     });
   });
   return err;
@@ -944,6 +985,7 @@ void launch_conv_down_sep(const float *g, Dim3i gd, const Taps &T, const Scaling
   int todo = 0;
   for (int ax = 0; ax < 3; ++ax) todo += !is_dirac(T, ax) || S.dim == ax;
   if (todo == 0) {  // identity: plain copy
+    CONV_NOTE(dim3(0), 0, "copy");
     (void)hipMemcpyAsync(dst, g, gd.numel() * sizeof(float), hipMemcpyDeviceToDevice, st);
     return;
   }
@@ -955,6 +997,7 @@ void launch_conv_down_sep(const float *g, Dim3i gd, const Taps &T, const Scaling
       // y and x passes in one kernel (cur is z-complete: cd.z == xd.z)
       Taps2 K2;
       for (int t = 0; t < 8; ++t) K2.x[t] = T.t[0][t], K2.y[t] = T.t[1][t];
+      CONV_NOTE(conv2d_grid(xd), 0, "k_conv2d_down_xy_v4");
       hipLaunchKernelGGL(k_conv2d_down_xy_v4, conv2d_grid(xd), vol_block(), 0, st, (const float4 *)cur, cd, K2, T.n[0],
                          T.s[0], T.n[1], T.s[1], even(S, 0), odd(S, 0), even(S, 1), odd(S, 1), (float4 *)dst, xd, done);
       return;
@@ -968,18 +1011,23 @@ void launch_conv_down_sep(const float *g, Dim3i gd, const Taps &T, const Scaling
       March2 M = march2_args(cd, od, ax, n_in, n_out, n_out, se, so);
       taps12(T, ax, M.k);
       by_taps(T.n[ax], [&](auto NT) {
+        CONV_NOTE(march2_grid(M, n_out), M.run, "k_conv1d_down2_m<%d>", (int)NT());
         hipLaunchKernelGGL((k_conv1d_down2_m<NT()>), march2_grid(M, n_out), vol_block(), 0, st, (const float4 *)cur,
                            (float4 *)out, M, done);
       });
-    } else if (ax == 2 && T.s[2] <= 8)
+    } else if (ax == 2 && T.s[2] <= 8) {
+      CONV_NOTE(conv1d_grid(od), 0, "k_conv1d_down_z");
       hipLaunchKernelGGL(k_conv1d_down_z, conv1d_grid(od), vol_block(), 0, st, cur, cd, K, T.n[2], T.s[2], se, so, out,
                          od, done);
-    else if (ax != 2 && conv1d_v4_ok(cur, out, cd, od))
+    } else if (ax != 2 && conv1d_v4_ok(cur, out, cd, od)) {
+      CONV_NOTE(conv1d_grid(Dim3i{od.x, od.y, od.z / 4}), 0, "k_conv1d_down<float4>");
       hipLaunchKernelGGL(k_conv1d_down<float4>, conv1d_grid(Dim3i{od.x, od.y, od.z / 4}), vol_block(), 0, st,
                          (const float4 *)cur, cd, ax, K, T.n[ax], T.s[ax], se, so, (float4 *)out, od, done);
-    else
+    } else {
+      CONV_NOTE(conv1d_grid(od), 0, "k_conv1d_down<float>");
       hipLaunchKernelGGL(k_conv1d_down<float>, conv1d_grid(od), vol_block(), 0, st, cur, cd, ax, K, T.n[ax], T.s[ax],
                          se, so, out, od, done);
+    }
     cur = out, cd = od;
   }
 }
@@ -1004,10 +1052,12 @@ float *launch_conv_up_sep(const float *xs, Dim3i xd, const Taps &T, const Scalin
         dim3 g = conv2d_grid(od);
         if (fan_in(T, 0) <= 2 && fan_in(T, 1) <= 2) {
           g.y = (od.x + 3) / 4;
+          CONV_NOTE(g, 0, "k_conv2d_up_xy_v4_t<2,2,4>");
           hipLaunchKernelGGL((k_conv2d_up_xy_v4_t<2, 2, 4>), g, vol_block(), 0, st, (const float4 *)cur, cd, KX, KY,
                              T.n[0], T.s[0], T.n[1], T.s[1], sex, sox, sey, soy, (float4 *)o2, od);
         } else {
           g.y = (od.x + 1) / 2;
+          CONV_NOTE(g, 0, "k_conv2d_up_xy_v4_t<3,3,2>");
           hipLaunchKernelGGL((k_conv2d_up_xy_v4_t<3, 3, 2>), g, vol_block(), 0, st, (const float4 *)cur, cd, KX, KY,
                              T.n[0], T.s[0], T.n[1], T.s[1], sex, sox, sey, soy, (float4 *)o2, od);
         }
@@ -1033,6 +1083,7 @@ float *launch_conv_up_sep(const float *xs, Dim3i xd, const Taps &T, const Scalin
       by_taps(T.n[1], [&](auto NT) {
         constexpr int FY = fan2(NT());
         const size_t lds = (size_t)(kUpYZRows + FY - 1) * Y.pitch * sizeof(float);
+        CONV_NOTE(dim3((unsigned)(cd.x * nyb)), 0, "k_conv_up_yz2<%d>", FY);
         hipLaunchKernelGGL((k_conv_up_yz2<FY>), dim3((unsigned)(cd.x * nyb)), vol_block(), lds, st, cur, cd, Z, even(S, 2),
                            odd(S, 2), out, oz, Y, nyb);
       });
@@ -1045,26 +1096,33 @@ float *launch_conv_up_sep(const float *xs, Dim3i xd, const Taps &T, const Scalin
       split_taps(T, 2, Z.ke, Z.ko);
       const long long rows = (long long)od.x * od.y;
       const unsigned blocks = (unsigned)std::min<long long>((rows + 3) / 4, 16384);
+      CONV_NOTE(dim3(blocks), 0, "k_conv1d_up_z2");
       hipLaunchKernelGGL(k_conv1d_up_z2, dim3(blocks), vol_block(), 0, st, cur, cd, Z, se, so, out, od);
     } else if (march2_ok(T, ax) && conv1d_v4_ok(cur, out, cd, od)) {
       const int n_in = axis_len(cd, ax), n_out = axis_len(od, ax);
       March2 M = march2_args(cd, od, ax, n_in, n_out, (n_out + 1) / 2, se, so);
       split_taps(T, ax, M.k, M.k + 6);
       by_taps(T.n[ax], [&](auto NT) {
+        CONV_NOTE(march2_grid(M, (n_out + 1) / 2), M.run, "k_conv1d_up2_m<%d>", fan2(NT()));
         hipLaunchKernelGGL((k_conv1d_up2_m<fan2(NT())>), march2_grid(M, (n_out + 1) / 2), vol_block(), 0, st,
                            (const float4 *)cur, (float4 *)out, M);
       });
-    } else if (ax == 2)
+    } else if (ax == 2) {
+      CONV_NOTE(conv1d_grid(od), 0, "k_conv1d_up_z");
       hipLaunchKernelGGL(k_conv1d_up_z, conv1d_grid(od), vol_block(), 0, st, cur, cd, K, T.n[2], T.s[2], se, so, out, od);
-    else if (conv1d_v4_ok(cur, out, cd, od))
+    } else if (conv1d_v4_ok(cur, out, cd, od)) {
+      CONV_NOTE(conv1d_grid(Dim3i{od.x, od.y, od.z / 4}), 0, "k_conv1d_up<float4>");
       hipLaunchKernelGGL(k_conv1d_up<float4>, conv1d_grid(Dim3i{od.x, od.y, od.z / 4}), vol_block(), 0, st,
                          (const float4 *)cur, cd, ax, K, T.n[ax], T.s[ax], se, so, (float4 *)out, od);
-    else
+    } else {
+      CONV_NOTE(conv1d_grid(od), 0, "k_conv1d_up<float>");
       hipLaunchKernelGGL(k_conv1d_up<float>, conv1d_grid(od), vol_block(), 0, st, cur, cd, ax, K, T.n[ax], T.s[ax], se, so,
                          out, od);
+    }
     cur = out, cd = od;
   }
   if (!out) {  // identity
+    CONV_NOTE(dim3(0), 0, "copy");
     (void)hipMemcpyAsync(a, xs, xd.numel() * sizeof(float), hipMemcpyDeviceToDevice, st);
     out = a;
   }
