@@ -306,6 +306,9 @@ int unires_plan_matvec_time(unires_plan_t *plan, int32_t *launches, double *tota
  * capped by what was allocated then.  k == 0 changes nothing.  *last (nullable) gets the K the plan's last solve ran
  * with (1 for solves outside the scope and for a plan that has not solved yet). */
 int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last);
+/* How the plan's last solve was enqueued at its two ends (see unires_cg_solve): *trimmed (nullable) = 1 if its last
+ * iteration updated x alone, *start_fused (nullable) = 1 if the operator's last kernel wrote the start's residual. */
+int unires_plan_cg_ends(unires_plan_t *plan, int32_t *trimmed, int32_t *start_fused);
 
 /* _proj_apply(operator, ., po_n)  (_project.py:99-190) for repeat n, WITHOUT tau.
  * in/out sizes follow the operator (A: dim_y -> dim_x; At: dim_x -> dim_y; AtA: dim_y -> dim_y). */
@@ -345,7 +348,18 @@ int unires_precond_apply(unires_plan_t *plan, const float *in, float *out, void 
 
 /* nitorch cg(A=lhs, b, x, precond, max_iter, tolerance, stop,
  * inplace=True, sum_dtype=float64)  (_update.py:142-148): x is updated in place.
- * tol == 0 runs exactly max_iter iterations with no objective evaluation.
+ * tol == 0 runs exactly max_iter iterations with no objective evaluation.  Such a solve (no FFT preconditioner)
+ * does only the work x needs at its two ends: its last iteration is A(p), alpha and x += the pending alpha p
+ * terms - no residual, r.z, beta or next direction, which nothing would read - so the plan's internal r, r.z and
+ * beta are afterwards those of iteration max_iter - 1 (no entry point hands them out, and the next solve on the
+ * plan starts by writing all of them); and where the operator's last kernel is the schedule-driven push of a
+ * forward-difference plan whose last repeat has no mask, that kernel writes r = b - A(x), the first direction and
+ * the partials of r.z (and of obj[0], for a solve with a tolerance) itself and A(x) is never stored.  The trimmed
+ * last iteration leaves x the same bits.  The fused start sums the same float32 terms of r.z and obj[0] in float64
+ * in another grouping: the two agree with the separate kernel's to the rounding of such a sum, and x changes only
+ * if that moves alpha_1 or beta_1 across a float32 rounding boundary (not seen; the bench's outputs are the same
+ * bytes).  UNIRES_CG_TRIM=0 / UNIRES_CG_START_FUSED=0 (read once per process) enqueue the last iteration in
+ * full / keep the separate start kernel everywhere.
  * If iters_out != NULL the call synchronises the stream and returns the realised
  * iteration count; obj_trace (HOST, max_iter+1 doubles, may be NULL) then
  * receives the objective values obj[0..iters].

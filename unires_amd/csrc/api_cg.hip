@@ -9,6 +9,12 @@
 
 using namespace unires;
 
+// UNIRES_CG_START_FUSED, read once per process: 0 keeps k_residual_init at the start of every solve
+static bool cg_start_fused_on() {
+  static const bool on = !(getenv("UNIRES_CG_START_FUSED") && getenv("UNIRES_CG_START_FUSED")[0] == '0');
+  return on;
+}
+
 // The solve is enqueued in two parts: the start (r = b - A x, p, r.z, obj[0]) and runs of iterations.
 // `dev_k`: the iteration index is the device state's own counter (a captured chunk of iterations then
 // serves any part of a solve); `hostw`: the scalar kernel that ends an iteration publishes the state's
@@ -20,15 +26,25 @@ static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long lon
   const int gv = vec_num_blocks(ny);
   // r = b - A(x); p = r; rz = r.r; obj[0]
   HIP_TRY(hipMemsetAsync(&S->done, 0, sizeof(int), st));
-  matvec(pl, s.rho, s.lam, s.x, pl->ap, nullptr, nullptr, st);
+  // Where the push that ends the operator can (matvec, api_operator.hip) it writes r, p and the partials of r.z - and
+  // of the start's objective, where the stopping rule wants obj[0] - itself, and A(x) is never stored.  The partials
+  // are then grouped by the push's waves, not by k_residual_init's blocks: r.z and obj[0] are the float64 sums of the
+  // same float32 terms in another order, and agree with the other route's to the rounding of such a sum.
   const bool want_obj0 = check && s.stop != UNIRES_STOP_RESIDUAL;
-  launch_residual_init(s.b, pl->ap, s.x, pl->r, pl->p, ny, pl->part0, want_obj0 ? pl->part1 : nullptr, s.M, st);
+  StartResidual res = {s.b, pl->r, pl->p, s.M, pl->part0, want_obj0 ? pl->part1 : nullptr, false};
+  const bool ask = cg_start_fused_on() && !s.fft;
+  int g0 = matvec(pl, s.rho, s.lam, s.x, pl->ap, nullptr, nullptr, st, nullptr, ask ? &res : nullptr);
+  pl->last_fused = ask && res.served;
+  if (!(ask && res.served)) {
+    launch_residual_init(s.b, pl->ap, s.x, pl->r, pl->p, ny, pl->part0, want_obj0 ? pl->part1 : nullptr, s.M, st);
+    g0 = gv;
+  }
   if (s.fft) {  // z = M^-1 r ; p = z ; rz = r.z
     if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
     HIP_TRY(hipMemcpyAsync(pl->p, pl->fft.z, ny * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_dot(pl->r, pl->fft.z, ny, pl->part0, nullptr, st);
   }
-  launch_sc_init(S, pl->part0, pl->part1, gv, s.stop, check ? 1 : 0, hostw, st);
+  launch_sc_init(S, pl->part0, pl->part1, g0, s.stop, check ? 1 : 0, hostw, st);
   return UNIRES_OK;
 }
 
@@ -37,10 +53,20 @@ static float *ring_slot(unires_plan *pl, int j) {
   return j == 0 ? pl->p : pl->ring + (size_t)(j - 1) * (align_up(pl->dy.numel() * 4) / 4);
 }
 
+// UNIRES_CG_TRIM, read once per process: 0 enqueues the last iteration of every solve in full
+static bool cg_trim_on() {
+  static const bool on = !(getenv("UNIRES_CG_TRIM") && getenv("UNIRES_CG_TRIM")[0] == '0');
+  return on;
+}
+
 // Iterations k_first .. k_first + count - 1 of the solve.
 // s.ring > 1 (tol = 0 solves enqueued whole, cg_ring_prepare): the iterate update is deferred - iteration k's
 // direction is slot (k - k_first) mod ring, and x takes the window's alpha p terms at every ring-th iteration and at
 // the last (k_update_p_flush, cg.hip).
+// The last iteration of a solve that runs all its iterations and is enqueued whole (tol = 0, !dev_k, no FFT
+// preconditioner: the scope of the deferred update) is the operator, alpha and the iterate alone: nothing reads the
+// residual, r.z, beta or direction that would follow it.  k_sc_alpha writes the iteration count in k_sc_beta's stead;
+// the plan's r, rz and beta stay those of the iteration before.
 static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
                             unsigned long long *hostw, hipStream_t st) {
   const size_t ny = pl->dy.numel();
@@ -51,6 +77,9 @@ static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int 
   const int gv = vec_num_blocks(ny);
   if (ring > 1 && (check || s.fft || dev_k || ring > kMaxRing || ring - 1 > pl->ring_slots))
     return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
+  // (enqueued whole: this call IS the solve, so its last iteration is the solve's)
+  const bool trim = cg_trim_on() && !check && !s.fft && !dev_k && k_first == 1 && count == s.max_iter;
+  pl->last_trim = trim && count > 0;
   RingPtrs rp = {};
   for (int j = 0; j < ring && ring > 1; ++j) rp.p[j] = ring_slot(pl, j);
   for (int k = k_first; k < k_first + count; ++k) {
@@ -83,6 +112,14 @@ static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int 
     if (recur) obj_kind = 2;
     // "x += alpha p" rides with the p update unless sc_beta can stop the solve in between
     const bool lazy_x = obj_kind == 0;
+    if (trim && k == k_first + count - 1) {
+      launch_sc_alpha(S, pl->part0, g, st, k);
+      if (ring > 1)
+        launch_update_x_flush(S, rp, slot + 1, ny, s.x, st);
+      else
+        launch_update_x(S, p, ny, s.x, st);
+      break;
+    }
     launch_sc_alpha(S, pl->part0, g, st);
     launch_update_xr(S, p, pl->ap, lazy_x ? nullptr : s.x, pl->r, s.b, ny, pl->part0,
                      recur ? pl->part1 : nullptr, s.M, st);
@@ -268,9 +305,12 @@ static int cg_run_start_impl(CgRun &R) {
       R.use_graph = false;
     } else {
       pl->cg_chunk_key = key;
+      pl->chunk_fused = pl->last_fused;
     }
   }
+  pl->last_trim = 0;  // (a chunked solve is never trimmed)
   if (R.use_graph) {
+    pl->last_fused = pl->chunk_fused;
     HIP_TRY(hipGraphLaunch(pl->cg_start_exec, R.st));
   } else {
     const int rc = cg_enqueue_start(pl, R.s, pl->progress_dev, R.st);
@@ -281,6 +321,7 @@ static int cg_run_start_impl(CgRun &R) {
   if (!rc) rc = cg_run_enqueue_chunk(R);
   if (rc) return rc;
   if (R.enqueued >= R.s.max_iter) R.finished = true;
+  pl->last_trim = 0;
   return UNIRES_OK;
 }
 
@@ -447,6 +488,7 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
   // captured once and re-launched as one graph while the arguments stay the same
   const bool graphable = cg_graphs_on() && !s.fft && max_iter > 0 && !pl->timing;  // (events go with plain launches)
   if (graphable && pl->cg_exec && pl->cg_key.same_graph(s)) {
+    pl->last_trim = pl->graph_trim, pl->last_fused = pl->graph_fused;
     HIP_TRY(hipGraphLaunch(pl->cg_exec, st));
   } else {
     if (graphable && pl->cg_exec) drop_cg_graph(pl);
@@ -457,6 +499,7 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
     }
     if (rc == 0) {
       pl->cg_key = s;
+      pl->graph_trim = pl->last_trim, pl->graph_fused = pl->last_fused;
       if (hipGraphLaunch(pl->cg_exec, st) != hipSuccess) {
         cg_resync_gen(pl);
         return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");

@@ -219,6 +219,9 @@ struct unires_plan {
   bool ring_tried = false;  // the allocation was decided (made, refused by the budget, or failed)
   int ring_req = 0;         // unires_plan_cg_ring: K asked for (0: UNIRES_CG_RING or the default)
   int last_ring = 1;        // K of the plan's last solve (1: the iterate updated every iteration)
+  // unires_plan_cg_ends: whether the plan's last solve had its last iteration trimmed / its start's residual written by
+  // the push (api_cg.hip); graph_*: the same for the captured solves, which a replay reports
+  int last_trim = 0, last_fused = 0, graph_trim = 0, graph_fused = 0, chunk_fused = 0;  // (chunk_: of cg_start_exec)
   unires::FftPre fft;      // FFT-diagonal preconditioner (plans + buffers, made on demand)
   float prec_rho = 0.f, prec_lam = 0.f;
   int prec_mode = UNIRES_PRECOND_IDENTITY;
@@ -250,7 +253,19 @@ void drop_cg_graph(unires_plan *pl);  // every captured solve of the plan, the c
 // With objb (and part): the partials hold sum (q - 2 objb) * p instead and the final q is not
 // stored (q is still scratch for the partial sums of a multi-repeat operator).
 // Returns the number of partials written (0 if none requested).
+// With res (the start of a CG solve; part and objb unset): a route that can (k_splat2 as the last repeat's push of a
+// forward-difference plan without masked repeats) writes r = b - q, z = r or r / M and the partials of sum r z
+// instead of storing q, and sets res->served; the return value is then the number of those partials.  Any other
+// route ignores it: q is stored as without res, served stays false.
+struct StartResidual {
+  const float *b;
+  float *r, *p;       // r, and z = the first direction
+  const float *M;     // Jacobi diagonal or nullptr
+  double *partials;
+  double *obj_partials;  // nullable: the partials of the start's objective sum (A(x) - 2 b) x
+  bool served;
+};
 int matvec(unires_plan *pl, float rho, float lam, const float *p, float *q, double *part, const int *done,
-           hipStream_t st, const float *objb = nullptr);
+           hipStream_t st, const float *objb = nullptr, StartResidual *res = nullptr);
 
 }  // namespace unires

@@ -124,11 +124,30 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
   return push_src(R, pl->xbuf, true, 0.f);
 }
 
+// An epilogue without the residual mode, i.e. what matvec() asks of the start's operator application when nothing
+// fuses the residual: out stored, no partials.
+static PushEpilogue without_residual(PushEpilogue ep) {
+  if (ep.res_r) ep.partials = nullptr;
+  ep.res_b = nullptr, ep.res_r = nullptr, ep.res_p = nullptr, ep.res_M = nullptr, ep.res_obj = nullptr;
+  return ep;
+}
+
 // out = [out +] alpha * push(src) [+ epilogue]; falls back to a materialised conv_up when
 // the conv_up fan-in is beyond what the fused kernel tabulates.
+// The residual mode of the epilogue (ep.res_r) is k_splat2's alone and whether a push serves it is decided HERE, in
+// one place: a launch_splat2 that takes the push of an unmasked repeat serves it and *served says so; every other
+// kernel gets the epilogue without it.  (What is asked at all is matvec()'s: the mode belongs to the matvec's last
+// push of a forward-difference operator.  ata_apply() strips it for k_ata1, which is not a push.)
 static int push_any(unires_plan *pl, const PushSrc &src, const Repeat &R, float alpha,
-                     const PushEpilogue &ep, float *out, const int *done, hipStream_t st) {
+                     const PushEpilogue &ep_in, float *out, const int *done, hipStream_t st, bool *served = nullptr) {
   const Affine &A = src.convup ? R.Af : R.A;
+  const PushEpilogue ep = without_residual(ep_in);  // what every kernel but k_splat2 is given
+  const PushEpilogue &ep2 = R.masked ? ep : ep_in;   // ... and k_splat2 (a masked repeat declines the mode)
+  const auto s2_done = [&] {
+    if (served) *served = ep2.res_r != nullptr;
+    return ep2.partials ? splat2_blocks(pl->dy, ep2.grid_cap) : 0;
+  };
+  if (served) *served = false;
   // default: the schedule-driven splat (k_splat2), then the r1 tile kernels where an operator is outside its
   // domain; UNIRES_PUSH=tile forces the general tile kernel (tests' cross-check)
   const bool use_tile = push_mode() == PushMode::kTile, sched_ok = push_mode() == PushMode::kDefault;
@@ -141,15 +160,15 @@ static int push_any(unires_plan *pl, const PushSrc &src, const Repeat &R, float 
     const float *h = xy_done ? src.data : launch_conv_up_sep(src.data, src.xd, Txy, Sxy, R.dim_h, pl->gbuf, pl->gbuf2, st);
     const float4 *tab = (const float4 *)R.ctab_dev[src.S.dim == 2 ? 1 : 0];
     if (!launch_splat2(R.sched, h, R.dim_h.numel(), tab, R.ctab_n, R.src_stride, R.ctab_step, R.src_stride,
-                       R.ctab_step, A, alpha, ep, out, pl->dy, done, st))
-      return ep.partials ? splat2_blocks(pl->dy, ep.grid_cap) : 0;
+                       R.ctab_step, A, alpha, ep2, out, pl->dy, done, st))
+      return s2_done();
   }
   if (sched_ok && !R.hyb && R.sched.valid && (src.convup != 0) == (R.sched.axis >= 0)) {
     const float4 *tab = src.convup ? (const float4 *)R.ctab_dev[src.S.dim >= 0 ? 1 : 0] : nullptr;
     const size_t numel = src.convup ? src.xd.numel() : src.gd.numel();
     if (!launch_splat2(R.sched, src.data, numel, tab, R.ctab_n, R.src_stride, R.ctab_step, R.src_stride,
-                       R.ctab_step, A, alpha, ep, out, pl->dy, done, st))
-      return ep.partials ? splat2_blocks(pl->dy, ep.grid_cap) : 0;
+                       R.ctab_step, A, alpha, ep2, out, pl->dy, done, st))
+      return s2_done();
   }
   if (!use_tile &&
       !launch_splat(src, A, R.Afinv, R.safe, alpha, pl->fov_tol, ep, out, pl->dy, done, st))
@@ -160,9 +179,9 @@ static int push_any(unires_plan *pl, const PushSrc &src, const Repeat &R, float 
     d.data = launch_conv_up_sep(src.data, src.xd, src.T, src.S, src.gd, pl->gbuf, pl->gbuf2, st);
     d.convup = 0;
     if (sched_ok && R.sched.valid && R.sched.axis < 0 &&
-        !launch_splat2(R.sched, d.data, d.gd.numel(), nullptr, 0, R.src_stride, 1, 0, 0, A, alpha, ep, out,
+        !launch_splat2(R.sched, d.data, d.gd.numel(), nullptr, 0, R.src_stride, 1, 0, 0, A, alpha, ep2, out,
                        pl->dy, done, st))
-      return ep.partials ? splat2_blocks(pl->dy, ep.grid_cap) : 0;
+      return s2_done();
     if (!launch_splat(d, A, R.Afinv, R.safe, alpha, pl->fov_tol, ep, out, pl->dy, done, st))
       return ep.partials ? splat_blocks(pl->dy, A) : 0;
     (void)launch_push_tile(d, A, R.Afinv, R.safe, alpha, pl->fov_tol, ep, out, pl->dy, done, st);
@@ -200,13 +219,16 @@ static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, floa
 // (denoising regime, ata1.hip; not a masked repeat, whose intermediate has to exist), else forward + push.  `share`: the persistent kernels' grids leave room for the
 // other channels' solves (unires_plan_set_concurrency).  Returns the number of partials written.
 static int ata_apply(unires_plan *pl, const Repeat &R, const float *in, float alpha, PushEpilogue ep, bool share,
-                     float *out, const int *done, hipStream_t st) {
-  ep.grid_cap = share ? pl->cap_f1 : 0;
-  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !R.masked && !launch_ata1(R.f1, in, R.Af, alpha, ep, out, pl->dy, done, st))
-    return ep.partials ? ata1_blocks(pl->dy, ep.grid_cap) : 0;
+                     float *out, const int *done, hipStream_t st, bool *served = nullptr) {
+  if (served) *served = false;
+  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !R.masked) {
+    PushEpilogue e1 = without_residual(ep);  // (k_ata1 declines the residual mode)
+    e1.grid_cap = share ? pl->cap_f1 : 0;
+    if (!launch_ata1(R.f1, in, R.Af, alpha, e1, out, pl->dy, done, st)) return e1.partials ? ata1_blocks(pl->dy, e1.grid_cap) : 0;
+  }
   ep.grid_cap = share ? pl->cap_s2 : 0;
   const PushSrc src = ata_forward(pl, R, in, done, st);
-  return push_any(pl, src, R, alpha, ep, out, done, st);
+  return push_any(pl, src, R, alpha, ep, out, done, st, served);
 }
 
 extern "C" int unires_proj_apply(unires_plan_t *plan, int32_t n, int32_t op, const float *in,
@@ -266,7 +288,8 @@ static int stencil_close(unires_plan *pl, float c, const float wr[3], const floa
 // stencil term (wr / wq) and close the matvec with the dot or the objective.  Backward's and central's run on the same
 // kernels with zero weights and no partials, and stencil_close() then adds c DtD_W p and closes the matvec.
 int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float *q, double *part, const int *done,
-                   hipStream_t st, const float *objb) {
+                   hipStream_t st, const float *objb, StartResidual *res) {
+  if (res) res->served = false;
   // stencil weights rho lam^2 / vx_d^2, in the two roundings the kernels were validated with bit for bit:
   // wr = c * (1 / vx^2) (flat stencil, shift and aligned kernels), wq = c / vx^2 (line stencil, push epilogue)
   const float c = rho * (lam * lam);
@@ -304,6 +327,9 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
     if (!shift()) return kpart ? shift_blocks(pl->dy) : 0;
     return -1;
   };
+  // The residual mode is asked of a forward-difference plan that takes the per-repeat route (the one-kernel forms do
+  // not know it), on the last repeat's push; push_any() serves or declines it.
+  const bool ask = res && fwd && !part && !objb;
   int npart = one_kernel();
   if (npart < 0) {
     // regimes 1/2: one or two kernels per repeat; forward's last one also adds c DtD p and the dot
@@ -317,8 +343,11 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
         ep.p = p;
         if (n == 0) ep.cx = wq[0], ep.cy = wq[1], ep.cz = wq[2];  // the stencil term goes in once
         if (n + 1 == nrep) ep.partials = part, ep.objb = objb;
+        if (n + 1 == nrep && ask)
+          ep.partials = res->partials, ep.res_obj = res->obj_partials, ep.res_b = res->b, ep.res_r = res->r,
+          ep.res_p = res->p, ep.res_M = res->M;
       }
-      npart = ata_apply(pl, R, p, R.tau, ep, true, q, done, st);
+      npart = ata_apply(pl, R, p, R.tau, ep, true, q, done, st, n + 1 == nrep && ask ? &res->served : nullptr);
     }
   }
   return fwd ? npart : stencil_close(pl, c, wr, wq, 0.f, true, p, q, part, done, st, objb);

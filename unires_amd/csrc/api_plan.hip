@@ -524,6 +524,13 @@ extern "C" int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last
   return UNIRES_OK;
 }
 
+extern "C" int unires_plan_cg_ends(unires_plan_t *plan, int32_t *trimmed, int32_t *start_fused) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
+  if (trimmed) *trimmed = plan->last_trim;
+  if (start_fused) *start_fused = plan->last_fused;
+  return UNIRES_OK;
+}
+
 extern "C" int unires_plan_matvec_time(unires_plan_t *plan, int32_t *launches, double *total_us) {
   if (!plan || !launches || !total_us) return fail(UNIRES_ERR_NULL, "null argument");
   *launches = 0, *total_us = 0.0;

@@ -260,11 +260,14 @@ __global__ void __launch_bounds__(kBlock)
 // p_out is slot 0 when the window is full (m = K): element i of slot 0 is read and then overwritten by the same thread
 // in the same loop trip, and no other thread touches element i, so the in-place write is safe (the pointers carry no
 // __restrict__, which keeps the compiler from moving the load below the store).
+// PUPD = false (the last iteration of a solve that runs all its iterations, api_cg.hip): the iterate alone - r is not
+// read and no p_out written, m + 2 volume passes instead of m + 4; the terms, their order and roundings are the same.
+template <bool PUPD>
 __global__ void __launch_bounds__(kBlock)
     k_update_p_flush(CgState *__restrict__ st, const float *__restrict__ r, RingPtrs ring, int m, float *p_out,
                      size_t n, const float *__restrict__ M, float *__restrict__ x) {
   const int done = st->done;
-  const float beta = (float)st->beta;
+  const float beta = PUPD ? (float)st->beta : 0.f;
   float a[kMaxRing];
   bool c[kMaxRing];
   bool any = false;
@@ -279,7 +282,7 @@ __global__ void __launch_bounds__(kBlock)
   GRID_STRIDE_VEC4(n);
   for (size_t i = tid0; i < n4; i += stride) {
     float4 vz = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!done) vz = zval4(ld4(r, i), M, i);
+    if (PUPD && !done) vz = zval4(ld4(r, i), M, i);
     float4 vx = ld4_stream(x, i);
     float4 vp[kMaxRing];
 #pragma unroll
@@ -292,7 +295,7 @@ __global__ void __launch_bounds__(kBlock)
       vx.y = __fadd_rn(vx.y, __fmul_rn(a[j], vp[j].y));
       vx.z = __fadd_rn(vx.z, __fmul_rn(a[j], vp[j].z));
       vx.w = __fadd_rn(vx.w, __fmul_rn(a[j], vp[j].w));
-      if (j == m - 1) {  // (c[m - 1] = !done)
+      if (PUPD && j == m - 1) {  // (c[m - 1] = !done)
         float4 b = vp[j];
         b.x = __fadd_rn(__fmul_rn(beta, b.x), vz.x);
         b.y = __fadd_rn(__fmul_rn(beta, b.y), vz.y);
@@ -313,8 +316,27 @@ __global__ void __launch_bounds__(kBlock)
       if (j == m - 1) own = pj;
     }
     x[i] = vx;
-    if (!done) p_out[i] = __fadd_rn(__fmul_rn(beta, own), zval1(r[i], M, i));
+    if (PUPD && !done) p_out[i] = __fadd_rn(__fmul_rn(beta, own), zval1(r[i], M, i));
   }
+}
+
+// x = fl(x + fl(alpha p)) alone: the last iteration of such a solve where the iterate is updated every iteration
+// (K = 1), 3 volume passes instead of k_update_p<true>'s 5.  This is the direction's last read.
+__global__ void __launch_bounds__(kBlock)
+    k_update_x(const CgState *__restrict__ st, const float *__restrict__ p, size_t n, float *__restrict__ x) {
+  if (st->done) return;
+  const float alpha = (float)st->alpha;
+  GRID_STRIDE_VEC4(n);
+  for (size_t i = tid0; i < n4; i += stride) {
+    const float4 vp = ld4_stream(p, i);
+    float4 vx = ld4_stream(x, i);
+    vx.x = __fadd_rn(vx.x, __fmul_rn(alpha, vp.x));
+    vx.y = __fadd_rn(vx.y, __fmul_rn(alpha, vp.y));
+    vx.z = __fadd_rn(vx.z, __fmul_rn(alpha, vp.z));
+    vx.w = __fadd_rn(vx.w, __fmul_rn(alpha, vp.w));
+    st4_stream(x, i, vx);
+  }
+  for (size_t i = n4 * 4 + tid0; i < n; i += stride) x[i] = __fadd_rn(x[i], __fmul_rn(alpha, p[i]));
 }
 
 // y = a*x + y (generic axpy; used by the identity regime's RHS)
@@ -425,7 +447,8 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-__global__ void __launch_bounds__(kBlock) k_sc_alpha(CgState *st, const double *part_pap, int g) {
+// iters_end > 0 (the last iteration of a solve whose k_sc_beta is not enqueued, api_cg.hip): the iteration count as well
+__global__ void __launch_bounds__(kBlock) k_sc_alpha(CgState *st, const double *part_pap, int g, int iters_end) {
   PartLoad L;
   part_issue(part_pap, g, L);
   const int done = st->done;
@@ -434,6 +457,7 @@ __global__ void __launch_bounds__(kBlock) k_sc_alpha(CgState *st, const double *
   if (threadIdx.x == 0 && !done) {
     st->pAp = pap;
     st->alpha = rz / pap;
+    if (iters_end > 0) st->iters = iters_end;
   }
 }
 
@@ -594,7 +618,14 @@ void launch_update_p_ring(CgState *s, const float *r, const float *p_in, float *
 }
 void launch_update_p_flush(CgState *s, const float *r, const RingPtrs &ring, int m, float *p_out, size_t n,
                            const float *M, float *x, hipStream_t st) {
-  hipLaunchKernelGGL(k_update_p_flush, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
+  hipLaunchKernelGGL(k_update_p_flush<true>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
+}
+void launch_update_x_flush(CgState *s, const RingPtrs &ring, int m, size_t n, float *x, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_p_flush<false>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, (const float *)nullptr, ring, m,
+                     (float *)nullptr, n, (const float *)nullptr, x);
+}
+void launch_update_x(const CgState *s, const float *p, size_t n, float *x, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_x, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, p, n, x);
 }
 // y = a*y + c  (preconditioner diagonal: tau * AtA(1) + const)
 __global__ void __launch_bounds__(kBlock) k_scale_shift(float a, float c, float *__restrict__ y, size_t n) {
@@ -633,8 +664,8 @@ void launch_sc_init(CgState *s, const double *part_rr, const double *part_obj, i
   hipLaunchKernelGGL(k_sc_init, dim3(1), dim3(kBlock), 0, st, s, part_rr, part_obj, g, mode,
                      check, hostw);
 }
-void launch_sc_alpha(CgState *s, const double *part, int g, hipStream_t st) {
-  hipLaunchKernelGGL(k_sc_alpha, dim3(1), dim3(kBlock), 0, st, s, part, g);
+void launch_sc_alpha(CgState *s, const double *part, int g, hipStream_t st, int iters_end) {
+  hipLaunchKernelGGL(k_sc_alpha, dim3(1), dim3(kBlock), 0, st, s, part, g, iters_end);
 }
 void launch_sc_beta(CgState *s, const double *part_rr, const double *part_obj, int g, int k,
                     int obj_kind, double tol, unsigned long long *hostw, hipStream_t st) {

@@ -55,6 +55,10 @@ void launch_update_p_ring(CgState *s, const float *r, const float *p_in, float *
 // x = fl(x + fl(alpha_j p_j)) for the committed slots j = 0 .. m - 1 in ascending order
 void launch_update_p_flush(CgState *s, const float *r, const RingPtrs &ring, int m, float *p_out, size_t n,
                            const float *M, float *x, hipStream_t st);
+// The iterate alone, for the last iteration of a solve that runs all of its iterations (nothing reads the r, beta and
+// p that would follow it): the flush without its p update and without reading r, and x = fl(x + fl(alpha p)) for K = 1
+void launch_update_x_flush(CgState *s, const RingPtrs &ring, int m, size_t n, float *x, hipStream_t st);
+void launch_update_x(const CgState *s, const float *p, size_t n, float *x, hipStream_t st);
 // M = nullptr: identity preconditioner; else z = r / M (Jacobi)
 void launch_scale_shift(float a, float c, float *y, size_t n, hipStream_t st);
 void launch_fill(float v, float *y, size_t n, hipStream_t st);
@@ -65,7 +69,9 @@ void launch_axpy(float a, const float *x, float *y, size_t n, hipStream_t st);
 // iters), so that a captured chunk of iterations can be replayed for any part of a solve.
 void launch_sc_init(CgState *s, const double *part_rr, const double *part_obj, int g, int mode,
                     int check, unsigned long long *hostw, hipStream_t st);
-void launch_sc_alpha(CgState *s, const double *part, int g, hipStream_t st);
+// iters_end > 0: sc_alpha also sets the state's iteration count to it (the last iteration of a solve enqueued without
+// that iteration's sc_beta)
+void launch_sc_alpha(CgState *s, const double *part, int g, hipStream_t st, int iters_end = 0);
 void launch_sc_beta(CgState *s, const double *part_rr, const double *part_obj, int g, int k,
                     int obj_kind, double tol, unsigned long long *hostw, hipStream_t st);
 void launch_sc_obj(CgState *s, const double *part, int g, int k, double tol, unsigned long long *hostw,

@@ -19,6 +19,14 @@ struct PushEpilogue {
   int accumulate = 0;          // dst += instead of dst =
   double *partials = nullptr;  // push_tile_blocks(dd) doubles: pieces of sum(p * dst)
   const float *objb = nullptr; // objective mode: partials = sum (dst - 2 objb) * p, dst not stored
+  // residual mode (the start of a CG solve, dst = A(x0) with p = x0): r = res_b - dst goes to res_r, z = r, or
+  // r / res_M, to res_p, partials = sum r z, res_obj (nullable, as many slots) = sum (dst - 2 res_b) p, and dst is not
+  // stored.  k_splat2 alone implements it: push_any() (api_operator.hip) decides whether a push serves it, clears it
+  // for every other kernel and says which happened.
+  const float *res_b = nullptr;
+  double *res_obj = nullptr;
+  float *res_r = nullptr, *res_p = nullptr;
+  const float *res_M = nullptr;
   int grid_cap = 0;            // persistent kernels (k_splat2, k_ata1): at most this many workgroups; 0 = as many as the chip holds
 };
 

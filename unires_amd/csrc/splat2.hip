@@ -847,10 +847,17 @@ struct S2Args {
   int xlo[9];  // position range [xlo[x], xlo[x + 1]) of partition x (an XCD when the grid has >= 8 workgroups)
   int active;  // workgroups that take tiles (the rest of the grid only clears its partials)
   unsigned long long *prof;  // -DUNIRES_S2_PROF builds: per-wave timeline (100 MHz ticks)
+  // residual mode (PushEpilogue::res_r; objb = b, OBJK kernels only): r = b - q to res_r, z = r [/ res_M] to res_p,
+  // partials = sum r z; q is not stored.  Last in the struct: every other field sits where it sat.
+  float *res_r, *res_p;
+  const float *res_M;
+  double *partials2;  // residual mode, nullable: sum obj_term(q, b, p), the start's objective, in the slots of `partials`
 };
 
 // OBJK: the launch evaluates the CG objective (P.objb set: q is not stored) - a kernel of its own since r6, so that the
-// sixteen extra rows its epilogue holds do not decide the register allocation of the form every CG iteration runs
+// sixteen extra rows its epilogue holds do not decide the register allocation of the form every CG iteration runs.
+// The same kernel serves the start of a CG solve (P.res_r set): with A(x0) in registers and b in its rows it writes the
+// residual and the first direction and sums r.z, where k_residual_init read A(x0) and b back.
 template <int AXIS, int NW, bool OBJK>
 __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(4, 4))) k_splat2(S2Args P, const int *__restrict__ done) {
   if (done && *done) return;
@@ -906,6 +913,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
   // the kernel took twice a workgroup's time (config 4: 424 us where 16.5 M points cost 81 us in config 3).
   if ((int)blockIdx.x >= P.active) {
     if (P.partials && lane == 0) P.partials[blockIdx.x * NW + wave] = 0.0;
+    if (OBJK && P.partials2 && lane == 0) P.partials2[blockIdx.x * NW + wave] = 0.0;
     return;
   }
   const int nwg = P.active;
@@ -928,6 +936,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
   v2k k_one0 = {1.f, 0.f};  // (likewise: the packed weight pairs' second constant, else re-made in front of every use)
   asm volatile("" : "+v"(k_one0));
   double dot = 0.0;
+  double dot2 = 0.0;  // (residual mode with the objective; OBJK kernels only)
 #ifdef UNIRES_S2_PROF
   unsigned long long *pw = P.prof ? P.prof + (size_t)(blockIdx.x * NW + wave) * 32 : nullptr;
   int ptile = 0;
@@ -1324,6 +1333,10 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     const float kcx = K->cx, kcy = K->cy, kcz = K->cz, ka0 = K->a0;
     asm volatile("" ::"s"(H.entries), "s"(H.ent_bytes), "s"(H.tab), "s"(H.gn), "s"(H.masks), "s"(H.bwords), "s"(pin), "s"(dst), "s"(objb),
                  "s"(accumulate), "s"(kcx), "s"(kcy), "s"(kcz), "s"(ka0));
+    float *res_r = OBJK ? K->res_r : nullptr, *res_p = OBJK ? K->res_p : nullptr;
+    const float *res_M = OBJK ? K->res_M : nullptr;
+    const bool res_obj = OBJK && K->partials2 != nullptr;
+    if (OBJK) asm volatile("" ::"s"(res_r), "s"(res_p), "s"(res_M));
     {
       // (the ring's chunk in flight may never have been used: let it land NOW, or the compiler waits for everything -
       // the header included - the first time the epilogue writes one of its registers)
@@ -1334,6 +1347,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
       if (rec_next.x != 0xffffffffu) issue_header(H, rec_next, lh);
     }
     double dtile = 0.0;  // this tile's part of the dot
+    double dtile2 = 0.0;
     const bool fast_xy = !S2_ABL(2) && pin != nullptr && !accumulate && ex == TX && ey == TY && dd.numel() < (1ull << 29);
     if (fast_xy) {
       // Whole tiles, wherever they lie: x / y stencil neighbours outside the volume read as zeros
@@ -1378,6 +1392,10 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
       const __amdgpu_buffer_rsrc_t rp = make_rsrc(pin, dd.numel() * 4),
                                    rd = make_rsrc(dst, dd.numel() * 4),
                                    rb = make_rsrc(objb ? objb : pin, dd.numel() * 4);
+      // (residual mode: out-of-range lanes store nowhere, as with q; a mode without the diagonal never loads through rm)
+      const __amdgpu_buffer_rsrc_t rrr = make_rsrc(res_r ? res_r : dst, dd.numel() * 4),
+                                   rrp = make_rsrc(res_p ? res_p : dst, dd.numel() * 4),
+                                   rm = make_rsrc(res_M ? res_M : pin, dd.numel() * 4);
       const float *arow = acc + ((4 * grp + 1) * SY + 1) * SZ + gl;
       float pv[6][6];  // pv[s + 1][ly + 1]: x slab s = -1 .. 4, row ly = -1 .. 4 (corners unused)
 #pragma unroll
@@ -1403,7 +1421,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
         float dxp[4];
 #pragma unroll
         for (int la = 1; la <= 4; ++la) dxp[la - 1] = pv[1][la] - pv[0][la];
-        double dt = 0.0;
+        double dt = 0.0, dt2 = 0.0;
 #pragma unroll
         for (int sa = 1; sa <= 4; ++sa) {
           float dy[5], av[4];  // (the slab's four accumulator reads issued together, ahead of its arithmetic)
@@ -1413,6 +1431,11 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
           if (OBJ) {
 #pragma unroll
             for (int la = 1; la <= 4; ++la) ob[la - 1] = buf_load(rb, e1, (unsigned)(sa - 1) * sxb + (unsigned)(la - 1) * syb);
+          }
+          float om[4] = {1.f, 1.f, 1.f, 1.f};  // (residual mode with the Jacobi diagonal: M of the slab's rows)
+          if (OBJ && res_M) {
+#pragma unroll
+            for (int la = 1; la <= 4; ++la) om[la - 1] = buf_load(rm, e1, (unsigned)(sa - 1) * sxb + (unsigned)(la - 1) * syb);
           }
 #pragma unroll
           for (int la = 0; la <= 4; ++la) dy[la] = pv[sa][la + 1] - pv[sa][la];
@@ -1428,7 +1451,14 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
             const float yf = dy[la], ybk = dy[la - 1];
             const float st = kcx * (xbk - xf) + kcy * (ybk - yf) + kcz * (zbk - zf);
             const float q = av[la - 1] + (ka0 * c + st);
-            if (OBJ) {
+            if (OBJ && res_r) {
+              const float r = __fsub_rn(ob[la - 1], q);
+              const float z = res_M ? __fdiv_rn(r, om[la - 1]) : r;
+              buf_store(r, rrr, est, (unsigned)(sa - 1) * sxb + (unsigned)(la - 1) * syb);
+              buf_store(z, rrp, est, (unsigned)(sa - 1) * sxb + (unsigned)(la - 1) * syb);
+              dt += (double)__fmul_rn(r, z);
+              if (res_obj) dt2 += (double)obj_term(q, ob[la - 1], c);
+            } else if (OBJ) {
               dt += (double)obj_term(q, ob[la - 1], c);
             } else {
               buf_store(q, rd, est, (unsigned)(sa - 1) * sxb + (unsigned)(la - 1) * syb);
@@ -1437,6 +1467,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
           }
         }
         dtile = out_z ? dt : 0.0;
+        if (OBJ) dtile2 = out_z ? dt2 : 0.0;
       };
       rows(std::integral_constant<bool, OBJK>{});
     } else if (!S2_ABL(2)) {
@@ -1456,6 +1487,14 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
           q += ka0 * pc + st;
         }
         if (accumulate) q += dst[idx];
+        if (OBJK && res_r) {
+          const float r = __fsub_rn(objb[idx], q);
+          const float z = res_M ? __fdiv_rn(r, res_M[idx]) : r;
+          res_r[idx] = r, res_p[idx] = z;
+          dtile += (double)__fmul_rn(r, z);
+          if (res_obj) dtile2 += (double)obj_term(q, objb[idx], pc);
+          continue;
+        }
         matvec_emit(dst, idx, q, pc, objb, P.partials != nullptr, dtile);
       }
     }
@@ -1465,6 +1504,7 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
     ++ptile;
 #endif
     dot += dtile;
+    if (OBJK) dot2 += dtile2;
     t = t_next, rec = rec_next;
   }
 #ifdef UNIRES_S2_PROF
@@ -1473,6 +1513,10 @@ __global__ void __launch_bounds__(kWave *NW) __attribute__((amdgpu_waves_per_eu(
   if (P.partials) {
     const double tot = wave_sum(dot);
     if (lane == 0) P.partials[blockIdx.x * NW + wave] = tot;
+  }
+  if (OBJK && P.partials2) {
+    const double tot2 = wave_sum(dot2);
+    if (lane == 0) P.partials2[blockIdx.x * NW + wave] = tot2;
   }
 }
 
@@ -1524,6 +1568,11 @@ int launch_splat2(const SplatSched &S, const float *src, size_t src_numel, const
   P.A = A, P.alpha = alpha;
   P.p = ep.p, P.a0 = ep.a0, P.cx = ep.cx, P.cy = ep.cy, P.cz = ep.cz;
   P.dst = dst, P.dd = dd, P.accumulate = ep.accumulate, P.partials = ep.partials, P.objb = ep.objb;
+  P.res_r = nullptr, P.res_p = nullptr, P.res_M = nullptr, P.partials2 = nullptr;
+  if (ep.res_r) {
+    if (!ep.res_b || !ep.res_p || !ep.partials || ep.objb) return 1;
+    P.objb = ep.res_b, P.res_r = ep.res_r, P.res_p = ep.res_p, P.res_M = ep.res_M, P.partials2 = ep.res_obj;
+  }
   static const int dbg = getenv("UNIRES_S2_DBG") ? atoi(getenv("UNIRES_S2_DBG")) : 0;
   P.dbg = dbg;
   const dim3 grid(s2_grid(dd, ep.grid_cap)), block(kWave * kS2Waves);
