@@ -271,6 +271,27 @@ int unires_plan_set_diff(unires_plan_t *plan, int32_t which);
  * be 0.  UNIRES_REGIME_IDENTITY has no x-space intermediate: UNIRES_ERR_UNSUPPORTED (build
  * the plan as UNIRES_REGIME_DENOISE with the identity affine instead). */
 int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const float *x, void *stream);
+/* Per-slice weights of repeat n's data term (no counterpart in the reference): u_dev = dim_x[axis] float32 ON THE
+ * DEVICE, one per slice along the caller's voxel axis `axis` (0, 1 or 2; the thick-slice axis dim_thick in
+ * practice), in the caller's slice order.  The data term becomes 1/2 tau_n sum_v u[s(v)] m(v) (x - A y)^2(v), a noise
+ * precision tau_n u_s per slice, and the plan applies A_n^T diag(u . m) A_n wherever it applied A_n^T diag(m) A_n
+ * (m: the mask of unires_plan_set_missing, or 1): the matvec of unires_ata_matvec and of the CG solves, the Jacobi
+ * diagonal tau A^T (u . m . A 1) + 2 rho lam^2 sum 1 / vx^2, the mean diagonal of the FFT preconditioner's symbol.
+ * Unlike a mask the weights change the right-hand side: unires_rhs_assemble and unires_atx_assemble accumulate
+ * tau_n A_n^T (u . x_n), made in the plan's scratch (the observation is not written).  unires_proj_apply keeps the
+ * unweighted A, A^T and A^T A (a mask still applies to its A^T A).  The values are not checked: u >= 0 is the caller's
+ * contract and keeps the system symmetric positive definite.
+ * The plan copies the weights into a buffer it owns whose address does not change while the repeat is weighted; the
+ * copy is enqueued on `stream` and not waited for - work that uses the plan on ANOTHER stream is ordered after it by
+ * the caller, as for unires_plan_set_missing.  A weighted repeat runs forward -> weights (and mask, same pass) ->
+ * push: it declines what a masked repeat declines.  A first set, a clear (u_dev == NULL) or a new axis therefore
+ * rebuilds the repeat's tables where its kernel family changes, waits for the plan's earlier launches, and drops the
+ * captured CG graphs and the built preconditioner.  New VALUES on the same axis rebuild nothing and wait for nothing:
+ * a captured solve is kept and reads the new values from the same buffer when it is replayed; only the built
+ * preconditioner is dropped.  unires_plan_set_repeat keeps the weights (the new descriptor must have the same dim_x;
+ * the canonical axis behind `axis` and its direction follow the new orientation).  Errors: a bad n or axis
+ * UNIRES_ERR_ARG; UNIRES_REGIME_IDENTITY UNIRES_ERR_UNSUPPORTED, as for the mask. */
+int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int32_t axis, const float *u_dev, void *stream);
 /* Bytes of device workspace the plan owns. */
 int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
 /* Which kernels repeat n's operator runs on (no counterpart in the reference, whose _proj_apply
@@ -280,7 +301,7 @@ int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
  * j is reversed, info[4] = 1 if the LDS-window pull serves it, info[5] = 0 if the schedule-driven
  * splat does not serve it, else 2 + its conv_up axis (1: grid-space source, 2..4: along x / y / z, 5: all), info[6] bit 0 = the translation-only one-kernel
  * matvec serves it, bit 1 = the single-pass AtA kernel of the denoising regime does (ata1.hip), bit 2 = the repeat is masked (unires_plan_set_missing:
- * bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
+ * bits 0 and 1 are then clear), bit 3 = the repeat is weighted (unires_plan_set_slice_weights: bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
 int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int32_t info[8]);
 /* The relabelling a plan applies to an operator with grid -> output affine M (host arithmetic only, no device
  * call): perm[j] = caller's voxel axis behind canonical axis j, flip[j] = 1 where it is reversed, chosen so that
@@ -413,6 +434,15 @@ int unires_nll_prior_which(const float *const *y_ptrs, const float *lam, int32_t
 
 /* sum_{x != 0} (x - ay)^2 in float64  (_update.py:414-417; the caller multiplies by tau/2). */
 int unires_masked_sse(const float *x, const float *ay, int64_t n, double *out_dev, void *stream);
+
+/* The same sum per slice (no counterpart in the reference; what per-slice weights are estimated from): x, ay x-space
+ * volumes `dim`, slices counted along dim_thick, S = dim[dim_thick].
+ *   out_dev[s]     = sum_{v in slice s, x != 0} (x - ay)^2
+ *   out_dev[S + s] = #{v in slice s : x != 0}
+ * float32 terms, float64 sums added in a fixed order (no atomics: the same bits every run); every one of the 2 S
+ * entries is written.  out_dev: 2 S doubles on the device. */
+int unires_slice_sums(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick, double *out_dev,
+                      void *stream);
 
 /* Gradient and Hessian sums of one rigid Gauss-Newton step (_update_rigid_channel,
  * _update.py:622-650) in one pass over the grid: gr3 (dim,3) = grid_grad of the pulled image,

@@ -79,6 +79,8 @@ class ChannelPlan:
         self.diff = 'forward'
         self._missing = [None] * len(repeats)  # per repeat: (weak reference, version) of the tensor its mask was built from, or None
         self.mask_zeros = False  # the setting the plan was last fetched with (_project._channel_plan)
+        self._slice_w = [None] * len(repeats)  # per repeat: (weak reference, version, axis) of the weight tensor the plan holds, or None
+        self.weights = False  # whether the plan was last fetched with the observations' slice weights (_channel_plan)
         check(self.lib.unires_plan_create(C.byref(self._h), i3(self.dim_y), f3(vx_y), self.regime,
                                           len(repeats), arr, fov_tol))
         self.dims_x = [self.dim_y if self.regime == REGIME_IDENTITY else tuple(po.dim_x)
@@ -109,15 +111,16 @@ class ChannelPlan:
 
     def repeat_info(self, n):
         """Which kernels repeat n runs on and how its voxel axes were relabelled
-        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused, masked);
+        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused, masked, weighted);
         ``fused``: the single-pass AtA kernel (denoising regime, ata1.hip) serves the CG matvec; ``masked``: the
-        repeat has a validity mask (:meth:`set_missing`) - ``shift`` and ``fused`` are then False."""
+        repeat has a validity mask (:meth:`set_missing`), ``weighted``: per-slice weights
+        (:meth:`set_slice_weights`) - ``shift`` and ``fused`` are then False."""
         info = (C.c_int32 * 8)()
         check(self.lib.unires_plan_repeat_info(self._h, int(n), info))
         v = list(info)
         return dict(perm=tuple(v[:3]), flip=tuple((v[3] >> j) & 1 for j in range(3)), pull2=bool(v[4]),
                     splat2_axis=None if v[5] == 0 else v[5] - 2, shift=bool(v[6] & 1), separable=bool(v[7]),
-                    fused=bool(v[6] & 2), masked=bool(v[6] & 4))
+                    fused=bool(v[6] & 2), masked=bool(v[6] & 4), weighted=bool(v[6] & 8))
 
     @on_device
     def time_matvecs(self, on=True):
@@ -179,6 +182,55 @@ class ChannelPlan:
             if key is not None and key[0]() is t and key[1] == t._version:
                 continue
             self.set_missing(n, t)
+
+    @on_device
+    def set_slice_weights(self, n, axis, w):
+        """Per-slice weights of repeat n's data term (``unires_plan_set_slice_weights``): ``w`` a float32 device tensor
+        with one weight >= 0 per slice along the caller's voxel axis ``axis`` (not checked here: ``fit`` validates the
+        user's once).  The plan's AtA_n becomes A_n^T diag(w) A_n - on top of a mask, where the repeat has one - in
+        the matvec, the CG solves and the preconditioners, and its right-hand side term A_n^T (w . x_n); A and At of
+        :meth:`proj_apply` stay unweighted.  ``w=None`` clears.  The plan keeps a copy: call again when the values
+        change (that rebuilds nothing, a captured solve reads the new values; a first set or a clear changes the
+        repeat's kernels)."""
+        import weakref
+        n, axis = int(n), int(axis)
+        if not 0 <= n < self.n_repeats:
+            raise ValueError('unires_amd: repeat index out of range')
+        if axis not in (0, 1, 2):
+            raise ValueError('unires_amd: slice axis must be 0, 1 or 2')
+        if w is not None and (not w.is_cuda or w.dtype != torch.float32
+                              or tuple(w.shape) != (int(self.dims_x[n][axis]),)):
+            raise ValueError('unires_amd: slice weights must be a float32 device tensor of shape (%d,)'
+                             % int(self.dims_x[n][axis]))
+        self._slice_w[n] = None
+        self._atx = None  # (sum tau At (w . x) follows the weights)
+        if w is None:
+            check(self.lib.unires_plan_set_slice_weights(self._h, n, axis, None, _stream()))
+            return
+        wc = w.contiguous()
+        check(self.lib.unires_plan_set_slice_weights(self._h, int(n), axis, _ptr(wc), _stream()))
+        self._slice_w[n] = (weakref.ref(w), w._version, axis)
+
+    def sync_slice_weights(self, ws):
+        """:meth:`set_slice_weights` for every repeat whose weights are not the tensor, at the version and axis, the
+        plan holds (``ws``: per repeat ``(axis, tensor)`` or None for an unweighted repeat; ``ws=None``: clear all).
+        Free when nothing changed.  Runs on the current stream, like :meth:`sync_missing`: ``_update_y`` fetches its
+        plans before it records the event its channel streams wait for."""
+        for n in range(self.n_repeats):
+            want = None if ws is None else ws[n]
+            key = self._slice_w[n]
+            if want is None:
+                if key is not None:
+                    self.set_slice_weights(n, key[2], None)
+                continue
+            axis, t = want
+            if key is not None and key[0]() is t and key[1] == t._version and key[2] == int(axis):
+                continue
+            self.set_slice_weights(n, axis, t)
+
+    def _slice_key(self):
+        """The weights' part of :meth:`rhs_cached`'s key: (object, version) per repeat."""
+        return tuple(None if k is None else (id(k[0]()), k[1]) for k in self._slice_w)
 
     def set_concurrency(self, n):
         """Tell the plan that ``n`` solves run on the device at once (the channels of a y-update on streams of their
@@ -255,8 +307,8 @@ class ChannelPlan:
     @on_device
     def rhs_cached(self, x_dats, w_c, z_c, rho, lam, out):
         """Same b as :meth:`rhs`, but sum_n tau_n At x_n is kept on the plan and only
-        recomputed when an observation tensor changed (the plan itself is rebuilt when a
-        rigid / scaling / tau changes).  The reference recomputes it every ADMM iteration
+        recomputed when an observation tensor or a repeat's slice weights changed (the plan itself
+        is rebuilt when a rigid / scaling / tau changes).  The reference recomputes it every ADMM iteration
         (unires/_update.py:125-128)."""
         xs = [_vol(t, 'x')[0] for t in x_dats]
         # The cache is keyed on the caller's tensor OBJECTS (weak references) and their version
@@ -264,7 +316,7 @@ class ChannelPlan:
         # 0.  An observation that had to be copied to become contiguous is never cached.
         import weakref
         copied = any(v is not t and v.data_ptr() != t.data_ptr() for v, t in zip(xs, x_dats))
-        key = None if copied else tuple((id(t), t._version) for t in x_dats)
+        key = None if copied else (tuple((id(t), t._version) for t in x_dats), self._slice_key())
         cache = getattr(self, '_atx', None)
         alive = cache is not None and all(r() is t for r, t in zip(cache[2], x_dats)) \
             and len(cache[2]) == len(x_dats)

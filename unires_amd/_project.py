@@ -140,7 +140,9 @@ def _proj_apply(operator, dat, po, method='super-resolution', bound='zero',
 def _plan_regime(method, do, mask_zeros=False):
     """(method, do) a channel's plan is built with.  The user's, but for regime A = I (``do`` false) under
     ``sett.mask_zeros``: that regime's matvec is the flat stencil alone and has no x-space intermediate to mask, so
-    the plan is built in the denoising regime with the identity affine and runs pull -> mask -> push."""
+    the plan is built in the denoising regime with the identity affine and runs pull -> mask -> push.  A channel
+    with a weighted repeat (``_input.slice_w``) takes the same detour: ``_channel_plan`` passes ``mask_zeros`` true
+    for it."""
     if method not in ('denoising', 'super-resolution'):
         raise ValueError('Undefined method')
     if mask_zeros and not do:
@@ -188,21 +190,43 @@ def _plan_signature(x, y, method, do, mask_zeros=False):
     return tuple(sig)
 
 
-def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None):
+def _slice_axis(xn):
+    """The caller's voxel axis the slices of an observation are counted along: ``po.dim_thick`` (the last axis where
+    the descriptor names none)."""
+    a = getattr(xn.po, 'dim_thick', None)
+    return 2 if a is None else int(a)
+
+
+def _slice_weights(x):
+    """Per repeat ``(axis, weights)`` or None, as ``ChannelPlan.sync_slice_weights`` takes them; None when no repeat
+    of the channel has weights."""
+    ws = [None if getattr(xn, 'slice_w', None) is None else (_slice_axis(xn), xn.slice_w) for xn in x]
+    return ws if any(w is not None for w in ws) else None
+
+
+def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weights=None):
     """Fused per-channel plan, cached on the output struct and rebuilt when any
     operator parameter (rigid, scl, tau, dims) changed.  ``diff``: the difference of the plan's D
     ('forward' | 'backward' | 'central'); None leaves the plan's as it is (callers that do not involve D).
     ``mask_zeros``: ``sett.mask_zeros`` - the plan's A^T A treats the zero voxels of each observation as missing
     (``ChannelPlan.set_missing``; the masks follow the observation tensors and their versions); None leaves the plan
-    as it is (callers that apply A or A^T only, which no mask changes)."""
+    as it is (callers that apply A or A^T only, which no mask changes).
+    ``weights``: True - the plan's A^T A and right-hand side carry the per-slice weights ``xn.slice_w`` of the repeats
+    that have some (``ChannelPlan.set_slice_weights``; they follow the weight tensors and their versions); False -
+    the unweighted operator; None leaves the plan as it is."""
     cached = getattr(y, '_plan', None)
     if mask_zeros is None:
         mask_zeros = cached[1].mask_zeros if cached is not None else False
-    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros))
+    if weights is None:
+        weights = cached[1].weights if cached is not None else False
+    ws = _slice_weights(x) if weights else None
+    # (regime A = I has no x-space intermediate for either pass: the denoising regime with the identity affine)
+    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros) or ws is not None)
     if diff is not None:
         plan.set_diff(diff)
     plan.sync_missing([xn.dat for xn in x] if mask_zeros else None)
-    plan.mask_zeros = bool(mask_zeros)
+    plan.sync_slice_weights(ws)
+    plan.mask_zeros, plan.weights = bool(mask_zeros), bool(weights)
     return plan
 
 
@@ -247,9 +271,9 @@ def _proj(operator, dat, x, y, method='super-resolution', do=True, rho=1, n=0, v
     _lib.diff_code(diff, 'diff')
     if bound != 'zero' or interpolation not in ('linear', 1):
         raise NotImplementedError("only bound='zero', linear are built")
-    # (the facade's AtA is the reference's, which has no mask; A and At take the plan as it is)
+    # (the facade's AtA is the reference's, which has no mask and no weights; A and At take the plan as it is)
     plan = _channel_plan(x, y, method, do, vx_y, diff=diff if operator == 'AtA' else None,
-                         mask_zeros=False if operator == 'AtA' else None)
+                         mask_zeros=False if operator == 'AtA' else None, weights=False if operator == 'AtA' else None)
     if operator == 'AtA':
         return plan.matvec(dat, float(rho), float(y.lam))
     if operator not in ('A', 'At'):

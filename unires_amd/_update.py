@@ -9,7 +9,7 @@ from ._lib import check, f3, i3
 from ._ops import _ptr, _stream, on_device
 from ._host import Pacer
 from ._plan import cg_many
-from ._project import _channel_plan, _proj
+from ._project import _channel_plan, _proj, _slice_axis
 from .spatial import voxel_size
 
 
@@ -50,6 +50,12 @@ def _mask_zeros(sett):
     return bool(getattr(sett, 'mask_zeros', False))
 
 
+def _slice_robust(sett):
+    """sett.slice_robust (False where the settings object has none): per-slice weights of every observation are
+    re-estimated from its residuals after each ADMM iteration (``_update_slice_weights``)."""
+    return bool(getattr(sett, 'slice_robust', False))
+
+
 class _Precond:
     """Callable x -> x / M like the lambda unires/_update.py:100 returns; carries the plan
     that holds the device copy of M so cg() can run the preconditioned iteration on device."""
@@ -68,7 +74,7 @@ def _precond(x, y, rho, sett):
     if len(x) != 1:
         raise ValueError('CG pre-conditioning only supports one repeat per contrast.')
     plan = _channel_plan(x, y, sett.method, sett.do_proj, voxel_size(y.mat).float(), diff=_diff(sett),
-                         mask_zeros=_mask_zeros(sett))
+                         mask_zeros=_mask_zeros(sett), weights=True)
     M = torch.empty(tuple(y.dim), dtype=torch.float32, device=y.dat.device)
     plan.precond_build(float(rho), float(y.lam), mode='jacobi', out=M)
     return _Precond(plan, M, 'jacobi')
@@ -101,7 +107,7 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
     if not concurrent:
         for c in range(C):
             plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett),
-                                 mask_zeros=_mask_zeros(sett))
+                                 mask_zeros=_mask_zeros(sett), weights=True)
             plan.set_concurrency(1)
             lam = float(y[c].lam)
             if getattr(sett, 'cache_atx', True) and not sync:
@@ -116,10 +122,10 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
                 info.append(res)
         return y
     main = torch.cuda.current_stream()
-    # the plans first: fetching one may enqueue work on the main stream (the masks of sett.mask_zeros are built there),
-    # and the channel streams wait for `ready` only
+    # the plans first: fetching one may enqueue work on the main stream (the masks of sett.mask_zeros are built there,
+    # the slice weights copied there), and the channel streams wait for `ready` only
     fetched = [_channel_plan(x[c], y[c], sett.method, sett.do_proj, vx_y, diff=_diff(sett),
-                             mask_zeros=_mask_zeros(sett)) for c in range(C)]
+                             mask_zeros=_mask_zeros(sett), weights=True) for c in range(C)]
     ready = torch.cuda.Event()
     ready.record(main)
     streams = _side_streams(y[0].dat.device, C)
@@ -203,16 +209,78 @@ def _update_zw(y, z, w, rho, tmp, sett):
 
 
 @on_device
-def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64):
+def _slice_sums(x, y, sett):
+    """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice weights: SSE_s = sum_{v in s, x != 0}
+    (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick`` (``unires_slice_sums``; float32 terms,
+    float64 sums in a fixed order).  A y is computed once per repeat; the result serves the objective
+    (``_compute_nll``) and the rule (``_update_slice_weights``).  Nothing is read back."""
+    lib = _lib.load()
+    out = {}
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            if getattr(xn, 'slice_w', None) is None:
+                continue
+            Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            xd = xn.dat.contiguous()
+            a = _slice_axis(xn)
+            sums = torch.empty(2 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
+            check(lib.unires_slice_sums(_ptr(xd), _ptr(Ay), i3(xd.shape), a, _ptr(sums), _stream()))
+            out[(c, n)] = sums
+    return out
+
+
+def slice_rule(sums, k):
+    """The variance-ratio rule on one observation's slice sums ((2 S,) float64: SSE_s, then N_s): over the slices
+    with N_s > 0, m_s = SSE_s / N_s and sigma^2 = their LOWER median (the ceil(K / 2)-th smallest of K, torch.median's
+    convention); u_s = 1 where N_s = 0 or m_s <= k^2 sigma^2, else k^2 sigma^2 / m_s; all ones where no slice has
+    data or sigma^2 = 0.  A slice keeps the observation's precision unless its own residual variance exceeds k^2
+    times the typical slice's, and then gets the maximum-likelihood precision its residual supports.  float64 tensor
+    ops on the device of ``sums``, no read-back.  Returns (S,) float64."""
+    S = sums.numel() // 2
+    sse, cnt = sums[:S], sums[S:]
+    has = cnt > 0
+    m = sse / cnt.clamp(min=1.0)
+    K = has.sum()
+    inf = torch.full_like(m, float('inf'))
+    ranked = torch.where(has, m, inf).sort().values
+    sig2 = ranked.gather(0, ((K + 1) // 2 - 1).clamp(min=0).reshape(1))[0]
+    thr = (float(k) * float(k)) * sig2
+    one = torch.ones_like(m)
+    u = torch.where(has & (m > thr), thr / m, one)
+    return torch.where((K > 0) & (sig2 > 0), u, one)
+
+
+@on_device
+def _update_slice_weights(x, y, sett, sums=None):
+    """Re-estimates the slice weights of every observation that has some by ``slice_rule`` with k = sett.slice_k,
+    from the residuals of the current y (``sums``: what ``_slice_sums`` returned for it, computed here when None).
+    The weight tensors are updated in place: their version counters tell the plans (``sync_slice_weights``, at the
+    next y-update's plan fetch) and the cached sum tau At (w . x)."""
+    sums = _slice_sums(x, y, sett) if sums is None else sums
+    k = float(getattr(sett, 'slice_k', 3.0))
+    for (c, n), s in sums.items():
+        x[c][n].slice_w.copy_(slice_rule(s, k))
+    return x
+
+
+@on_device
+def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     """Negative model log-likelihood (unires/_update.py:396-427); returns 0-d float64
-    device tensors (nll_yx, nll_xy, nll_y) without synchronising."""
+    device tensors (nll_yx, nll_xy, nll_y) without synchronising.  A repeat with slice weights contributes
+    1/2 tau sum_s u_s SSE_s (``slice_sums``: ``_slice_sums``' result for this y, computed here when None)."""
     dev = y[0].dat.device
+    if slice_sums is None:
+        slice_sums = _slice_sums(x, y, sett)
     lib = _lib.load()
     vx = [float(v) for v in voxel_size(y[0].mat).tolist()]
     nll_xy = torch.zeros((), dtype=torch.float64, device=dev)
     sse = torch.zeros((), dtype=torch.float64, device=dev)
     for c in range(len(x)):
         for n in range(len(x[c])):
+            if (c, n) in slice_sums:
+                w, s = x[c][n].slice_w, slice_sums[(c, n)]
+                nll_xy = nll_xy + 0.5 * float(x[c][n].tau) * (w.double() * s[:w.numel()]).sum()
+                continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = x[c][n].dat.contiguous()
             check(lib.unires_masked_sse(_ptr(xd), _ptr(Ay), xd.numel(), _ptr(sse), _stream()))
@@ -289,9 +357,14 @@ def _update_admm(x, y, z, w, rho, tmp, obj, n_iter, sett, info=None):
     z-update, w-update - same order, same in-place semantics, `tmp` returned as the
     joint-TV shrinkage image."""
     y = _update_y(x, y, z, w, rho, tmp, sett, info)
-    if obj is not None and sett.tolerance > 0:
-        obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho)
+    want_obj = obj is not None and sett.tolerance > 0
+    # (the per-slice residual sums of the weighted repeats: once, for the objective and for the rule)
+    sums = _slice_sums(x, y, sett) if want_obj or _slice_robust(sett) else None
+    if want_obj:
+        obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums)
     z, w, tmp = _update_zw(y, z, w, rho, tmp, sett)
+    if _slice_robust(sett):  # (after the objective: each iteration's is taken with the weights its y-update used)
+        _update_slice_weights(x, y, sett, sums)
     # An iteration is enqueue-only (no read-back): a host loop would run ahead until the hardware queue is
     # full and then spin inside every launch call.  The pacer parks the thread - sleeping between looks at a
     # stream mark (_host.StreamMark) - until the device is at most `host_pace` iterations behind (settings.host_pace; 0: off).

@@ -494,6 +494,20 @@ extern "C" int unires_masked_sse(const float *x, const float *ay, int64_t n, dou
   return UNIRES_OK;
 }
 
+extern "C" int unires_slice_sums(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
+                                 double *out_dev, void *stream) {
+  if (!x || !ay || !dim || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (dim_thick < 0 || dim_thick > 2) return fail(UNIRES_ERR_ARG, "bad dim_thick");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  const size_t cols = 2 * (size_t)dim[dim_thick];
+  if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), dim_thick), &part)) return rc;
+  launch_slice_sums(x, ay, mk(dim), dim_thick, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 // --------------------------------------------------------------------------
 // Stream marks (round 5): how a host thread follows its GPU WITHOUT runtime calls.
 // Every hipEventQuery / hipStreamQuery on work that is still running makes the runtime submit a marker

@@ -22,6 +22,7 @@
 #include "orient.hpp"
 #include "pull2.hpp"
 #include "shift.hpp"
+#include "slice.hpp"
 #include "splat2.hpp"
 
 namespace unires {
@@ -151,9 +152,31 @@ struct RepeatMask {
   size_t mask_cap = 0;  // entries of either allocation
 };
 
-struct Repeat : RepeatDesc, RepeatTables, RepeatMask {
+// Per-slice weights (unires_plan_set_slice_weights): u, one float per slice along the caller's axis w_axis, in the
+// caller's slice order.  ONE buffer, whatever the orientation: the pass that applies it (slice.hip) is given the
+// canonical axis behind w_axis and whether it is reversed, so unires_plan_set_repeat needs no device work, and the
+// buffer's address stays while the repeat is weighted - a captured solve reads the values it holds when it runs.
+// Sized for the longest axis of the observation at the first set; freed with the plan.
+struct RepeatWeights {
+  bool weighted = false;
+  float *w_dev = nullptr;
+  int w_axis = 0;
+  size_t w_cap = 0;  // entries
+};
+
+struct Repeat : RepeatDesc, RepeatTables, RepeatMask, RepeatWeights {
   // the mask in the layout the x-space intermediate of A^T A has
   const uint8_t *mask() const { return oriented ? mask_c : mask_u; }
+  // a pass runs on the x-space intermediate of A^T A (mask, weights or both): the intermediate has to exist, so the
+  // one-kernel matvecs, the single-pass AtA kernel and the hybrid forms are declined
+  bool mid() const { return masked || weighted; }
+  // the canonical axis the slices of w_axis run along, and whether the plan reversed it
+  int w_caxis() const {
+    for (int j = 0; j < 3; ++j)
+      if (orient.perm[j] == w_axis) return j;
+    return w_axis;
+  }
+  bool w_flip() const { return orient.flip[w_caxis()] != 0; }
 };
 
 // --------------------------------------------------------------------------
@@ -254,7 +277,7 @@ void drop_cg_graph(unires_plan *pl);  // every captured solve of the plan, the c
 // stored (q is still scratch for the partial sums of a multi-repeat operator).
 // Returns the number of partials written (0 if none requested).
 // With res (the start of a CG solve; part and objb unset): a route that can (k_splat2 as the last repeat's push of a
-// forward-difference plan without masked repeats) writes r = b - q, z = r or r / M and the partials of sum r z
+// forward-difference plan without masked or weighted repeats) writes r = b - q, z = r or r / M and the partials of sum r z
 // instead of storing q, and sets res->served; the return value is then the number of those partials.  Any other
 // route ignores it: q is stored as without res, served stays false.
 struct StartResidual {

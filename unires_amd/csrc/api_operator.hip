@@ -60,16 +60,28 @@ static void forward(unires_plan *pl, const Repeat &R, const float *in, const Sca
   }
 }
 
+// The pass on the x-space intermediate of a masked and / or weighted repeat's A^T A: A^T diag(u . m) A, mask and
+// weights in ONE pass (slice.hip); the mask alone stays k_mask_apply's.  diag(u) is diagonal in observation space like
+// diag(m) and commutes with it and with S.  `weights` false: the repeat's unweighted operator (unires_proj_apply's
+// UNIRES_OP_ATA, which stays the reference's).
+static void mid_pass(const Repeat &R, float *buf, bool weights, const int *done, hipStream_t st) {
+  if (R.weighted && weights)
+    launch_slice_apply(buf, buf, R.masked ? R.mask() : nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), done, st);
+  else if (R.masked)
+    launch_mask_apply(buf, R.mask(), R.dim_x.numel(), done, st);
+}
+
 // x-space intermediate of AtA: xbuf = S(2 scl) conv_down pull(in)  (regime 2) or
 // gbuf = pull(in) (regime 1); returns the push source that finishes the operator.  A masked repeat
 // (unires_plan_set_missing) has its intermediate materialised - fill_repeat gave it no hybrid form, so the branch
 // below that fuses conv_down with conv_up is not its - and zeroed where the observation is: A^T diag(m) A.  The mask
-// is 0 / 1 in observation space, where it commutes with the even / odd scaling S.
+// is 0 / 1 in observation space, where it commutes with the even / odd scaling S.  A weighted repeat
+// (unires_plan_set_slice_weights) likewise, multiplied by its slice's weight (mid_pass).
 static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, const int *done,
-                           hipStream_t st) {
+                           hipStream_t st, bool weights = true) {
   if (pl->regime == UNIRES_REGIME_DENOISE) {
     forward(pl, R, in, kNoScaling, pl->gbuf, done, st);
-    if (R.masked) launch_mask_apply(pl->gbuf, R.mask(), R.dim_x.numel(), done, st);
+    mid_pass(R, pl->gbuf, weights, done, st);
     return push_src(R, pl->gbuf, false, 0.f);
   }
   // S(2 scl) once between conv and conv^T  (unires/_project.py:175-177)
@@ -80,7 +92,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
   // grid-source splat) or x- and y-complete (hybrid: the z-profile splat takes it as it is)
   const bool fwd_only = R.hybf && !R.hyb && R.sep && !(R.sched.valid && R.sched.axis >= 0);
   const bool both = R.hyb && R.sched.valid && R.sched.axis == 2 && R.Tf.s[1] == 2;
-  if (!R.masked && push_mode() == PushMode::kDefault && (fwd_only || both) && pl->gbuf2 && R.pplan.valid && R.Tf.s[0] == 2 &&
+  if (!R.mid() && push_mode() == PushMode::kDefault && (fwd_only || both) && pl->gbuf2 && R.pplan.valid && R.Tf.s[0] == 2 &&
       !(R.Tf.n[0] == 1)) {
     // (x taps = Dirac for what follows the x pair; y taps too where conv_up_y went in)
     Taps Ty = R.Txy;
@@ -120,7 +132,7 @@ static PushSrc ata_forward(unires_plan *pl, const Repeat &R, const float *in, co
     }
   }
   forward(pl, R, in, S2, pl->xbuf, done, st);
-  if (R.masked) launch_mask_apply(pl->xbuf, R.mask(), R.dim_x.numel(), done, st);
+  mid_pass(R, pl->xbuf, weights, done, st);
   return push_src(R, pl->xbuf, true, 0.f);
 }
 
@@ -135,14 +147,14 @@ static PushEpilogue without_residual(PushEpilogue ep) {
 // out = [out +] alpha * push(src) [+ epilogue]; falls back to a materialised conv_up when
 // the conv_up fan-in is beyond what the fused kernel tabulates.
 // The residual mode of the epilogue (ep.res_r) is k_splat2's alone and whether a push serves it is decided HERE, in
-// one place: a launch_splat2 that takes the push of an unmasked repeat serves it and *served says so; every other
+// one place: a launch_splat2 that takes the push of a repeat without mask or weights serves it and *served says so; every other
 // kernel gets the epilogue without it.  (What is asked at all is matvec()'s: the mode belongs to the matvec's last
 // push of a forward-difference operator.  ata_apply() strips it for k_ata1, which is not a push.)
 static int push_any(unires_plan *pl, const PushSrc &src, const Repeat &R, float alpha,
                      const PushEpilogue &ep_in, float *out, const int *done, hipStream_t st, bool *served = nullptr) {
   const Affine &A = src.convup ? R.Af : R.A;
   const PushEpilogue ep = without_residual(ep_in);  // what every kernel but k_splat2 is given
-  const PushEpilogue &ep2 = R.masked ? ep : ep_in;   // ... and k_splat2 (a masked repeat declines the mode)
+  const PushEpilogue &ep2 = R.mid() ? ep : ep_in;   // ... and k_splat2 (a masked or weighted repeat declines the mode)
   const auto s2_done = [&] {
     if (served) *served = ep2.res_r != nullptr;
     return ep2.partials ? splat2_blocks(pl->dy, ep2.grid_cap) : 0;
@@ -197,15 +209,22 @@ static int push_any(unires_plan *pl, const PushSrc &src, const Repeat &R, float 
   return ep.partials ? push_tile_blocks(pl->dy) : 0;
 }
 
-// out (+)= alpha * At_n(x)
+// out (+)= alpha * At_n(x); with `weights`, of a weighted repeat: alpha * At_n(u_n . x) - the right-hand side's term.
+// u . x is made in the plan's scratch (the observation is never written): in place on the canonical copy where the
+// plan relabels the observation, else out of place from the caller's volume.
 static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, float *out, float alpha,
-                          bool accumulate, hipStream_t st) {
+                          bool accumulate, hipStream_t st, bool weights = false) {
   if (pl->regime == UNIRES_REGIME_IDENTITY) {
     launch_axpy(alpha, x, out, pl->dy.numel(), st);  // caller initialised out
     return;
   }
+  const bool w = weights && R.weighted;
   if (R.oriented) {  // the caller's voxel layout -> the plan's
     launch_to_canonical(R.orient, x, R.dim_xu, pl->xperm, st);
+    if (w) launch_slice_apply(pl->xperm, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
+    x = pl->xperm;
+  } else if (w) {
+    launch_slice_apply(x, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_axis, false, nullptr, st);
     x = pl->xperm;
   }
   PushEpilogue ep;
@@ -216,18 +235,18 @@ static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, floa
 }
 
 // out (+)= alpha AtA_n(in) [+ epilogue]: pull, push, stencil and dot in ONE pass over `in` where the plan has it
-// (denoising regime, ata1.hip; not a masked repeat, whose intermediate has to exist), else forward + push.  `share`: the persistent kernels' grids leave room for the
+// (denoising regime, ata1.hip; not a masked or weighted repeat, whose intermediate has to exist), else forward + push.  `share`: the persistent kernels' grids leave room for the
 // other channels' solves (unires_plan_set_concurrency).  Returns the number of partials written.
 static int ata_apply(unires_plan *pl, const Repeat &R, const float *in, float alpha, PushEpilogue ep, bool share,
-                     float *out, const int *done, hipStream_t st, bool *served = nullptr) {
+                     float *out, const int *done, hipStream_t st, bool *served = nullptr, bool weights = true) {
   if (served) *served = false;
-  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !R.masked) {
+  if (pl->regime == UNIRES_REGIME_DENOISE && R.f1.valid && !R.mid()) {
     PushEpilogue e1 = without_residual(ep);  // (k_ata1 declines the residual mode)
     e1.grid_cap = share ? pl->cap_f1 : 0;
     if (!launch_ata1(R.f1, in, R.Af, alpha, e1, out, pl->dy, done, st)) return e1.partials ? ata1_blocks(pl->dy, e1.grid_cap) : 0;
   }
   ep.grid_cap = share ? pl->cap_s2 : 0;
-  const PushSrc src = ata_forward(pl, R, in, done, st);
+  const PushSrc src = ata_forward(pl, R, in, done, st, weights);
   return push_any(pl, src, R, alpha, ep, out, done, st, served);
 }
 
@@ -253,7 +272,7 @@ extern "C" int unires_proj_apply(unires_plan_t *plan, int32_t n, int32_t op, con
   } else if (op == UNIRES_OP_AT) {
     at_accumulate(plan, R, in, out, 1.f, false, st);
   } else {
-    ata_apply(plan, R, in, 1.f, PushEpilogue(), false, out, nullptr, st);
+    ata_apply(plan, R, in, 1.f, PushEpilogue(), false, out, nullptr, st, nullptr, false);  // (the unweighted operator)
   }
   CHECK_LAUNCH();
   return UNIRES_OK;
@@ -312,7 +331,7 @@ int unires::matvec(unires_plan *pl, float rho, float lam, const float *p, float 
   // the one-kernel forms of a one-repeat plan: the partials written, or -1 where none applies
   const auto one_kernel = [&]() -> int {
     const Repeat &R = pl->reps[0];
-    if (nrep != 1 || no_aligned() || R.masked) return -1;  // (masked: no intermediate to multiply in one kernel)
+    if (nrep != 1 || no_aligned() || R.mid()) return -1;  // (masked / weighted: no intermediate to multiply in one kernel)
     // translated by a fraction of a voxel (no rotation): the factorised one-kernel matvec.  Where the x-marching
     // kernel's fast form applies it serves integer shifts too (31.5 us against k_ata_aligned4x2's 36 - 37 at 256^3)
     // and is tried first
@@ -464,9 +483,9 @@ extern "C" int unires_rhs_assemble(unires_plan_t *plan, const float *const *x_pt
   mark_use(plan, st);  // (before anything is enqueued: an error return below is remembered too)
   // b = -lam * Dt(w - rho z)   (unires/_update.py:131-133)
   launch_div(w_c, z_c, 1.f, -rho, plan->dy, plan->vx, -lam, nullptr, b, st, plan->diff);
-  // b += tau_n At_n x_n         (unires/_update.py:125-128)
+  // b += tau_n At_n x_n         (unires/_update.py:125-128; At_n (u_n . x_n) for a weighted repeat)
   for (size_t n = 0; n < plan->reps.size(); ++n)
-    at_accumulate(plan, plan->reps[n], x_ptrs[n], b, plan->reps[n].tau, true, st);
+    at_accumulate(plan, plan->reps[n], x_ptrs[n], b, plan->reps[n].tau, true, st, true);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
@@ -482,7 +501,7 @@ extern "C" int unires_atx_assemble(unires_plan_t *plan, const float *const *x_pt
     HIP_TRY(hipMemsetAsync(atx, 0, plan->dy.numel() * sizeof(float), st));
   for (size_t n = 0; n < plan->reps.size(); ++n)
     at_accumulate(plan, plan->reps[n], x_ptrs[n], atx, plan->reps[n].tau,
-                  n > 0 || plan->regime == UNIRES_REGIME_IDENTITY, st);
+                  n > 0 || plan->regime == UNIRES_REGIME_IDENTITY, st, true);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

@@ -397,6 +397,12 @@ static void free_mask(RepeatMask &R) {
   R.mask_cap = 0, R.masked = false;
 }
 
+static void free_weights(RepeatWeights &R) {
+  if (R.w_dev) (void)hipFree(R.w_dev);
+  R.w_dev = nullptr;
+  R.w_cap = 0, R.weighted = false;
+}
+
 // the canonical-layout copy of a masked, relabelled repeat's mask, for the orientation the repeat has now
 static int canonical_mask(Repeat &R, hipStream_t st) {
   if (!R.masked || !R.oriented) return UNIRES_OK;
@@ -497,7 +503,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->last_use) (void)hipEventDestroy(plan->last_use);
   drop_timing(plan);
   fftpre_destroy(plan->fft);
-  for (Repeat &R : plan->reps) free_tables(R), free_mask(R);
+  for (Repeat &R : plan->reps) free_tables(R), free_mask(R), free_weights(R);
   delete plan;
   return UNIRES_OK;
 }
@@ -568,10 +574,14 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   if (!plan || !repeat) return fail(UNIRES_ERR_NULL, "null argument");
   if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
   RepeatDesc tmp;
-  int rc = fill_repeat(plan, repeat, tmp, plan->reps[n].masked);  // (a masked repeat stays masked: no hybrid form)
+  int rc = fill_repeat(plan, repeat, tmp, plan->reps[n].mid());  // (a masked / weighted repeat stays so: no hybrid form)
   if (rc) return rc;
   if (plan->reps[n].masked && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
     return fail(UNIRES_ERR_DIM, "a masked repeat keeps its observation's dims (clear the mask first)");
+  // (the weights stay too: one per slice of the same observation, in the caller's order - the canonical axis behind
+  // them and its direction are read from the new orientation at every launch, no device work here)
+  if (plan->reps[n].weighted && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
+    return fail(UNIRES_ERR_DIM, "a weighted repeat keeps its observation's dims (clear the weights first)");
   if (plan->regime != UNIRES_REGIME_IDENTITY &&
       (tmp.dim_g.numel() > plan->cap_g || tmp.dim_x.numel() > plan->cap_x))
     return fail(UNIRES_ERR_DIM, "new repeat exceeds the plan's workspace");
@@ -615,12 +625,12 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   return rc;
 }
 
-// The family of kernels and the tables of a repeat whose `masked` flag changed (choose_family): rebuilt where the family
+// The family of kernels and the tables of a repeat whose `masked` / `weighted` flags changed (choose_family): rebuilt where the family
 // differs, as unires_plan_set_repeat rebuilds them, but with the thorough schedule builds of unires_plan_create - a mask
 // is set once per observation, and a masked repeat then has the tables of a plan created without hybrid forms.
 static int refamily(unires_plan *pl, Repeat &R) {
   const bool hyb = R.hyb, hybf = R.hybf, sep = R.sep;
-  choose_family(pl, R, R.masked);
+  choose_family(pl, R, R.mid());
   // (a hybrid repeat whose kernels had turned out unavailable was rebuilt by build_repeat_kernels as what it is
   // chosen as now: rebuilding it once more is correct, only not needed)
   if (hyb == R.hyb && hybf == R.hybf && sep == R.sep) return UNIRES_OK;
@@ -647,13 +657,13 @@ extern "C" int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const flo
   await_use(plan);  // (the mask is rewritten: earlier launches may still read it)
   drop_cg_graph(plan);
   plan->prec_ready = false;
-  const bool was = R.masked;
+  const bool was = R.masked, was_mid = R.mid();
   if (x) {
     // every allocation first: a failure leaves the repeat as it was
     const size_t nx = R.dim_xu.numel();
     if (R.mask_cap < nx) {
       free_mask(R);
-      if (was) (void)refamily(plan, R);  // (the old mask is gone with its allocation)
+      if (was_mid != R.mid()) (void)refamily(plan, R);  // (the old mask is gone with its allocation)
       if (hipMalloc((void **)&R.mask_u, nx) != hipSuccess) {
         R.mask_u = nullptr;
         return fail(UNIRES_ERR_ALLOC, "hipMalloc mask");
@@ -671,7 +681,7 @@ extern "C" int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const flo
   } else {
     R.masked = false;
   }
-  if (was != R.masked) {
+  if (was_mid != R.mid()) {  // (a weighted repeat has the two-kernel family already)
     if (int rc = refamily(plan, R)) {
       // the tables of the new family could not be built: back to the state before the call
       R.masked = was;
@@ -680,6 +690,67 @@ extern "C" int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const flo
     }
   }
   CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+// Per-slice weights of repeat n's data term: u_dev holds one float per slice along the caller's axis `axis`, on the
+// device; the plan copies them into a buffer of its own and its A^T A becomes A^T diag(u . m) A (api_operator.hip:
+// mid_pass), its right-hand side term A^T (u . x).  Three kinds of call:
+//   a first set, a clear, a new axis: the repeat's forms change (a weighted repeat declines what a masked one declines:
+//     choose_family, the gates of api_operator.hip), so the plan's earlier launches are waited for, the captured solves
+//     and the preconditioner go, and the tables are rebuilt where the family differs;
+//   new values on the same axis: nothing is rebuilt and nothing waited for.  The copy is enqueued on `stream`, in order
+//     behind that stream's earlier solves; a captured solve is KEPT - it has the buffer's address baked in, which does
+//     not change, and reads the values there when it is replayed.  (Dropping it would cost a capture per ADMM
+//     iteration under sett.slice_robust, which changes the values every iteration.)  The preconditioner is dropped:
+//     the Jacobi diagonal and the FFT symbol's mean follow u; it is rebuilt into the same allocations.
+// The values are not looked at (they are on the device): u >= 0 is the caller's contract.
+extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int32_t axis, const float *u_dev,
+                                             void *stream) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null plan");
+  if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "slice axis: 0, 1 or 2");
+  if (plan->regime == UNIRES_REGIME_IDENTITY)
+    return fail(UNIRES_ERR_UNSUPPORTED,
+                "regime A = I has no x-space intermediate to weight: build the plan in the denoising regime with the "
+                "identity affine");
+  Repeat &R = plan->reps[n];
+  if (!u_dev && !R.weighted) return UNIRES_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool was = R.weighted, was_mid = R.mid();
+  const int was_axis = R.w_axis;
+  const bool values_only = u_dev && was && axis == R.w_axis;
+  plan->prec_ready = false;
+  if (!values_only) {
+    await_use(plan);
+    drop_cg_graph(plan);
+  }
+  if (u_dev) {
+    const int du[3] = {R.dim_xu.x, R.dim_xu.y, R.dim_xu.z};
+    const size_t cap = (size_t)std::max(du[0], std::max(du[1], du[2]));
+    if (R.w_cap < cap) {  // (never while the repeat is weighted: its dims are kept, and the buffer was sized for them)
+      if (R.w_dev) (void)hipFree(R.w_dev);
+      R.w_dev = nullptr, R.w_cap = 0;
+      if (hipMalloc((void **)&R.w_dev, cap * sizeof(float)) != hipSuccess) {
+        R.w_dev = nullptr;
+        return fail(UNIRES_ERR_ALLOC, "hipMalloc slice weights");
+      }
+      R.w_cap = cap;
+    }
+    mark_use(plan, st);
+    HIP_TRY(hipMemcpyAsync(R.w_dev, u_dev, (size_t)du[axis] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    R.weighted = true, R.w_axis = axis;
+  } else {
+    R.weighted = false;
+  }
+  if (was_mid != R.mid()) {  // (a masked repeat has the two-kernel family already)
+    if (int rc = refamily(plan, R)) {
+      // the tables of the new family could not be built: back to the state before the call
+      R.weighted = was, R.w_axis = was_axis;
+      (void)refamily(plan, R);
+      return rc;
+    }
+  }
   return UNIRES_OK;
 }
 
@@ -747,8 +818,9 @@ extern "C" int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int
   info[3] = id ? 0 : (R.orient.flip[0] | (R.orient.flip[1] << 1) | (R.orient.flip[2] << 2));
   info[4] = R.pplan.valid ? 1 : 0;
   info[5] = R.sched.valid ? 2 + R.sched.axis : 0;
-  // (the forms the matvec takes: a masked repeat skips the one-kernel matvec and the single-pass AtA kernel)
-  info[6] = (R.shift.valid && !R.masked ? 1 : 0) | (R.f1.valid && !R.masked ? 2 : 0) | (R.masked ? 4 : 0);
+  // (the forms the matvec takes: a masked or weighted repeat skips the one-kernel matvec and the single-pass AtA kernel)
+  info[6] = (R.shift.valid && !R.mid() ? 1 : 0) | (R.f1.valid && !R.mid() ? 2 : 0) | (R.masked ? 4 : 0) |
+            (R.weighted ? 8 : 0);
   info[7] = R.sep ? 1 : 0;
   return UNIRES_OK;
 }

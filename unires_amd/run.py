@@ -48,6 +48,35 @@ def _clean_fov(x, y):
     return y
 
 
+def _init_slice_weights(x, sett, dev):
+    """The observations' slice weights as the iterations take them: a user's ``_input.slice_w`` validated (one weight
+    per slice along ``po.dim_thick``, finite, >= 0 - the one read-back) and moved to the device as float32; with
+    ``sett.slice_robust`` all ones where there are none, so that the plans' kernels do not change mid-fit."""
+    from ._project import _slice_axis
+    robust = bool(getattr(sett, 'slice_robust', False))
+    if robust and not float(getattr(sett, 'slice_k', 3.0)) > 0:
+        raise ValueError('sett.slice_k must be positive')
+    for c, xc in enumerate(x):
+        for n, xn in enumerate(xc):
+            w = getattr(xn, 'slice_w', None)
+            if w is None and not robust:
+                continue
+            S = int(xn.dat.shape[_slice_axis(xn)])
+            if w is None:
+                xn.slice_w = torch.ones(S, dtype=torch.float32, device=dev)
+                continue
+            w = torch.as_tensor(w)
+            if tuple(w.shape) != (S,):
+                raise ValueError('x[%d][%d].slice_w has shape %s, expected (%d,): one weight per slice along axis %d'
+                                 % (c, n, tuple(w.shape), S, _slice_axis(xn)))
+            if w.is_complex() or w.dtype == torch.bool:
+                raise ValueError('x[%d][%d].slice_w must be real numbers' % (c, n))
+            w = w.detach().to(device=dev, dtype=torch.float32)
+            if not bool((torch.isfinite(w) & (w >= 0)).all()):
+                raise ValueError('x[%d][%d].slice_w must be finite and >= 0' % (c, n))
+            xn.slice_w = w.clone() if w is xn.slice_w else w
+
+
 @on_device
 def fit(x, y, sett):
     """Fit model (unires/run.py:24-207).  ``x[c][n]`` / ``y[c]`` are the _input / _output
@@ -56,11 +85,14 @@ def fit(x, y, sett):
 
     Returns (dat_y, mat_y, R, info): reconstructions stacked to (dim_y, C) float32, the
     output affine, the rigid matrices (N, 4, 4) and a dict with the objective trace
-    ``obj`` (n_iter, 3), the iteration count and the regularisation schedule."""
+    ``obj`` (n_iter, 3), the iteration count, the regularisation schedule and ``slice_w``: per channel a list with
+    each repeat's final slice weights (a CPU float32 tensor, one per slice along ``po.dim_thick``) or None for a
+    repeat without weights."""
     if len(x) != len(y):
         raise ValueError('one output per channel')
     with torch.no_grad():
         dev = y[0].dat.device
+        _init_slice_weights(x, sett, dev)
         N = sum(len(xc) for xc in x)
         sett = _get_sched(N, sett)
         cnt_scl = 0
@@ -111,7 +143,8 @@ def fit(x, y, sett):
             y = _clean_fov(x, y)
         R = torch.stack([xn.po.rigid.double().cpu() for xc in x for xn in xc])
         dat_y = torch.stack([yc.dat for yc in y], dim=-1)
-        info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone())
+        slice_w = [[None if getattr(xn, 'slice_w', None) is None else xn.slice_w.detach().cpu() for xn in xc] for xc in x]
+        info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w)
         return dat_y, y[0].mat, R, info
 
 

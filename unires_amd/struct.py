@@ -19,6 +19,11 @@ class _input:
         self.sd = 1.0
         self.rigid_q = None
         self.label = None   # [dat, header] of a manual label volume (_util._read_label)
+        # per-slice weights of the data term, float32 (dim[po.dim_thick],), >= 0: None - every slice has weight 1.
+        # Set before fit() to distrust known slices (used as given with sett.slice_robust off; fit() validates them
+        # once and moves them to the device); with sett.slice_robust fit() starts from ones where None and
+        # re-estimates them every ADMM iteration
+        self.slice_w = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
         self.fname = None
@@ -78,6 +83,13 @@ class settings:
         # guess): the solve minimises the data term _compute_nll reports (ChannelPlan.set_missing).  Off: the
         # reference's system, which pulls the reconstruction towards 0 wherever an observation is zero-filled.
         self.mask_zeros = False
+        # build-side knobs: robust slice outlier rejection.  slice_robust: after every ADMM iteration each observation's
+        # slices get a weight from their residuals (_update.slice_rule): 1 unless a slice's residual variance exceeds
+        # slice_k^2 times the median slice's, then the ratio.  The y-update's data term becomes
+        # 1/2 tau sum_v u[s(v)] (x - A y)^2(v) (ChannelPlan.set_slice_weights).  slice_k = 3 is a modelling default
+        # nobody has tuned on real data.  Off: every slice has weight 1 unless the user set _input.slice_w.
+        self.slice_robust = False
+        self.slice_k = 3.0
         self.gap = 0.0
         self.interpolation = 'linear'
         self.method = None
