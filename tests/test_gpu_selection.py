@@ -67,7 +67,7 @@ json.dump(out, open(sys.argv[1], 'w'))
 
 
 def test_one_pass_schedule_build_equals_the_two_pass_build(tmp_path):
-    """The splat's schedule is built in ONE pass into per-tile staging slots and compacted (splat2.hip,
+    """The splat's schedule is built in ONE pass into per-tile staging slots and compacted (splat2_sched.hip,
     k_splat2_build<2> + k_splat2_compact); UNIRES_S2_BUILD_2PASS=1 runs the count + fill passes of rounds 2-4.
     Same schedule, bit for bit - seen through bit-identical matvecs: thick slices along z, along x / y, all three
     axes (the extended entries), the Gaussian in-plane profile and the pull / push regime."""

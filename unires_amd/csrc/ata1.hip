@@ -16,17 +16,13 @@
 // rebuilds in set_repeat) or, point by point on the shared planes, cells >= 2 apart in x or y (the exact
 // rule, plan creation - k_f1_build).  The schedule is fixed: results are bit-reproducible.
 #include "ata1.hpp"
-#include "splat2.hpp"
 
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
 #include <vector>
 
 namespace unires {
@@ -46,29 +42,7 @@ constexpr int kF1TZ = 30, kF1SZ = 32;
 constexpr unsigned kF1KBias = 64u, kF1KMask = 0x1fffu;  // pk = (k of lane 0 + bias) | first lane << 13 | len << 19
 constexpr int kF1MaxSeg = 8;  // segments per instruction
 
-struct F1TileGeom {
-  int x0, y0, z0, ex, ey, ez;
-};
-template <int TX, int TY>
-__host__ __device__ __forceinline__ F1TileGeom f1_tile(int t, const Dim3i &dd) {
-  const int nty = (dd.y + TY - 1) / TY, ntz = (dd.z + kF1TZ - 1) / kF1TZ;
-  const int tzi = t % ntz, tyi = (t / ntz) % nty, txi = t / (ntz * nty);
-  F1TileGeom g;
-  g.x0 = txi * TX, g.y0 = tyi * TY, g.z0 = tzi * kF1TZ;
-  g.ex = min(TX, dd.x - g.x0), g.ey = min(TY, dd.y - g.y0), g.ez = min(kF1TZ, dd.z - g.z0);
-  return g;
-}
-static int f1_ntiles(Dim3i dd, int tx, int ty) {
-  return ((dd.x + tx - 1) / tx) * ((dd.y + ty - 1) / ty) * ((dd.z + kF1TZ - 1) / kF1TZ);
-}
-
-// coordinate of grid point k of a row with base (rx, ry, rz): affine_along() / s2_point(), bit for bit
-__device__ __forceinline__ void f1_point(const Affine &A, float rx, float ry, float rz, float kf, float &gx,
-                                         float &gy, float &gz) {
-  gx = fmaf(A.m[2], kf, rx) + A.m[3];
-  gy = fmaf(A.m[6], kf, ry) + A.m[7];
-  gz = fmaf(A.m[10], kf, rz) + A.m[11];
-}
+static int f1_ntiles(Dim3i dd, int tx, int ty) { return tile_count(dd, tx, ty, kF1TZ); }
 
 // --------------------------------------------------------------------------
 // schedule build: one wave per tile
@@ -96,97 +70,14 @@ __global__ void __launch_bounds__(kWave)
   __shared__ F1Seg segs[kSegs];
   __shared__ unsigned short order[kSegs], tmp[kSegs];
   const int lane = threadIdx.x;
-  const Dim3i dd = B.dd;
   const int slot = blockIdx.x;
   const int t = geom ? geom[slot] : slot;
-  const F1TileGeom g = f1_tile<TX, TY>(t, dd);
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  const float flx = (float)(g.x0 - 1), fly = (float)(g.y0 - 1), flz = (float)(g.z0 - 1);
-  const float fhx = (float)(g.x0 + g.ex), fhy = (float)(g.y0 + g.ey), fhz = (float)(g.z0 + g.ez);
-  // acceptance box of a point: floor cell inside the aproned tile AND inside the field of view
-  const float tlo = nextafterf(-B.tol, 1.f);
-  const float tlx = fmaxf(flx, tlo), tly = fmaxf(fly, tlo), tlz = fmaxf(flz, tlo);
-  const float thx = fminf(fhx, (float)(dd.x - 1) + B.tol), thy = fminf(fhy, (float)(dd.y - 1) + B.tol),
-              thz = fminf(fhz, (float)(dd.z - 1) + B.tol);
-  float lo0 = 1e30f, lo1 = 1e30f, lo2 = 1e30f, hi0 = -1e30f, hi1 = -1e30f, hi2 = -1e30f;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    float ux, uy, uz;
-    affine_point(B.Ainv, (c & 4) ? fhx : flx, (c & 2) ? fhy : fly, (c & 1) ? fhz : flz, ux, uy, uz);
-    lo0 = fminf(lo0, ux), hi0 = fmaxf(hi0, ux);
-    lo1 = fminf(lo1, uy), hi1 = fmaxf(hi1, uy);
-    lo2 = fminf(lo2, uz), hi2 = fmaxf(hi2, uz);
-  }
-  const int bx0 = max(0, (int)floorf(lo0 - 0.01f)), bx1 = min(B.gd.x - 1, (int)ceilf(hi0 + 0.01f));
-  const int by0 = max(0, (int)floorf(lo1 - 0.01f)), by1 = min(B.gd.y - 1, (int)ceilf(hi1 + 0.01f));
-  const int bz0 = max(0, (int)floorf(lo2 - 0.01f) - 1), bz1 = min(B.gd.z - 1, (int)ceilf(hi2 + 0.01f) + 1);
-  const int nby = by1 - by0 + 1;
-  const int nrow_cand = max(bx1 - bx0 + 1, 0) * max(nby, 0);
-  const float c0 = B.A.m[2], c1 = B.A.m[6], c2 = B.A.m[10];
-  int nseg = 0;
-  for (int rc0 = 0; rc0 < nrow_cand; rc0 += kWave) {
-    const int rc = rc0 + lane;
-    int ui = 0, uj = 0, k0 = 0, k1 = -1;
-    RowBase rb{0.f, 0.f, 0.f};
-    if (rc < nrow_cand) {
-      const int a = rc / nby, b = rc - a * nby;
-      ui = bx0 + a, uj = by0 + b;
-      rb = affine_row(B.A, (float)ui, (float)uj);
-      k0 = bz0, k1 = bz1;
-      // slab clipping in real arithmetic gives a superset (with slack) of the accepted interval ...
-      const float rr[3] = {rb.x + B.A.m[3], rb.y + B.A.m[7], rb.z + B.A.m[11]}, cc[3] = {c0, c1, c2};
-      const float lw[3] = {flx, fly, flz}, hg[3] = {fhx, fhy, fhz};
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        if (fabsf(cc[d]) > 1e-6f) {
-          float ta = (lw[d] - rr[d]) / cc[d], tb = (hg[d] - rr[d]) / cc[d];
-          const float tmin = fminf(ta, tb), tmax = fmaxf(ta, tb);
-          ta = fmaxf(tmin, -1e6f), tb = fminf(tmax, 1e6f);
-          k0 = max(k0, (int)ceilf(ta - 2e-3f - 1e-5f * fabsf(ta)) - 1);
-          k1 = min(k1, (int)floorf(tb + 2e-3f + 1e-5f * fabsf(tb)) + 1);
-        } else if (rr[d] < lw[d] - 0.01f || rr[d] >= hg[d] + 0.01f) {
-          k1 = k0 - 1;
-        }
-      }
-      // ... then exactly: the accepted points of a row form an interval (every rounding in f1_point is
-      // monotone in k), so shrinking from both ends finds it
-      auto accept = [&](int k) {
-        float gx, gy, gz;
-        f1_point(B.A, rb.x, rb.y, rb.z, (float)k, gx, gy, gz);
-        return gx >= tlx && gx < thx && gy >= tly && gy < thy && gz >= tlz && gz < thz;
-      };
-      while (k0 <= k1 && !accept(k0)) ++k0;
-      while (k1 >= k0 && !accept(k1)) --k1;
-    }
-    // cut into segments: <= 32 points, every point exactly one z plane above its predecessor
-    int cur = k0;
-    bool more = k1 >= k0;
-    while (__any(more)) {
-      int e = cur;
-      float za = 0.f;
-      if (more) {
-        float gx, gy, gz;
-        f1_point(B.A, rb.x, rb.y, rb.z, (float)cur, gx, gy, gz);
-        float plz = floorf(gz);
-        za = plz;
-        while (e + 1 <= k1 && e + 1 - cur < kF1SZ) {
-          f1_point(B.A, rb.x, rb.y, rb.z, (float)(e + 1), gx, gy, gz);
-          const float lz = floorf(gz);
-          if (lz != plz + 1.f) break;
-          plz = lz;
-          ++e;
-        }
-      }
-      const unsigned long long m = __ballot(more);
-      const int pos = nseg + __popcll(m & lt_mask);
-      if (more && pos < kSegs)
-        segs[pos] = F1Seg{(short)ui, (short)uj, (short)cur, (unsigned char)(e - cur + 1),
-                          (unsigned char)((int)za - (g.z0 - 1))};
-      nseg += __popcll(m);
-      cur = e + 1;
-      more = more && cur <= k1;
-    }
-  }
+  const TileBox g = tile_box<TX, TY, kF1TZ>(t, B.dd);
+  const float flx = (float)(g.x0 - 1), fly = (float)(g.y0 - 1);
+  // segments: <= 32 points, every point exactly one z plane above its predecessor
+  int nseg = sched_scan_rows<kF1SZ, SegCut::kPlaneNotNext, kSegs>(B, g, lane, [&](int pos, int ui, int uj, int k0, int len, float za, float) {
+    segs[pos] = F1Seg{(short)ui, (short)uj, (short)k0, (unsigned char)len, (unsigned char)((int)za - (g.z0 - 1))};
+  });
   if (nseg > kSegs) {
     if (lane == 0) atomicExch(err, 1);
     nseg = kSegs;
@@ -245,11 +136,13 @@ __global__ void __launch_bounds__(kWave)
       const RowBase ra = affine_row(B.A, (float)m.ui, (float)m.uj), rq = affine_row(B.A, (float)q.ui, (float)q.uj);
       for (int pl = lo; pl <= hi; ++pl) {
         float ax, ay, az, bx, by, bz;
-        f1_point(B.A, ra.x, ra.y, ra.z, (float)((int)m.k0 + pl - (int)m.pos), ax, ay, az);
-        f1_point(B.A, rq.x, rq.y, rq.z, (float)((int)q.k0 + pl - (int)q.pos), bx, by, bz);
-        // (the kernel floors g - (tile0 - 1): for a tile on the volume's low faces the base is -1 and an accepted
-        // in-tolerance point with g in (-6e-8, 0) rounds g + 1 to 1.0 - its cell moves from -1 to 0; the test uses
-        // the kernel's local arithmetic, not the floor of the global coordinate)
+        sched_point(B.A, ra.x, ra.y, ra.z, (float)((int)m.k0 + pl - (int)m.pos), ax, ay, az);
+        sched_point(B.A, rq.x, rq.y, rq.z, (float)((int)q.k0 + pl - (int)q.pos), bx, by, bz);
+        // (The cells are floored as the STREAM kernel floors them, which differs between the two schedules on purpose.
+        // k_ata1 floors g - (tile0 - 1): for a tile on the volume's low faces the base is -1 and an accepted
+        // in-tolerance point with g in (-6e-8, 0) rounds g + 1 to 1.0 - its cell moves from -1 to 0 - so this test
+        // uses the local arithmetic, ADVICE r5.  k_splat2 floors the global coordinate since round 6 took the
+        // subtraction in front of v_fract out, and splat2_sched.hip's test floors that.)
         if (fabsf(floorf(ax - flx) - floorf(bx - flx)) < 2.f && fabsf(floorf(ay - fly) - floorf(by - fly)) < 2.f) {
           free = false;
           break;
@@ -364,10 +257,8 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   static const bool off = getenv("UNIRES_NO_ATA1") != nullptr;
   static const bool verbose = getenv("UNIRES_ATA1_VERBOSE") != nullptr;
   if (off) return 1;
-  if (safe.use_atomics) return 1;
   if (!(A.m[10] > 0.f)) return 1;  // lane = z plane needs grid z to run up the output's z (canonical layout)
-  if (dd.x > 4000 || dd.y > 4000 || dd.z > 4000 || gd.x > 4000 || gd.y > 4000 || gd.z > 4000) return 1;
-  if (!fits_fast_index(gd) || !fits_fast_index(dd) || dd.numel() >= (1ull << 30)) return 1;
+  if (!sched_in_domain(gd, dd, safe)) return 1;
   int tx, ty;
   f1_shape(tx, ty);
   const int nt = f1_ntiles(dd, tx, ty);
@@ -383,8 +274,7 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
     if (hipMalloc((void **)&S.tile_org, ((size_t)nt + 1) * sizeof(uint2)) != hipSuccess) return 1;
     S.cap_tiles = (size_t)nt + 1;
   }
-  if (!S.scratch && hipMalloc((void **)&S.scratch, 4 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  (void)hipMemset(S.scratch, 0, 4 * sizeof(unsigned long long));
+  if (!sched_scratch_clear(S.scratch)) return 1;
   int *err_dev = (int *)S.scratch;
   unsigned long long *stats_dev = S.scratch + 1;
   F1BuildArgs B;
@@ -392,7 +282,7 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   static const int pack = getenv("UNIRES_F1_PACK") ? atoi(getenv("UNIRES_F1_PACK")) : 1;
   B.pack = pack;
   static const int exact = getenv("UNIRES_F1_EXACT") ? atoi(getenv("UNIRES_F1_EXACT")) : -1;  // (-1: as the plan asks)
-  B.exact = exact >= 0 ? exact : (sched_thorough() ? 1 : 0);
+  B.exact = sched_exact(exact);
   auto run = [&](bool fill, const int *geom) {
     if (tx == 8)
       f1_launch_build<8, 4>(fill, B, nt, S.tile_off, geom, S.desc, S.hdr, err_dev, fill ? stats_dev : nullptr);
@@ -406,36 +296,12 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   if (hipMemcpy(cnt2.data(), S.tile_off, (size_t)nt * sizeof(uint2), hipMemcpyDeviceToHost) != hipSuccess) return 1;
   std::vector<unsigned> cnt((size_t)nt);
   for (int i = 0; i < nt; ++i) cnt[i] = cnt2[i].y;
-  // Processing order, as the splat's (splat2_build): contiguous runs of tiles per XCD with equal COST (a
-  // tile costs its instructions + a constant for staging and epilogue); inside a run the tiles with (next
-  // to) no instructions go last, emptiest at the very end.
+  // Processing order (sched_order): one run of tiles of equal COST per XCD - a tile costs its instructions + a
+  // constant for staging and epilogue - the tiles with (next to) no instructions last; no y strips (1 MB slabs of
+  // 4 x 4 tiles fit the L2 anyway).
   static const double kTileCost = getenv("UNIRES_F1_TILE_COST") ? atof(getenv("UNIRES_F1_TILE_COST")) : 5.0;
   std::vector<int> geom((size_t)nt + 1);
-  {
-    double total = 0.0;
-    unsigned imax = 0;
-    for (int i = 0; i < nt; ++i) total += (double)cnt[i] + kTileCost, imax = std::max(imax, cnt[i]);
-    int x = 1;
-    double cum = 0.0;
-    S.xcd_lo[0] = 0;
-    for (int i = 0; i < nt && x < 8; ++i) {
-      cum += (double)cnt[i] + kTileCost;
-      while (x < 8 && cum >= total * x / 8.0) S.xcd_lo[x++] = i + 1;
-    }
-    for (; x <= 8; ++x) S.xcd_lo[x] = nt;
-    const unsigned cheap = imax / 2u;
-    for (int xc = 0; xc < 8; ++xc) {
-      const int lo = S.xcd_lo[xc], hi = S.xcd_lo[xc + 1];
-      int u = lo;
-      for (int g = lo; g < hi; ++g)
-        if (cnt[g] > cheap) geom[u++] = g;
-      const int first_cheap = u;
-      for (int g = lo; g < hi; ++g)
-        if (cnt[g] <= cheap) geom[u++] = g;
-      std::stable_sort(geom.begin() + first_cheap, geom.begin() + hi, [&](int a, int b) { return cnt[a] > cnt[b]; });
-    }
-    geom[nt] = 0;
-  }
+  sched_order(cnt.data(), nt, kTileCost, 8, S.xcd_lo, geom.data());
   unsigned re = 0, ri = 0;
   for (int u = 0; u < nt; ++u) {
     h[u] = make_uint2(re, ri);
@@ -443,20 +309,8 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   }
   h[nt] = make_uint2(re, ri);
   constexpr size_t kPad = 16;  // entries / headers read (never used) past the end by the prefetch
-  if ((size_t)re + kPad > S.cap_entries) {
-    if (S.desc) (void)hipFree(S.desc);
-    S.desc = nullptr;
-    const size_t cap = (size_t)re + re / 8 + kPad;
-    if (hipMalloc((void **)&S.desc, cap * sizeof(uint4)) != hipSuccess) return 1;
-    S.cap_entries = cap;
-  }
-  if ((size_t)ri + 64 + kPad > S.cap_instr) {
-    if (S.hdr) (void)hipFree(S.hdr);
-    S.hdr = nullptr;
-    const size_t cap = (size_t)ri + ri / 8 + 64 + kPad;  // (a wave reads 64 headers from its tile's first on)
-    if (hipMalloc((void **)&S.hdr, cap * sizeof(uint4)) != hipSuccess) return 1;
-    S.cap_instr = cap;
-  }
+  if (!sched_grow(S.desc, S.cap_entries, (size_t)re, kPad)) return 1;
+  if (!sched_grow(S.hdr, S.cap_instr, (size_t)ri, 64 + kPad)) return 1;  // (a wave reads 64 headers from its tile's first on)
   if (hipMemcpy(S.tile_off, h.data(), ((size_t)nt + 1) * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)
     return 1;
   if (hipMemcpy(S.tile_geom, geom.data(), ((size_t)nt + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
@@ -464,7 +318,9 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   {
     std::vector<uint2> org((size_t)nt + 1);
     for (int u = 0; u <= nt; ++u) {
-      const F1TileGeom g = tx == 8 ? f1_tile<8, 4>(geom[u], dd) : tx == 6 ? f1_tile<6, 4>(geom[u], dd) : f1_tile<4, 4>(geom[u], dd);
+      const TileBox g = tx == 8   ? tile_box<8, 4, kF1TZ>(geom[u], dd)
+                        : tx == 6 ? tile_box<6, 4, kF1TZ>(geom[u], dd)
+                                  : tile_box<4, 4, kF1TZ>(geom[u], dd);
       org[u] = make_uint2((unsigned)g.x0 | ((unsigned)g.y0 << 16), (unsigned)g.z0);
     }
     if (hipMemcpy(S.tile_org, org.data(), ((size_t)nt + 1) * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) return 1;
@@ -474,8 +330,7 @@ int ata1_build(F1Sched &S, const Affine &A, const Affine &Ainv, Dim3i gd, Dim3i 
   run(true, S.tile_geom);
   int herr = 0;
   unsigned long long hs[2] = {0, 0};
-  if (hipMemcpy(&herr, err_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 1;
-  if (hipMemcpy(hs, stats_dev, sizeof(hs), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (!sched_scratch_read(S.scratch, herr, hs)) return 1;
   if (herr) {
     if (verbose) fprintf(stderr, "[ata1] a tile exceeds the segment / instruction lists: two-kernel path used\n");
     return 1;
@@ -693,6 +548,7 @@ __global__ void __launch_bounds__(kWave *NW) k_ata1(F1Args P, const int *__restr
       const int kb = (int)(pk & kF1KMask) - (int)kF1KBias;
       const unsigned pos = (pk >> 13) & 63u, len = pk >> 19;
       const float kf = (float)(kb + lane);
+      // (sched_point's arithmetic, bit for bit, on hoisted coefficients: the call itself compiles to another stream)
       const float gx = fmaf(c0, kf, __uint_as_float(d.x)) + t0;
       const float gy = fmaf(c1, kf, __uint_as_float(d.y)) + t1;
       const float gz = fmaf(c2, kf, __uint_as_float(d.z)) + t2;
@@ -839,11 +695,8 @@ __global__ void __launch_bounds__(kWave *NW) k_ata1(F1Args P, const int *__restr
 }
 
 static int f1_grid(Dim3i dd, int tx, int ty, int share_cap = 0) {
-  const int nt = f1_ntiles(dd, tx, ty);
   static const int cap_env = getenv("UNIRES_F1_BLOCKS") ? atoi(getenv("UNIRES_F1_BLOCKS")) : 0;
-  const int cap = cap_env > 0 ? cap_env : (share_cap >= 8 ? share_cap : 1024);
-  const int want = (nt + kF1Waves - 1) / kF1Waves;
-  return want < cap ? want : cap;
+  return persistent_grid(f1_ntiles(dd, tx, ty), kF1Waves, cap_env, share_cap);
 }
 
 int ata1_blocks(Dim3i dd, int grid_cap) {
@@ -858,26 +711,13 @@ static const void *f1_fn(int tx) {
                    : (const void *)k_ata1<4, 4, kF1Waves, 0>;
 }
 
-// workgroups the device holds at once, rounded down to whole rounds over the 8 XCDs
+// workgroups of k_ata1<tx> that take tiles (sched.hpp)
 static int f1_active(int tx, int grid) {
-  static std::map<int, int> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(tx);
-  if (it == cache.end()) {
-    int per_cu = 0, dev = 0, ncu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f1_fn(tx), kWave * kF1Waves, 0) != hipSuccess) per_cu = 0;
-    static const int force = getenv("UNIRES_F1_RESIDENT") ? atoi(getenv("UNIRES_F1_RESIDENT")) : 0;
-    if (force > 0) per_cu = force;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 0;
-    const int n = per_cu > 0 && ncu > 0 ? per_cu * ncu : 1 << 30;
-    static const bool verbose = getenv("UNIRES_ATA1_VERBOSE") != nullptr;
-    if (verbose) fprintf(stderr, "[ata1] %d workgroups per CU resident (tile %d x 4)\n", per_cu, tx);
-    it = cache.emplace(tx, n).first;
-  }
-  int n = std::min(grid, it->second);
-  if (n >= 8) n -= n % 8;
+  static const int force = getenv("UNIRES_F1_RESIDENT") ? atoi(getenv("UNIRES_F1_RESIDENT")) : 0;
+  static const bool verbose = getenv("UNIRES_ATA1_VERBOSE") != nullptr;
+  int per_cu = -1;
+  const int n = resident_workgroups(f1_fn(tx), kWave * kF1Waves, grid, force, &per_cu);
+  if (verbose && per_cu >= 0) fprintf(stderr, "[ata1] %d workgroups per CU resident (tile %d x 4)\n", per_cu, tx);
   return n;
 }
 

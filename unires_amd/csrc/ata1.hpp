@@ -9,11 +9,12 @@
 // No grid- or x-space intermediate exists, no second kernel, no second read of p.
 //
 // Which grid points a tile visits is fixed by the operator: a per-operator schedule (ata1_build,
-// once per plan / set_repeat) lists, per tile, 64-lane instructions of row segments (lane = z plane
+// once per plan / set_repeat; the row scan and the processing order are sched.hpp's, shared with
+// k_splat2's) lists, per tile, 64-lane instructions of row segments (lane = z plane
 // of the point inside each 32-lane half, so LDS banks never collide and lanes of a half never
 // share a cell) whose footprints provably cannot meet.  16 bytes per segment and per instruction.
 #pragma once
-#include "fused.hpp"
+#include "sched.hpp"
 
 namespace unires {
 

@@ -1,4 +1,4 @@
-// splat2.hpp - schedule-driven owner-computes push (splat2.hip).
+// splat2.hpp - schedule-driven owner-computes push (the stream: splat2.hip; its schedule: splat2_sched.hip, on sched.hpp).
 //
 // The affine of an operator is constant for thousands of matvecs, so everything about
 // "which grid points land in which output tile" is computed ONCE per operator by a build
@@ -14,7 +14,7 @@
 // floor/fract, 14 products and two dense 4-cell read-add-write groups (z plane, then z+1
 // plane) per 64 lanes.
 #pragma once
-#include "fused.hpp"
+#include "sched.hpp"
 
 namespace unires {
 
@@ -67,13 +67,6 @@ int splat2_build(SplatSched &S, const Affine &A, const Affine &Ainv, Dim3i gd, D
                  const SplatSafety &safe, int axis, int rows_y, const float4 *xtab = nullptr,
                  const float4 *ytab = nullptr, Dim3i xd = Dim3i{0, 0, 0});
 void splat2_free(SplatSched &S);
-
-// How hard the schedule builders (splat2_build, ata1_build) of the calling thread try: thorough = rows closer than
-// row_sep are tested point by point (a better lane fill, 2 - 4 x the build time); quick = kept apart wholesale.
-// The plan builds thoroughly once (unires_plan_create) and quickly whenever an operator changes under a running
-// reconstruction (unires_plan_set_repeat: every rigid Gauss-Newton step).
-void sched_set_thorough(bool on);
-bool sched_thorough();
 
 int splat2_blocks(Dim3i dd, int grid_cap = 0);  // (grid_cap: PushEpilogue::grid_cap of the launch)
 // tab_dev: gn float4 {bits(koff), w0, w1, -} conv_up table along the schedule's axis (nullptr for
