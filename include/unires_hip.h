@@ -469,6 +469,22 @@ int unires_clean_fov(float *y, const int32_t dim_y[3], const float M[12], const 
 int unires_scaling_sums(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
                         double *out_dev, void *stream);
 
+/* The same five sums of the weighted data term 1/2 tau sum_v u[s(v)] [x != 0] (x - ay)^2 (per-slice weights; no
+ * counterpart in the reference): every term above times the weight of its voxel's slice along dim_thick.  u_dev: a
+ * DEVICE pointer to dim[dim_thick] floats, NULL is UNIRES_ERR_NULL.  A term is the float32 term of
+ * unires_scaling_sums times the float32 weight, the product taken in float64 (exact); float64 sums in a fixed order,
+ * no atomics: the same bits every run, and with u = 1 the bits of unires_scaling_sums. */
+int unires_scaling_sums_w(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
+                          const float *u_dev, double *out_dev, void *stream);
+
+/* The x-space residual of one rigid Gauss-Newton step (_rigid_match, _update.py:515-519) in one pass:
+ *   out[v] = u[s(v)] * (ay[v] - x[v])  where x[v] != 0 and ay[v] != 0, else +0
+ * x, ay, out: volumes `dim`; s(v) = v's index along `axis`; u_dev: a DEVICE pointer to dim[axis] floats, or NULL
+ * (weight 1: the unweighted residual, bit for bit).  float32: the difference and the product round once each.
+ * out == ay is allowed; x is only read. */
+int unires_rigid_resid(const float *x, const float *ay, const int32_t dim[3], int32_t axis, const float *u_dev,
+                       float *out, void *stream);
+
 /* ------------------------------------------------------------------------
  * Stream marks: following a stream from the host by reading memory.
  * Not part of the reference (single process, unires/run.py); it serves the one-process-per-GPU batch

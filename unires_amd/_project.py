@@ -193,7 +193,12 @@ def _plan_signature(x, y, method, do, mask_zeros=False):
 def _slice_axis(xn):
     """The caller's voxel axis the slices of an observation are counted along: ``po.dim_thick`` (the last axis where
     the descriptor names none)."""
-    a = getattr(xn.po, 'dim_thick', None)
+    return _thick_axis(xn.po)
+
+
+def _thick_axis(po):
+    """``po.dim_thick``, the last axis where the descriptor names none."""
+    a = getattr(po, 'dim_thick', None)
     return 2 if a is None else int(a)
 
 

@@ -23,7 +23,8 @@ from . import _lib, _ops
 from ._host import light_host
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
-from ._project import _apply_scaling, _proj_info, _taps
+from ._project import _apply_scaling, _proj_info, _slice_axis, _taps, _thick_axis
+from ._update import _slice_ll
 from .spatial import _m12
 
 _F64 = torch.float64
@@ -98,10 +99,17 @@ def _grid_matrix(po, rigid, method):
 
 
 @on_device
-def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False):
+def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None):
     """ll and, if ``diff``, the raw ingredients of the derivatives: gr3 (dim,3) = grid_grad,
-    dg (dim) = residual in grid space."""
+    dg (dim) = residual in grid space.
+
+    ``slice_w``: the repeat's slice weights along ``axis`` of ``dat_x`` (float32, on the device, one per slice of
+    ``dat_x`` - already decimated where ``dat_x`` is), or None.  With weights the terms are those of the weighted data
+    term 1/2 tau sum_v u[s(v)] [x != 0] (x - A y)^2: ll = 1/2 tau sum_s u_s SSE_s from ``unires_slice_sums``
+    (``_update._slice_ll``, the objective's own expression) and the x-space residual u[s(v)] (A y - x), masked, in one
+    pass (``unires_rigid_resid``).  Without, the code path is what it was."""
     method = sett.method
+    lib = _lib.load()
     mat, dim = _grid_matrix(po, rigid, method)
     M = _m12(mat)
     dat_yx = _ops.pull_affine(dat_y, M, dim)
@@ -109,44 +117,77 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False):
         scl = float(po.scl)
         dat_yx = _ops.conv_down(dat_yx, _taps(po), po.ratio, scl, po.dim_thick)
     dat_yx = dat_yx.reshape(tuple(dat_x.shape))
-    sse = torch.zeros((), dtype=_F64, device=dat_x.device)
-    check(_lib.load().unires_masked_sse(_ptr(dat_x), _ptr(dat_yx), dat_x.numel(), _ptr(sse),
-                                        _stream()))
-    ll = 0.5 * float(tau) * sse
+    if slice_w is None:
+        sse = torch.zeros((), dtype=_F64, device=dat_x.device)
+        check(lib.unires_masked_sse(_ptr(dat_x), _ptr(dat_yx), dat_x.numel(), _ptr(sse), _stream()))
+        ll = 0.5 * float(tau) * sse
+    else:
+        dat_x, dat_yx, slice_w = dat_x.contiguous(), dat_yx.contiguous(), slice_w.contiguous()
+        if slice_w.dtype != torch.float32 or slice_w.numel() != dat_x.shape[axis]:
+            raise ValueError('slice_w: one float32 weight per slice of dat_x along axis %d' % axis)
+        sums = torch.empty(2 * slice_w.numel(), dtype=_F64, device=dat_x.device)
+        check(lib.unires_slice_sums(_ptr(dat_x), _ptr(dat_yx), i3(dat_x.shape), axis, _ptr(sums), _stream()))
+        ll = _slice_ll(tau, slice_w, sums)
     if not diff:
         return ll, None, None
     gr3 = _ops.pull_grad_affine(dat_y, M, dim).reshape(dim + (3,))
-    d = dat_yx - dat_x
-    d[(dat_x == 0) | (dat_yx == 0)] = 0  # :517-519
+    if slice_w is None:
+        d = dat_yx - dat_x
+        d[(dat_x == 0) | (dat_yx == 0)] = 0  # :517-519
+    else:
+        d = dat_yx  # (in place: A y is not needed again)
+        check(lib.unires_rigid_resid(_ptr(dat_x), _ptr(dat_yx), i3(dat_x.shape), axis, _ptr(slice_w), _ptr(d),
+                                     _stream()))
     if method == 'super-resolution':
         d = _ops.conv_up(d, _taps(po), po.ratio)  # no slice scaling here (:524)
     return ll, gr3, d.reshape(dim).contiguous()
 
 
 @on_device
-def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0):
+def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None):
     """Rigid matching term with the reference's return shapes (unires/_update.py:448-538):
-    ll, gr (dim, 3) = grid_grad * residual, Hes (dim, 6) = outer(grid_grad) [* CtC]."""
-    ll, gr3, d = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=diff)
+    ll, gr (dim, 3) = grid_grad * residual, Hes (dim, 6) = outer(grid_grad) [* CtC].
+    ``slice_w``: the observation's slice weights along ``po.dim_thick`` (``_rigid_terms``); the Hessian's weight is the
+    caller's ``CtC`` (``_ctc`` with the same weights)."""
+    ll, gr3, d = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=diff, slice_w=slice_w,
+                              axis=None if slice_w is None else _thick_axis(po))
     if not diff:
         return ll, None, None
     Hes = torch.stack([gr3[..., 0] * gr3[..., 0], gr3[..., 1] * gr3[..., 1], gr3[..., 2] * gr3[..., 2],
                        gr3[..., 0] * gr3[..., 1], gr3[..., 0] * gr3[..., 2], gr3[..., 1] * gr3[..., 2]], -1)
-    if sett.method == 'super-resolution':
+    if sett.method == 'super-resolution' or (slice_w is not None and CtC is not None):
         Hes = Hes * CtC[..., None]
     return ll, gr3 * d[..., None], Hes
 
 
-def _ctc(po, dim, device):
-    """conv_transpose(conv(1)) (unires/_update.py:603-607)."""
+def _spread(slice_w, shape, axis):
+    """The (S,) weights as a view of ``shape``: u[s(v)] at every voxel, s counted along ``axis``."""
+    view = [1, 1, 1]
+    view[axis] = int(shape[axis])
+    return slice_w.reshape(view).expand(tuple(int(v) for v in shape))
+
+
+def _ctc(po, dim, device, slice_w=None, axis=None):
+    """conv_transpose(conv(1)) (unires/_update.py:603-607); with slice weights conv_transpose(u . conv(1)): the
+    weights applied in x space between the two halves (times 1 is exact: u = 1 gives the unweighted bits)."""
     ones = torch.ones(dim, dtype=torch.float32, device=device)
-    return _ops.conv_up(_ops.conv_down(ones, _taps(po), po.ratio), _taps(po), po.ratio).contiguous()
+    low = _ops.conv_down(ones, _taps(po), po.ratio)
+    if slice_w is not None:
+        low = low * _spread(slice_w, low.shape, axis)
+    return _ops.conv_up(low, _taps(po), po.ratio).contiguous()
 
 
 @on_device
 @light_host
 def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbose=0, samp=3, c=1):
-    """Updates the rigid parameters of all images of one channel (unires/_update.py:541-710)."""
+    """Updates the rigid parameters of all images of one channel (unires/_update.py:541-710).
+
+    A repeat with slice weights (``xn.slice_w``, a float32 device tensor as ``fit()`` leaves it) takes its step on
+    the weighted data term: the objective of the step and of every line-search evaluation, the residual and the
+    Hessian's weight - conv_transpose(u . conv(1)), or the volume u[s(v)] in the denoising regime - all carry the
+    weights, decimated with the observation (``u[::sk[a]][:dim_x[a]]``) and built once per repeat.  A repeat whose
+    weights are all zero has a zero Hessian: its ``rigid_q`` and ``po.rigid`` are left as they are and it adds 0 to
+    ``sll``.  A repeat without weights runs exactly what it ran before."""
     lib = _lib.load()
     dev = yc.dat.device
     method = sett.method
@@ -172,13 +213,20 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
         sk = getattr(po, 'sk', (1, 1, 1))
         dat_x = xn.dat[::sk[0], ::sk[1], ::sk[2]][:po.dim_x[0], :po.dim_x[1], :po.dim_x[2]].contiguous()
         dat_y = yc.dat
-        CtC = _ctc(po, dim, dev) if method == 'super-resolution' else None
+        u = getattr(xn, 'slice_w', None)
+        a = _slice_axis(xn)
+        if u is None:
+            CtC = _ctc(po, dim, dev) if method == 'super-resolution' else None
+        else:
+            u = u[::sk[a]][:po.dim_x[a]].contiguous()
+            CtC = _ctc(po, dim, dev, u, a) if method == 'super-resolution' else _spread(u, dat_x.shape, a).contiguous()
+        empty = False
         ll = torch.zeros((), dtype=_F64, device=dev)
         rigid = _expm(q, basis)
         for _gn in range(max_niter_gn):
             rigid, d_rigid = _expm(q, basis, grad_X=True)
             D = torch.stack([torch.linalg.solve(po.mat_y, d_rigid[i].mm(mat)) for i in range(num_q)])
-            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True)
+            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a)
             d72 = (C.c_float * 72)(*D[:, :3, :].reshape(-1).float().tolist())
             check(lib.unires_rigid_sums(_ptr(gr3), _ptr(dg), _ptr(CtC) if CtC is not None else None,
                                         i3(dim), d72, _ptr(sums), _stream()))
@@ -186,6 +234,9 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
             Hes = np.zeros((num_q, num_q))
             Hes[iu] = s[num_q:]
             Hes = Hes + np.triu(Hes, 1).T
+            if u is not None and not Hes.any():  # (all weights zero: no data term, no step - nothing to solve)
+                empty = True
+                break
             Update = torch.from_numpy(np.linalg.solve(Hes, s[:num_q]))
             old_ll, old_q, old_rigid = ll.clone(), q.clone(), rigid.clone()
             if num_linesearch == 0:
@@ -195,7 +246,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
                 for n_ls in range(num_linesearch):
                     q = old_q - armijo * Update
                     rigid = _expm(q, basis)
-                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett)[0]
+                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a)[0]
                     if bool(ll < old_ll):
                         armijo = min(1.25 * armijo, 1.0)
                         if verbose >= 1:
@@ -204,6 +255,8 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
                         break
                     ll, q, rigid = old_ll, old_q, old_rigid
                     armijo *= 0.5
+        if empty:
+            continue
         xn.rigid_q = q
         xn.po.rigid = rigid
         sll = sll + ll

@@ -263,6 +263,14 @@ def _update_slice_weights(x, y, sett, sums=None):
     return x
 
 
+def _slice_ll(tau, w, sums):
+    """1/2 tau sum_s u_s SSE_s of one weighted repeat: ``w`` its (S,) weights, ``sums`` its ``unires_slice_sums``
+    ((2 S,) float64: SSE_s, then N_s).  A float64 dot product on the device, no read-back.  The one statement of a
+    weighted repeat's data term: the objective (``_compute_nll``) and the rigid update's line search take it from
+    here."""
+    return 0.5 * float(tau) * (w.double() * sums[:w.numel()]).sum()
+
+
 @on_device
 def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     """Negative model log-likelihood (unires/_update.py:396-427); returns 0-d float64
@@ -278,8 +286,7 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     for c in range(len(x)):
         for n in range(len(x[c])):
             if (c, n) in slice_sums:
-                w, s = x[c][n].slice_w, slice_sums[(c, n)]
-                nll_xy = nll_xy + 0.5 * float(x[c][n].tau) * (w.double() * s[:w.numel()]).sum()
+                nll_xy = nll_xy + _slice_ll(x[c][n].tau, x[c][n].slice_w, slice_sums[(c, n)])
                 continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = x[c][n].dat.contiguous()
@@ -300,7 +307,12 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
     of ten masked-index passes; the step logic - including the reference's line search, which
     rescales the already rescaled ``dat_y`` after a rejected step (:362-366) - runs on the host
     with one 40-byte read-back per evaluation.  ``po.rigid`` is used where the reference
-    recomputes the same matrix from ``rigid_q`` (:301).  Returns (x, sll)."""
+    recomputes the same matrix from ``rigid_q`` (:301).  Returns (x, sll).
+
+    A repeat with slice weights (``xn.slice_w``, a float32 device tensor as ``fit()`` leaves it) minimises its own data
+    term 1/2 tau sum_v u[s(v)] [x != 0] (x - A y)^2: every one of the five sums carries the weight of the voxel's slice
+    (``unires_scaling_sums_w``).  A repeat whose weights are all zero has no data term: its ``po.scl`` is left as it
+    is and it adds 0 to ``sll``.  A repeat without weights runs exactly what it ran before."""
     from ._project import _apply_scaling
     if sett.method != 'super-resolution':
         raise ValueError('_update_scaling needs the super-resolution projection '
@@ -319,18 +331,28 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
             plan = _channel_plan(x[c], y[c], sett.method, sett.do_proj)
             dat_x = xn.dat.contiguous()
             dat_y = plan.proj_apply(n_x, 'A', y[c].dat)  # pull + conv + S(scl)  (:316-322)
+            u = getattr(xn, 'slice_w', None)
+            u = None if u is None else u.contiguous()
 
             def evaluate(ay):
-                check(lib.unires_scaling_sums(_ptr(dat_x), _ptr(ay), i3(dat_x.shape), dim_thick,
-                                              _ptr(sums), _stream()))
+                if u is None:
+                    check(lib.unires_scaling_sums(_ptr(dat_x), _ptr(ay), i3(dat_x.shape), dim_thick,
+                                                  _ptr(sums), _stream()))
+                else:
+                    check(lib.unires_scaling_sums_w(_ptr(dat_x), _ptr(ay), i3(dat_x.shape), dim_thick, _ptr(u),
+                                                    _ptr(sums), _stream()))
                 return sums.tolist()  # one small device-to-host copy
 
             ll = 0.0
+            empty = False
             for _ in range(max_niter_gn):
                 s = evaluate(dat_y)
                 ll = 0.5 * tau * s[0]
                 gr = tau * (s[1] - s[2])
                 hes = tau * (s[3] + s[4])
+                if u is not None and hes == 0.0:  # (all weights zero: no data term, no step - not the 0 / 0 below)
+                    empty = True
+                    break
                 update = float(torch.tensor(gr, dtype=torch.float64) / torch.tensor(hes, dtype=torch.float64))  # IEEE: 0/0 -> nan, like the reference's tensors
                 old_scl, old_ll, armijo = scl, ll, 1.0
                 if num_linesearch == 0:
@@ -346,6 +368,8 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
                         armijo *= 0.5
                 if verbose >= 1:
                     print('c={}, n={} | exp(s)={:.5f} ll={:.2f}'.format(c, n_x, torch.tensor(scl).exp(), ll))
+            if empty:
+                continue
             po.scl = scl  # the next _channel_plan() call rebuilds the operator with it
             sll = sll + ll
     return x, sll

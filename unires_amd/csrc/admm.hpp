@@ -17,9 +17,10 @@ void launch_sum_cols(const double *part, int nb, int ncols, double *out, hipStre
 void launch_zw_update(const float *y, float lam, const float *scale, float *z, float *w, Dim3i d,
                       const float vx[3], float rho, float alpha, hipStream_t st, int which = kDiffForward);
 int scaling_sums_blocks(Dim3i d);
-// part: 5 * scaling_sums_blocks(d) doubles of scratch (per-workgroup sums, added in index order)
-void launch_scaling_sums(const float *x, const float *y, Dim3i d, int dim_thick, double *part, double *out,
-                         hipStream_t st);
+// part: 5 * scaling_sums_blocks(d) doubles of scratch (per-workgroup sums, added in index order); u: d[dim_thick]
+// slice weights on the device (every term times the weight of its slice), or nullptr (= 1)
+void launch_scaling_sums(const float *x, const float *y, Dim3i d, int dim_thick, const float *u, double *part,
+                         double *out, hipStream_t st);
 int rigid_sums_blocks(Dim3i dm);
 // part: 27 * rigid_sums_blocks(dm) doubles of scratch
 void launch_rigid_sums(const float *gr3, const float *diff, const float *ctc, Dim3i dm,

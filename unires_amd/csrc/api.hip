@@ -451,7 +451,20 @@ extern "C" int unires_scaling_sums(const float *x, const float *ay, const int32_
   hipStream_t st = (hipStream_t)stream;
   double *part = nullptr;
   if (int rc = reduce_scratch(st, 5 * (size_t)scaling_sums_blocks(mk(dim)), &part)) return rc;
-  launch_scaling_sums(x, ay, mk(dim), dim_thick, part, out_dev, st);
+  launch_scaling_sums(x, ay, mk(dim), dim_thick, nullptr, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_scaling_sums_w(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
+                                     const float *u_dev, double *out_dev, void *stream) {
+  if (!x || !ay || !dim || !u_dev || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (dim_thick < 0 || dim_thick > 2) return fail(UNIRES_ERR_ARG, "bad dim_thick");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  if (int rc = reduce_scratch(st, 5 * (size_t)scaling_sums_blocks(mk(dim)), &part)) return rc;
+  launch_scaling_sums(x, ay, mk(dim), dim_thick, u_dev, part, out_dev, st);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }
@@ -504,6 +517,16 @@ extern "C" int unires_slice_sums(const float *x, const float *ay, const int32_t 
   const size_t cols = 2 * (size_t)dim[dim_thick];
   if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), dim_thick), &part)) return rc;
   launch_slice_sums(x, ay, mk(dim), dim_thick, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_rigid_resid(const float *x, const float *ay, const int32_t dim[3], int32_t axis,
+                                  const float *u_dev, float *out, void *stream) {
+  if (!x || !ay || !dim || !out) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
+  launch_rigid_resid(x, ay, out, u_dev, mk(dim), axis, (hipStream_t)stream);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

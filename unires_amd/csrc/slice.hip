@@ -5,6 +5,7 @@
 //   k_slice_apply: buf[v] *= u[s(v)] on the x-space intermediate between the forward half of A^T A and its push
 //     (A^T diag(u . m) A), with the validity mask of mask.hip in the same pass; out of place it makes u . x for the
 //     right-hand side.
+//   k_rigid_resid: u[s(v)] (A y - x), masked - the residual of the rigid Gauss-Newton step on the same data term.
 #include <algorithm>
 
 #include "slice.hpp"
@@ -150,6 +151,71 @@ __global__ void __launch_bounds__(kBlock) k_slice_apply(const float *src, float 
   }
 }
 
+// one voxel of the rigid step's residual: w (ay - x) where both are non-zero (_rigid_terms' mask), else +0
+__device__ __forceinline__ float resid_term(float xv, float av, float w) {
+  return (xv != 0.f && av != 0.f) ? __fmul_rn(w, __fsub_rn(av, xv)) : 0.f;
+}
+
+// out = u[s(v)] (ay - x), masked: the residual of the rigid Gauss-Newton step in one pass (four volume-sized tensor
+// passes before: difference, two comparisons, masked store).  k_slice_apply's shape: 16-byte loads and stores whatever
+// the row length, (i, j, k) of a thread's group of four kept by carry arithmetic, a group that crosses a row end
+// stepped through voxel by voxel, the voxels from 4 n4 on one by one (n4 = 0 for a buffer off its boundary).  Without
+// W the weight is 1 - times 1 is exact - and no position is kept.  out may be ay: a thread reads its group before it
+// stores it, and no other thread touches the group.
+template <bool W>
+__global__ void __launch_bounds__(kBlock) k_rigid_resid(const float *__restrict__ x, const float *ay, float *out,
+                                                        const float *__restrict__ u, Dim3i d, int axis, int si, int sj,
+                                                        int sk, size_t n4, size_t n) {
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, step = (size_t)gridDim.x * kBlock;
+  const size_t plane = (size_t)d.y * d.z;
+  const auto weight = [&](int i, int j, int k) { return W ? u[axis == 0 ? i : (axis == 1 ? j : k)] : 1.f; };
+  if (tid < n4) {
+    int i = 0, j = 0, k = 0;
+    if (W) {
+      const size_t e0 = 4 * tid;
+      if (n <= 0xffffffffull) {  // (uniform: the usual case, without 64-bit divisions)
+        const unsigned e = (unsigned)e0, pl = (unsigned)plane, r = e / (unsigned)d.z;
+        i = (int)(e / pl), j = (int)(r - (unsigned)i * (unsigned)d.y), k = (int)(e - r * (unsigned)d.z);
+      } else {
+        i = (int)(e0 / plane), j = (int)((e0 % plane) / d.z), k = (int)(e0 % d.z);
+      }
+    }
+    for (size_t g = tid; g < n4; g += step) {
+      float w[4] = {1.f, 1.f, 1.f, 1.f};
+      if (W) {
+        if (axis != 2 && k + 3 < d.z) {  // (axes 0 and 1: the weight is uniform over a z-row, and the group stays in its row)
+          w[0] = w[1] = w[2] = w[3] = weight(i, j, k);
+        } else {
+          int ie = i, je = j, ke = k;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            w[e] = weight(ie, je, ke);
+            if (++ke == d.z) {
+              ke = 0;
+              if (++je == d.y) je = 0, ++ie;
+            }
+          }
+        }
+      }
+      const float4 xv = *reinterpret_cast<const float4 *>(x + 4 * g);
+      const float4 av = *reinterpret_cast<const float4 *>(ay + 4 * g);
+      float4 v;
+      v.x = resid_term(xv.x, av.x, w[0]), v.y = resid_term(xv.y, av.y, w[1]);
+      v.z = resid_term(xv.z, av.z, w[2]), v.w = resid_term(xv.w, av.w, w[3]);
+      *reinterpret_cast<float4 *>(out + 4 * g) = v;
+      if (W) {
+        k += sk;
+        if (k >= d.z) k -= d.z, ++j;
+        j += sj;
+        if (j >= d.y) j -= d.y, ++i;  // (j + carry + sj <= 2 dy - 1: once)
+        i += si;
+      }
+    }
+  }
+  for (size_t e = 4 * n4 + tid; e < n; e += step)
+    out[e] = resid_term(x[e], ay[e], weight((int)(e / plane), (int)((e % plane) / d.z), (int)(e % d.z)));
+}
+
 }  // namespace
 
 int slice_sums_parts(Dim3i d, int axis) {
@@ -198,6 +264,25 @@ void launch_slice_apply(const float *src, float *dst, const uint8_t *mask, const
   else
     hipLaunchKernelGGL(k_slice_apply<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, dst, mask, u, d, axis,
                        flip ? 1 : 0, si, sj, sk, n4, n, done);
+}
+
+void launch_rigid_resid(const float *x, const float *ay, float *out, const float *u, Dim3i d, int axis,
+                        hipStream_t st) {
+  const size_t n = d.numel();
+  if (!n) return;
+  const bool aligned = (((uintptr_t)x | (uintptr_t)ay | (uintptr_t)out) & 15) == 0;
+  const size_t n4 = aligned ? n / 4 : 0;
+  // launch_slice_apply's grid and stride decode
+  const size_t work = aligned ? n4 + 3 : n;
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((work + kBlock - 1) / kBlock, 2048));
+  const size_t se = 4 * blocks * kBlock, plane = (size_t)d.y * d.z;
+  const int si = (int)(se / plane), sj = (int)((se % plane) / d.z), sk = (int)(se % d.z);
+  if (u)
+    hipLaunchKernelGGL(k_rigid_resid<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, out, u, d, axis, si, sj,
+                       sk, n4, n);
+  else
+    hipLaunchKernelGGL(k_rigid_resid<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, out, u, d, axis, si, sj,
+                       sk, n4, n);
 }
 
 }  // namespace unires

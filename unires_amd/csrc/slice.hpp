@@ -18,4 +18,10 @@ void launch_slice_sums(const float *x, const float *ay, Dim3i d, int axis, doubl
 void launch_slice_apply(const float *src, float *dst, const uint8_t *mask, const float *u, Dim3i d, int axis,
                         bool flip, const int *done, hipStream_t st);
 
+// The x-space residual of the rigid Gauss-Newton step (_rigid.py): out[v] = u[s(v)] * (ay[v] - x[v]) where x[v] != 0
+// and ay[v] != 0, else +0; float32, one rounding each for the difference and the product.  u == nullptr: weight 1,
+// the bits of the unweighted residual.  out == ay is allowed; x is only read.
+void launch_rigid_resid(const float *x, const float *ay, float *out, const float *u, Dim3i d, int axis,
+                        hipStream_t st);
+
 }  // namespace unires

@@ -87,7 +87,11 @@ def fit(x, y, sett):
     output affine, the rigid matrices (N, 4, 4) and a dict with the objective trace
     ``obj`` (n_iter, 3), the iteration count, the regularisation schedule and ``slice_w``: per channel a list with
     each repeat's final slice weights (a CPU float32 tensor, one per slice along ``po.dim_thick``) or None for a
-    repeat without weights."""
+    repeat without weights.
+
+    Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
+    ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
+    ``_update_rigid``).  Under ``sett.slice_robust`` they see the weights ``_update_admm`` has just re-estimated."""
     if len(x) != len(y):
         raise ValueError('one output per channel')
     with torch.no_grad():

@@ -22,7 +22,9 @@ class _input:
         # per-slice weights of the data term, float32 (dim[po.dim_thick],), >= 0: None - every slice has weight 1.
         # Set before fit() to distrust known slices (used as given with sett.slice_robust off; fit() validates them
         # once and moves them to the device); with sett.slice_robust fit() starts from ones where None and
-        # re-estimates them every ADMM iteration
+        # re-estimates them every ADMM iteration.  They define the observation's data term: the y-update, the objective
+        # and the scaling and rigid Gauss-Newton updates (sett.scaling, sett.unified_rigid) all minimise it - a slice
+        # of weight 0 reaches none of them
         self.slice_w = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
@@ -85,8 +87,9 @@ class settings:
         self.mask_zeros = False
         # build-side knobs: robust slice outlier rejection.  slice_robust: after every ADMM iteration each observation's
         # slices get a weight from their residuals (_update.slice_rule): 1 unless a slice's residual variance exceeds
-        # slice_k^2 times the median slice's, then the ratio.  The y-update's data term becomes
-        # 1/2 tau sum_v u[s(v)] (x - A y)^2(v) (ChannelPlan.set_slice_weights).  slice_k = 3 is a modelling default
+        # slice_k^2 times the median slice's, then the ratio.  The data term becomes
+        # 1/2 tau sum_v u[s(v)] (x - A y)^2(v) - in the y-update (ChannelPlan.set_slice_weights), the objective and the
+        # scaling and rigid updates, which see the weights just re-estimated.  slice_k = 3 is a modelling default
         # nobody has tuned on real data.  Off: every slice has weight 1 unless the user set _input.slice_w.
         self.slice_robust = False
         self.slice_k = 3.0
