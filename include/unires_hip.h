@@ -330,6 +330,8 @@ int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last);
 /* How the plan's last solve was enqueued at its two ends (see unires_cg_solve): *trimmed (nullable) = 1 if its last
  * iteration updated x alone, *start_fused (nullable) = 1 if the operator's last kernel wrote the start's residual. */
 int unires_plan_cg_ends(unires_plan_t *plan, int32_t *trimmed, int32_t *start_fused);
+/* 1 if the plan's last solve ran inside the two-lane schedule of unires_cg_solve_many (see there), else 0. */
+int unires_plan_cg_lockstep(unires_plan_t *plan);
 
 /* _proj_apply(operator, ., po_n)  (_project.py:99-190) for repeat n, WITHOUT tau.
  * in/out sizes follow the operator (A: dim_y -> dim_x; At: dim_x -> dim_y; AtA: dim_y -> dim_y). */
@@ -398,7 +400,21 @@ int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const float *b, f
  * not couple inside the y-update): n plans, each with its own b, x, rho, lam and stream (all HOST
  * arrays of n entries).  One host loop feeds the chunks of all of them, so channels on separate
  * streams keep overlapping on the device.  iters_out: n ints or NULL (non-NULL synchronises every
- * stream); obj_trace: n x (min(max_iter, 4096) + 1) doubles or NULL. */
+ * stream); obj_trace: n x (min(max_iter, 4096) + 1) doubles or NULL.
+ * With UNIRES_CG_LOCKSTEP=1 (read once per process; off by default: measured slower, experiments/E20), fixed-iteration
+ * solves (tol == 0, max_iter > 0, identity or Jacobi preconditioner) of n >= 2 plans, none in timing mode, no stream
+ * under capture, at least two different streams among `streams`, are enqueued as ONE
+ * two-lane schedule - the operator applications of all channels in rotation on streams[0], their scalar and vector
+ * kernels in the same rotation on the first other stream, so that a channel's vector phase runs under the next
+ * channel's operator - captured once into one hipGraph (two parallel branches) and replayed while every channel's
+ * arguments and plan stay what they were.  streams[0] waits for every channel stream before the graph and every
+ * channel stream for the graph's end, so the caller orders its work as for free-running solves.  Per channel the
+ * kernels, arguments and order are unires_cg_solve's: x is the same bits as that plan's solve alone with the same
+ * grids (the mode has its own cap on k_splat2's grid, UNIRES_LOCKSTEP_S2, in unires_plan_set_concurrency's unit).
+ * The switch also takes the flush of the deferred iterate update in two halves of four directions (fewer registers,
+ * the same bits).  GPU_MAX_HW_QUEUES below 4 (read once: the runtime is not trusted with branched graphs on fewer
+ * hardware queues) and a refused capture keep the free-running solves.  unires_plan_cg_lockstep tells which way a
+ * plan's last solve went. */
 int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, const float *rho, const float *lam,
                          const float *const *b, float *const *x, int32_t max_iter, double tol,
                          int32_t stop_mode, int32_t precond_mode, int32_t *iters_out,

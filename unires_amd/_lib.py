@@ -83,6 +83,7 @@ SIGNATURES = {
     'unires_plan_matvec_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     'unires_plan_cg_ring': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     'unires_plan_cg_ends': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'unires_plan_cg_lockstep': (C.c_int, [C.c_void_p]),
     'unires_proj_apply': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     'unires_ata_matvec': (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,

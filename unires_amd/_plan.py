@@ -137,6 +137,11 @@ class ChannelPlan:
         check(self.lib.unires_plan_cg_ring(self._h, int(k), C.byref(last)))
         return int(last.value)
 
+    @property
+    def cg_lockstep(self):
+        """Whether the plan's last solve ran inside the channels' two-lane schedule (``unires_plan_cg_lockstep``)."""
+        return bool(self.lib.unires_plan_cg_lockstep(self._h))
+
     @on_device
     def matvec_time(self):
         """(launches, total microseconds) recorded since the last call; waits for them."""

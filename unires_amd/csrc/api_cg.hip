@@ -4,6 +4,7 @@
 #include <time.h>
 
 #include <functional>
+#include <mutex>
 
 #include "api_internal.hpp"
 
@@ -67,88 +68,131 @@ static bool cg_trim_on() {
 // preconditioner: the scope of the deferred update) is the operator, alpha and the iterate alone: nothing reads the
 // residual, r.z, beta or direction that would follow it.  k_sc_alpha writes the iteration count in k_sc_beta's stead;
 // the plan's r, rz and beta stay those of the iteration before.
-static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
-                            unsigned long long *hostw, hipStream_t st) {
+// An iteration is stated in two parts, each once: its operator application (cg_iter_operator) and everything after
+// it (cg_iter_rest).  cg_enqueue_iters puts them on one stream in turn; the two-lane schedule of several channels
+// (cg_lockstep_enqueue) puts the first on one stream and the second on another.
+struct CgIters {
+  int k_first = 1, count = 0;
+  bool dev_k = false, trim = false;
+  unsigned long long *hostw = nullptr;
+  RingPtrs rp = {};
+};
+
+static int cg_iters_begin(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
+                          unsigned long long *hostw, CgIters &it) {
+  const bool check = s.tol != 0.0;
+  const int ring = s.ring;
+  if (ring > 1 && (check || s.fft || dev_k || ring > kMaxRing || ring - 1 > pl->ring_slots))
+    return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
+  it.k_first = k_first, it.count = count, it.dev_k = dev_k, it.hostw = hostw;
+  // (enqueued whole: this call IS the solve, so its last iteration is the solve's)
+  it.trim = cg_trim_on() && !check && !s.fft && !dev_k && k_first == 1 && count == s.max_iter;
+  pl->last_trim = it.trim && count > 0;
+  it.rp = RingPtrs{};
+  for (int j = 0; j < ring && ring > 1; ++j) it.rp.p[j] = ring_slot(pl, j);
+  return UNIRES_OK;
+}
+
+// this iteration's direction
+static float *cg_iter_direction(unires_plan *pl, const CgSolve &s, const CgIters &it, int k) {
+  return s.ring > 1 ? ring_slot(pl, (k - it.k_first) % s.ring) : pl->p;
+}
+
+// The operator of iteration k: ap = A(p_k) and the partials of p.Ap.  Returns the number of partials.
+static int cg_iter_operator(unires_plan *pl, const CgSolve &s, const CgIters &it, int k, hipStream_t st) {
+  const int *done = &pl->state->done;
+  float *p = cg_iter_direction(pl, s, it, k);
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (pl->timing && hipEventCreate(&ev0) == hipSuccess) {
+    if (hipEventCreate(&ev1) == hipSuccess) {
+      (void)hipEventRecord(ev0, st);
+    } else {
+      (void)hipEventDestroy(ev0);
+      ev0 = nullptr;
+    }
+  }
+  if (pl->twice) (void)matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);  // (measurement: see the header)
+  const int g = matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);
+  if (ev0 && ev1) {
+    (void)hipEventRecord(ev1, st);
+    if (pl->tev.size() >= 65536) {  // a caller that never collects: forget the oldest pair
+      (void)hipEventDestroy(pl->tev.front().first), (void)hipEventDestroy(pl->tev.front().second);
+      pl->tev.erase(pl->tev.begin());
+    }
+    pl->tev.emplace_back(ev0, ev1);
+  }
+  return g;
+}
+
+// The rest of iteration k, after its operator wrote `g` partials: alpha, x / r, beta and the next direction - or,
+// for the trimmed last iteration, alpha and the iterate alone.
+static int cg_iter_rest(unires_plan *pl, const CgSolve &s, const CgIters &it, int k, int g, hipStream_t st) {
   const size_t ny = pl->dy.numel();
   const bool check = s.tol != 0.0;
   const int ring = s.ring;
   CgState *S = pl->state;
   const int *done = &S->done;
   const int gv = vec_num_blocks(ny);
-  if (ring > 1 && (check || s.fft || dev_k || ring > kMaxRing || ring - 1 > pl->ring_slots))
-    return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
-  // (enqueued whole: this call IS the solve, so its last iteration is the solve's)
-  const bool trim = cg_trim_on() && !check && !s.fft && !dev_k && k_first == 1 && count == s.max_iter;
-  pl->last_trim = trim && count > 0;
-  RingPtrs rp = {};
-  for (int j = 0; j < ring && ring > 1; ++j) rp.p[j] = ring_slot(pl, j);
-  for (int k = k_first; k < k_first + count; ++k) {
-    const int kk = dev_k ? -1 : k;
-    const int slot = ring > 1 ? (k - k_first) % ring : 0;
-    float *p = ring > 1 ? ring_slot(pl, slot) : pl->p;  // this iteration's direction
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (pl->timing && hipEventCreate(&ev0) == hipSuccess) {
-      if (hipEventCreate(&ev1) == hipSuccess) {
-        (void)hipEventRecord(ev0, st);
-      } else {
-        (void)hipEventDestroy(ev0);
-        ev0 = nullptr;
-      }
-    }
-    if (pl->twice) (void)matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);  // (measurement: see the header)
-    const int g = matvec(pl, s.rho, s.lam, p, pl->ap, pl->part0, done, st);
-    if (ev0 && ev1) {
-      (void)hipEventRecord(ev1, st);
-      if (pl->tev.size() >= 65536) {  // a caller that never collects: forget the oldest pair
-        (void)hipEventDestroy(pl->tev.front().first), (void)hipEventDestroy(pl->tev.front().second);
-        pl->tev.erase(pl->tev.begin());
-      }
-      pl->tev.emplace_back(ev0, ev1);
-    }
-    const bool guarded = check && s.stop == UNIRES_STOP_MAXGAIN_GUARDED;
-    const bool recur = check && (s.stop == UNIRES_STOP_MAXGAIN_RECURRED || guarded);
-    int obj_kind = 0;
-    if (check && s.stop == UNIRES_STOP_RESIDUAL) obj_kind = 1;
-    if (recur) obj_kind = 2;
-    // "x += alpha p" rides with the p update unless sc_beta can stop the solve in between
-    const bool lazy_x = obj_kind == 0;
-    if (trim && k == k_first + count - 1) {
-      launch_sc_alpha(S, pl->part0, g, st, k);
-      if (ring > 1)
-        launch_update_x_flush(S, rp, slot + 1, ny, s.x, st);
-      else
-        launch_update_x(S, p, ny, s.x, st);
-      break;
-    }
-    launch_sc_alpha(S, pl->part0, g, st);
-    launch_update_xr(S, p, pl->ap, lazy_x ? nullptr : s.x, pl->r, s.b, ny, pl->part0,
-                     recur ? pl->part1 : nullptr, s.M, st);
-    if (s.fft) {  // (the transforms also run after convergence: hipFFT has no device-side skip)
-      if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
-      launch_dot(pl->r, pl->fft.z, ny, pl->part0, done, st);
-    }
-    if (guarded)
-      launch_sc_beta_guarded(S, pl->part0, pl->part1, gv, kk, s.tol, hostw, st);
+  unsigned long long *hostw = it.hostw;
+  const RingPtrs &rp = it.rp;
+  const int k_first = it.k_first, count = it.count;
+  const int kk = it.dev_k ? -1 : k;
+  const int slot = ring > 1 ? (k - k_first) % ring : 0;
+  float *p = cg_iter_direction(pl, s, it, k);
+  const bool guarded = check && s.stop == UNIRES_STOP_MAXGAIN_GUARDED;
+  const bool recur = check && (s.stop == UNIRES_STOP_MAXGAIN_RECURRED || guarded);
+  int obj_kind = 0;
+  if (check && s.stop == UNIRES_STOP_RESIDUAL) obj_kind = 1;
+  if (recur) obj_kind = 2;
+  // "x += alpha p" rides with the p update unless sc_beta can stop the solve in between
+  const bool lazy_x = obj_kind == 0;
+  if (it.trim && k == k_first + count - 1) {
+    launch_sc_alpha(S, pl->part0, g, st, k);
+    if (ring > 1)
+      launch_update_x_flush(S, rp, slot + 1, ny, s.x, st);
     else
-      launch_sc_beta(S, pl->part0, pl->part1, gv, kk, obj_kind, s.tol, obj_kind ? hostw : nullptr, st);
-    if (ring > 1 && (slot == ring - 1 || k == k_first + count - 1))
-      launch_update_p_flush(S, pl->r, rp, slot + 1, ring_slot(pl, (slot + 1) % ring), ny, s.M, s.x, st);
-    else if (ring > 1)
-      launch_update_p_ring(S, pl->r, p, ring_slot(pl, slot + 1), slot, ny, s.M, st);
-    else
-      launch_update_p(S, s.fft ? pl->fft.z : pl->r, pl->p, ny, s.M, lazy_x ? s.x : nullptr, st);
-    if (check && s.stop == UNIRES_STOP_MAXGAIN) {
-      // objective sum x (Ax - 2b) folded into the matvec epilogue: A(x) is never stored
-      const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, done, st, s.b);
-      launch_sc_obj(S, pl->part1, go, kk, s.tol, hostw, st);
-    }
-    if (guarded) {
-      // ... the same, but its kernels return at entry unless k_sc_beta_guarded asked for it (cg.hip)
-      const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, &S->skip_fresh, st, s.b);
-      launch_sc_obj_guarded(S, pl->part1, go, kk, s.tol, hostw, st);
-    }
+      launch_update_x(S, p, ny, s.x, st);
+    return UNIRES_OK;
+  }
+  launch_sc_alpha(S, pl->part0, g, st);
+  launch_update_xr(S, p, pl->ap, lazy_x ? nullptr : s.x, pl->r, s.b, ny, pl->part0,
+                   recur ? pl->part1 : nullptr, s.M, st);
+  if (s.fft) {  // (the transforms also run after convergence: hipFFT has no device-side skip)
+    if (fftpre_apply(pl->fft, pl->r, pl->fft.z, st)) return fail(UNIRES_ERR_HIP, "hipFFT execution failed");
+    launch_dot(pl->r, pl->fft.z, ny, pl->part0, done, st);
+  }
+  if (guarded)
+    launch_sc_beta_guarded(S, pl->part0, pl->part1, gv, kk, s.tol, hostw, st);
+  else
+    launch_sc_beta(S, pl->part0, pl->part1, gv, kk, obj_kind, s.tol, obj_kind ? hostw : nullptr, st);
+  if (ring > 1 && (slot == ring - 1 || k == k_first + count - 1))
+    launch_update_p_flush(S, pl->r, rp, slot + 1, ring_slot(pl, (slot + 1) % ring), ny, s.M, s.x, st);
+  else if (ring > 1)
+    launch_update_p_ring(S, pl->r, p, ring_slot(pl, slot + 1), slot, ny, s.M, st);
+  else
+    launch_update_p(S, s.fft ? pl->fft.z : pl->r, pl->p, ny, s.M, lazy_x ? s.x : nullptr, st);
+  if (check && s.stop == UNIRES_STOP_MAXGAIN) {
+    // objective sum x (Ax - 2b) folded into the matvec epilogue: A(x) is never stored
+    const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, done, st, s.b);
+    launch_sc_obj(S, pl->part1, go, kk, s.tol, hostw, st);
+  }
+  if (guarded) {
+    // ... the same, but its kernels return at entry unless k_sc_beta_guarded asked for it (cg.hip)
+    const int go = matvec(pl, s.rho, s.lam, s.x, pl->ax, pl->part1, &S->skip_fresh, st, s.b);
+    launch_sc_obj_guarded(S, pl->part1, go, kk, s.tol, hostw, st);
   }
   return UNIRES_OK;
+}
+
+static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
+                            unsigned long long *hostw, hipStream_t st) {
+  CgIters it;
+  int rc = cg_iters_begin(pl, s, k_first, count, dev_k, hostw, it);
+  for (int k = k_first; !rc && k < k_first + count; ++k) {
+    const int g = cg_iter_operator(pl, s, it, k, st);
+    rc = cg_iter_rest(pl, s, it, k, g, st);
+  }
+  return rc;
 }
 
 // Enqueues the whole solve (every kernel of nitorch's cg()) on `st`.
@@ -463,6 +507,7 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
   unires_plan *pl = plan;
   CgSolve s = cg_describe(pl, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode);
   mark_use(pl, st);  // (before anything is enqueued: a failed start or drive below is remembered too)
+  pl->last_lockstep = 0;
 
   // (a stream under capture - e.g. the caller's torch.cuda.graph - runs nothing until the graph is launched: the
   // chunk feeder would wait for progress that never comes.  The whole solve then joins the capture, as in r3;
@@ -514,6 +559,190 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
   return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
 }
 
+// --------------------------------------------------------------------------
+// The two-lane schedule of several channels' fixed-iteration solves.  The operator of an iteration is bound by
+// instruction issue and LDS, the scalar and vector kernels after it by the fabric; on free-running streams the
+// channels mostly queue behind each other.  Here all of them are enqueued as ONE schedule on two streams:
+//   lane M: start(0) .. start(n-1), then matvec(c, k) for k = 1 .. N, c = 0 .. n-1 (c fastest);
+//   lane V: in the same (k, c) order, the rest of iteration k of channel c;
+//   matvec(c, k) waits for V(c, k-1) (for start(c) when k = 1: same lane), V(c, k) waits for matvec(c, k)
+// - channel c's vector phase runs under channel c+1's operator every time.  Per channel the kernels, their arguments
+// and their order are those of cg_enqueue, so x is the same bits as that plan's solve alone with the same grids.
+// The schedule is captured once, by fork / join capture across the two lanes, into one hipGraphExec_t with two
+// parallel branches, kept here and keyed by every channel's CgSolve and the plans' epochs (drop_cg_graph moves a
+// plan's epoch: whatever invalidates a plan's own captured solve invalidates this one).
+// --------------------------------------------------------------------------
+namespace {
+struct Lockstep {
+  std::vector<unires_plan *> plans;
+  std::vector<CgSolve> keys;
+  std::vector<unsigned long long> epochs;
+  std::vector<int> trim, fused;  // what unires_plan_cg_ends reports for a replay
+  std::vector<hipEvent_t> joins;  // one per channel stream, and the graph's end
+  hipGraphExec_t exec = nullptr;
+};
+std::vector<Lockstep> g_lockstep;
+std::mutex g_lockstep_mutex;
+constexpr size_t kMaxLockstep = 4;  // sets of plans with a captured schedule (a reconstruction has one)
+
+void lockstep_destroy(Lockstep &L, bool wait) {
+  if (wait)
+    for (unires_plan *pl : L.plans) await_use(pl);  // (a launch of the graph may still be in flight)
+  if (L.exec) (void)hipGraphExecDestroy(L.exec);
+  for (hipEvent_t e : L.joins) (void)hipEventDestroy(e);
+  L.exec = nullptr, L.joins.clear();
+}
+}  // namespace
+
+// unires_plan_destroy: the schedules the plan is part of go with it
+void unires::cg_lockstep_forget(unires_plan *pl) {
+  std::lock_guard<std::mutex> lock(g_lockstep_mutex);
+  for (size_t i = g_lockstep.size(); i-- > 0;)
+    if (std::find(g_lockstep[i].plans.begin(), g_lockstep[i].plans.end(), pl) != g_lockstep[i].plans.end()) {
+      lockstep_destroy(g_lockstep[i], false);
+      g_lockstep.erase(g_lockstep.begin() + (long)i);
+    }
+}
+
+// UNIRES_CG_LOCKSTEP (cg_lockstep_env, cg.hpp) off: one free-running chain per channel.  GPU_MAX_HW_QUEUES, read once:
+// the schedule's graph has two parallel branches, which the runtime is known to mishandle with fewer than 4 hardware
+// queues - then never.
+static bool cg_lockstep_on() {
+  static const bool on = [] {
+    const char *q = getenv("GPU_MAX_HW_QUEUES");
+    return cg_lockstep_env() && !(q && atoi(q) < 4);
+  }();
+  return on;
+}
+
+// The whole schedule on lanes lm (operators) and lv (everything else); called under capture of lm.  `ev`: fresh
+// events, one per edge.
+static int cg_lockstep_enqueue(int n, unires_plan *const *plans, const std::vector<CgSolve> &s, hipStream_t lm,
+                               hipStream_t lv, const std::vector<hipEvent_t> &ev) {
+  size_t ne = 0;
+  auto edge = [&](hipStream_t from, hipStream_t to) -> int {
+    hipEvent_t e = ev[ne++];
+    HIP_TRY(hipEventRecord(e, from));
+    HIP_TRY(hipStreamWaitEvent(to, e, 0));
+    return UNIRES_OK;
+  };
+  int rc = edge(lm, lv);  // fork: lane V joins the capture
+  std::vector<CgIters> it((size_t)n);
+  for (int c = 0; c < n && !rc; ++c) {
+    rc = cg_enqueue_start(plans[c], s[c], nullptr, lm);
+    if (!rc) rc = cg_iters_begin(plans[c], s[c], 1, s[c].max_iter, false, nullptr, it[c]);
+  }
+  const int N = s[0].max_iter;
+  std::vector<hipEvent_t> vdone((size_t)n, nullptr);
+  for (int k = 1; k <= N && !rc; ++k)
+    for (int c = 0; c < n && !rc; ++c) {
+      if (vdone[c]) HIP_TRY(hipStreamWaitEvent(lm, vdone[c], 0));  // matvec(c, k) after V(c, k - 1)
+      const int g = cg_iter_operator(plans[c], s[c], it[c], k, lm);
+      if ((rc = edge(lm, lv))) break;  // V(c, k) after matvec(c, k)
+      if ((rc = cg_iter_rest(plans[c], s[c], it[c], k, g, lv))) break;
+      if (k < N) {
+        vdone[c] = ev[ne++];
+        HIP_TRY(hipEventRecord(vdone[c], lv));
+      }
+    }
+  if (!rc) rc = edge(lv, lm);  // join
+  return rc;
+}
+
+// Takes the channels' solves if they are in the schedule's scope and it could be captured (or was): returns 0 with
+// *taken set, or an error.  *taken false: nothing was enqueued, the caller goes on as before.
+static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho, const float *lam,
+                             const float *const *b, float *const *x, int max_iter, double tol, int stop_mode,
+                             int precond_mode, void *const *streams, bool *taken) {
+  *taken = false;
+  if (!cg_lockstep_on() || !cg_graphs_on() || n < 2 || tol != 0.0 || max_iter < 1 ||
+      precond_mode == UNIRES_PRECOND_FFT)
+    return UNIRES_OK;
+  hipStream_t lm = (hipStream_t)streams[0], lv = nullptr;
+  for (int c = 1; c < n && !lv; ++c)
+    if (streams[c] != streams[0]) lv = (hipStream_t)streams[c];
+  if (!lm || !lv) return UNIRES_OK;  // (two lanes need two of the caller's streams)
+  for (int c = 0; c < n; ++c)
+    if (plans[c]->timing || stream_capturing((hipStream_t)streams[c])) return UNIRES_OK;
+
+  std::vector<CgSolve> s;
+  for (int c = 0; c < n; ++c) {
+    s.push_back(cg_describe(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode));
+    s[c].ring = cg_ring_prepare(plans[c], (hipStream_t)streams[c]);  // (before capture: it may allocate)
+  }
+  std::lock_guard<std::mutex> lock(g_lockstep_mutex);
+  Lockstep *L = nullptr;
+  for (Lockstep &e : g_lockstep)
+    if (e.plans == std::vector<unires_plan *>(plans, plans + n)) L = &e;
+  bool fresh = !L || !L->exec;
+  for (int c = 0; L && !fresh && c < n; ++c)
+    fresh = !L->keys[c].same_graph(s[c]) || L->epochs[c] != plans[c]->cg_epoch;
+  if (fresh) {
+    if (L) {
+      lockstep_destroy(*L, true);
+    } else {
+      if (g_lockstep.size() >= kMaxLockstep) {
+        lockstep_destroy(g_lockstep.front(), true);
+        g_lockstep.erase(g_lockstep.begin());
+      }
+      g_lockstep.emplace_back();
+      L = &g_lockstep.back();
+      L->plans.assign(plans, plans + n);
+    }
+    std::vector<hipEvent_t> ev((size_t)(2 + 2 * n * max_iter), nullptr);
+    bool ok = true;
+    for (hipEvent_t &e : ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    L->joins.assign((size_t)n + 1, nullptr);
+    for (hipEvent_t &e : L->joins) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    int rc = -1;
+    if (ok) {
+      for (int c = 0; c < n; ++c) plans[c]->lockstep = true;  // (the operators' grids are this mode's: cap_s2_ls)
+      rc = capture_graph(lm, &L->exec, [&] { return cg_lockstep_enqueue(n, plans, s, lm, lv, ev); });
+      for (int c = 0; c < n; ++c) plans[c]->lockstep = false;
+    }
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    (void)hipGetLastError();
+    if (rc != 0) {  // refused (rc < 0: the caller's path serves the solves) or failed
+      lockstep_destroy(*L, false);
+      g_lockstep.erase(g_lockstep.begin() + (L - g_lockstep.data()));
+      if (rc > 0)
+        for (int c = 0; c < n; ++c) cg_resync_gen(plans[c]);
+      return rc > 0 ? rc : UNIRES_OK;
+    }
+    L->keys = s;
+    L->epochs.clear(), L->trim.clear(), L->fused.clear();
+    for (int c = 0; c < n; ++c) {
+      L->epochs.push_back(plans[c]->cg_epoch);
+      L->trim.push_back(plans[c]->last_trim), L->fused.push_back(plans[c]->last_fused);
+    }
+  }
+  // the right-hand sides were enqueued on the channels' streams: the launch stream waits for every one of them, and
+  // every one of them for the graph's end (the caller joins its streams as it did)
+  for (int c = 0; c < n; ++c)
+    if ((hipStream_t)streams[c] != lm) {
+      HIP_TRY(hipEventRecord(L->joins[c], (hipStream_t)streams[c]));
+      HIP_TRY(hipStreamWaitEvent(lm, L->joins[c], 0));
+    }
+  for (int c = 0; c < n; ++c) {
+    ++plans[c]->cg_gen;  // (k_sc_init counts every solve)
+    plans[c]->last_ring = s[c].ring, plans[c]->last_trim = L->trim[c], plans[c]->last_fused = L->fused[c];
+  }
+  if (hipGraphLaunch(L->exec, lm) != hipSuccess) {
+    for (int c = 0; c < n; ++c) cg_resync_gen(plans[c]);
+    return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
+  }
+  HIP_TRY(hipEventRecord(L->joins[n], lm));
+  for (int c = 0; c < n; ++c) {
+    if ((hipStream_t)streams[c] != lm) HIP_TRY(hipStreamWaitEvent((hipStream_t)streams[c], L->joins[n], 0));
+    plans[c]->last_lockstep = 1;
+    mark_use(plans[c], (hipStream_t)streams[c]);
+  }
+  *taken = true;
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 // Several channels' solves at once, each on its own plan and stream (unires/_update.py:122-150 loops over
 // the channels; they do not couple inside the y-update): the chunks of all of them are fed from one host
 // loop, so that the channels still overlap on the device where they run on separate streams.
@@ -534,7 +763,14 @@ extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, cons
     return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
                                 "(it is fed to the device chunk by chunk, following its progress)");
   for (int c = 0; c < n; ++c) mark_use(plans[c], (hipStream_t)streams[c]);  // (before anything is enqueued)
-  if (!cg_chunked(tol, max_iter) || (capturing && max_iter <= kMaxCgIter)) {  // nothing to steer: each solve is enqueued whole
+  bool lockstep = false;
+  if (!capturing) {
+    const int rc = cg_lockstep_solve(n, plans, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode, streams, &lockstep);
+    if (rc) return rc;
+  }
+  if (lockstep) {
+    // (enqueued as one schedule across the channels' streams)
+  } else if (!cg_chunked(tol, max_iter) || (capturing && max_iter <= kMaxCgIter)) {  // nothing to steer: each solve is enqueued whole
     for (int c = 0; c < n; ++c) {
       const int rc = unires_cg_solve(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode,
                                      nullptr, nullptr, streams[c]);
@@ -542,7 +778,7 @@ extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, cons
     }
   } else {
     std::vector<CgRun> runs;
-    for (int c = 0; c < n; ++c) plans[c]->last_ring = 1;
+    for (int c = 0; c < n; ++c) plans[c]->last_ring = 1, plans[c]->last_lockstep = 0;
     for (int c = 0; c < n; ++c)
       runs.push_back(cg_make_run(plans[c], cg_describe(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode,
                                                        precond_mode), (hipStream_t)streams[c]));

@@ -260,6 +260,14 @@ struct unires_plan {
   // streams of their own), and the caps on the persistent kernels' grids that follow from it (0: the whole chip)
   int concurrency = 1;
   int cap_s2 = 0, cap_f1 = 0;
+  // the two-lane schedule of several channels' solves (api_cg.hip: cg_lockstep_solve).  cap_s2_ls: k_splat2's grid
+  // cap in that mode, taken while `lockstep` is up (the schedule is being enqueued); cg_epoch: moved by drop_cg_graph,
+  // unique among all plans of the process - a schedule captured at another epoch is stale; last_lockstep: whether
+  // the plan's last solve ran in the schedule (unires_plan_cg_lockstep)
+  int cap_s2_ls = 0;
+  bool lockstep = false;
+  unsigned long long cg_epoch = 0;
+  int last_lockstep = 0;
 };
 
 namespace unires {
@@ -270,6 +278,10 @@ void mark_use(unires_plan *pl, hipStream_t st);  // note the plan's last use (se
 void await_use(unires_plan *pl);                 // ... and wait for it
 void drop_cg_chunk_graphs(unires_plan *pl);
 void drop_cg_graph(unires_plan *pl);  // every captured solve of the plan, the chunk graphs included
+unsigned long long next_cg_epoch();
+
+// api_cg.hip
+void cg_lockstep_forget(unires_plan *pl);  // the captured schedules the plan is part of (unires_plan_destroy)
 
 // api_operator.hip
 // q = sum_n tau_n AtA_n p + rho lam^2 DtD p ; optional dot partials of sum(p*q).

@@ -245,7 +245,7 @@ static int ata_apply(unires_plan *pl, const Repeat &R, const float *in, float al
     e1.grid_cap = share ? pl->cap_f1 : 0;
     if (!launch_ata1(R.f1, in, R.Af, alpha, e1, out, pl->dy, done, st)) return e1.partials ? ata1_blocks(pl->dy, e1.grid_cap) : 0;
   }
-  ep.grid_cap = share ? pl->cap_s2 : 0;
+  ep.grid_cap = share ? (pl->lockstep ? pl->cap_s2_ls : pl->cap_s2) : 0;
   const PushSrc src = ata_forward(pl, R, in, done, st, weights);
   return push_any(pl, src, R, alpha, ep, out, done, st, served);
 }

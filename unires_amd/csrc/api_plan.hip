@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <time.h>
 
+#include <atomic>
 #include <new>
 
 #include "api_internal.hpp"
@@ -90,7 +91,13 @@ void unires::drop_cg_chunk_graphs(unires_plan *pl) {
 
 // Drop the captured CG solves.  A launch of one may still be in flight (the ADMM loop never syncs):
 // wait for the plan's last use before destroying the executable graph.
+unsigned long long unires::next_cg_epoch() {
+  static std::atomic<unsigned long long> epoch{0};
+  return ++epoch;
+}
+
 void unires::drop_cg_graph(unires_plan *pl) {
+  pl->cg_epoch = next_cg_epoch();  // (the channels' joint schedule, kept in api_cg.hip, is stale from here on)
   drop_cg_chunk_graphs(pl);
   if (!pl->cg_exec) return;
   await_use(pl);
@@ -429,6 +436,7 @@ extern "C" int unires_plan_create(unires_plan_t **plan, const int32_t dim_y[3],
   unires_plan *pl = new (std::nothrow) unires_plan();
   if (!pl) return fail(UNIRES_ERR_ALLOC, "host allocation failed");
   pl->dy = mk(dim_y);
+  pl->cg_epoch = next_cg_epoch();
   memcpy(pl->vx, vx_y, sizeof(pl->vx));
   pl->regime = regime;
   pl->fov_tol = fov_tol;
@@ -496,6 +504,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->ws) (void)hipFree(plan->ws);
   if (plan->precM) (void)hipFree(plan->precM);
   if (plan->ring) (void)hipFree(plan->ring);
+  cg_lockstep_forget(plan);
   if (plan->cg_exec) (void)hipGraphExecDestroy(plan->cg_exec);
   if (plan->cg_start_exec) (void)hipGraphExecDestroy(plan->cg_start_exec);
   if (plan->cg_chunk_exec) (void)hipGraphExecDestroy(plan->cg_chunk_exec);
@@ -529,6 +538,8 @@ extern "C" int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last
   if (last) *last = plan->last_ring;
   return UNIRES_OK;
 }
+
+extern "C" int unires_plan_cg_lockstep(unires_plan_t *plan) { return plan ? plan->last_lockstep : 0; }
 
 extern "C" int unires_plan_cg_ends(unires_plan_t *plan, int32_t *trimmed, int32_t *start_fused) {
   if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
@@ -762,22 +773,29 @@ extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int
 // 4 879 -> 5 190 CG it/s with 384 - 448 splat workgroups of 1 024; at 384^3 x 4 a smaller grid LOSES (the pull and
 // conv kernels between the splats leave room anyway): the cap applies below 2^25 output voxels.  A launch under a
 // cap takes longer and the job as a whole gets faster.  n <= 1: the whole chip (the default).
+// k_splat2's grid cap under the two-lane schedule, workgroups per 16 CUs (0: none) - E20's scan
+static constexpr int kLockstepS2 = 0;
+
 extern "C" int unires_plan_set_concurrency(unires_plan_t *plan, int32_t n_concurrent) {
   if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
   if (n_concurrent < 1 || n_concurrent > 64) return fail(UNIRES_ERR_ARG, "concurrency out of range (1 .. 64)");
   if (n_concurrent == plan->concurrency) return UNIRES_OK;
-  int cap_s2 = 0, cap_f1 = 0;
+  int cap_s2 = 0, cap_f1 = 0, cap_s2_ls = 0;
   if (n_concurrent > 1 && plan->dy.numel() <= (1ull << 25)) {
     int dev = 0, ncu = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     static const int s2_16 = getenv("UNIRES_SHARE_S2") ? atoi(getenv("UNIRES_SHARE_S2")) : 28;  // workgroups per 16 CUs
     static const int f1_16 = getenv("UNIRES_SHARE_F1") ? atoi(getenv("UNIRES_SHARE_F1")) : 48;
+    // (the two-lane schedule has a cap of its own, UNIRES_LOCKSTEP_S2 in the same unit; 0: none.  E20)
+    static const int ls_16 = getenv("UNIRES_LOCKSTEP_S2") ? atoi(getenv("UNIRES_LOCKSTEP_S2")) : kLockstepS2;
     cap_s2 = std::max(8, ncu * s2_16 / 16 / 8 * 8);  // 448 of 1 024 on 256 CUs
+    cap_s2_ls = ls_16 > 0 ? std::max(8, ncu * ls_16 / 16 / 8 * 8) : 0;
     cap_f1 = std::max(8, ncu * f1_16 / 16 / 8 * 8);  // 768 of 1 024
   }
-  if (cap_s2 != plan->cap_s2 || cap_f1 != plan->cap_f1) drop_cg_graph(plan);  // (a captured solve has its grids baked in)
-  plan->concurrency = n_concurrent, plan->cap_s2 = cap_s2, plan->cap_f1 = cap_f1;
+  if (cap_s2 != plan->cap_s2 || cap_f1 != plan->cap_f1 || cap_s2_ls != plan->cap_s2_ls)
+    drop_cg_graph(plan);  // (a captured solve has its grids baked in)
+  plan->concurrency = n_concurrent, plan->cap_s2 = cap_s2, plan->cap_f1 = cap_f1, plan->cap_s2_ls = cap_s2_ls;
   return UNIRES_OK;
 }
 

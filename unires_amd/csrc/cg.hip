@@ -14,7 +14,9 @@ namespace unires {
 static inline int vec_blocks(size_t n) {
   size_t b = (n / 4 + kBlock - 1) / kBlock;
   if (b < 1) b = 1;
-  const size_t cap = 4096;  // enough workgroups to saturate HBM
+  // enough workgroups to saturate HBM (UNIRES_VEC_BLOCKS=<cap>, read once: measurement of how the vector kernels share
+  // the chip with another channel's operator, E20; the partials of r.z are then grouped by that many blocks)
+  static const size_t cap = getenv("UNIRES_VEC_BLOCKS") ? (size_t)std::max(1, std::min(atoi(getenv("UNIRES_VEC_BLOCKS")), kMaxPartials)) : 4096;
   return (int)(b < cap ? b : cap);
 }
 
@@ -262,7 +264,11 @@ __global__ void __launch_bounds__(kBlock)
 // __restrict__, which keeps the compiler from moving the load below the store).
 // PUPD = false (the last iteration of a solve that runs all its iterations, api_cg.hip): the iterate alone - r is not
 // read and no p_out written, m + 2 volume passes instead of m + 4; the terms, their order and roundings are the same.
-template <bool PUPD>
+// H: directions loaded before they are applied.  kMaxRing: the whole window at once, 8 float4 in flight per thread and
+// 118 - 121 VGPRs; 4: the window in two halves - load four, apply, load four, apply - so that a flush wave fits beside
+// an operator's on a SIMD (the channels' two-lane schedule, api_cg.hip).  Per element the terms, their order and
+// their roundings are the same: the same bits.
+template <bool PUPD, int H>
 __global__ void __launch_bounds__(kBlock)
     k_update_p_flush(CgState *__restrict__ st, const float *__restrict__ r, RingPtrs ring, int m, float *p_out,
                      size_t n, const float *__restrict__ M, float *__restrict__ x) {
@@ -284,25 +290,30 @@ __global__ void __launch_bounds__(kBlock)
     float4 vz = make_float4(0.f, 0.f, 0.f, 0.f);
     if (PUPD && !done) vz = zval4(ld4(r, i), M, i);
     float4 vx = ld4_stream(x, i);
-    float4 vp[kMaxRing];
 #pragma unroll
-    for (int j = 0; j < kMaxRing; ++j)
-      if (c[j]) vp[j] = ld4_stream(ring.p[j], i);
+    for (int h = 0; h < kMaxRing; h += H) {
+      float4 vp[H];
 #pragma unroll
-    for (int j = 0; j < kMaxRing; ++j) {
-      if (!c[j]) continue;
-      vx.x = __fadd_rn(vx.x, __fmul_rn(a[j], vp[j].x));
-      vx.y = __fadd_rn(vx.y, __fmul_rn(a[j], vp[j].y));
-      vx.z = __fadd_rn(vx.z, __fmul_rn(a[j], vp[j].z));
-      vx.w = __fadd_rn(vx.w, __fmul_rn(a[j], vp[j].w));
-      if (PUPD && j == m - 1) {  // (c[m - 1] = !done)
-        float4 b = vp[j];
-        b.x = __fadd_rn(__fmul_rn(beta, b.x), vz.x);
-        b.y = __fadd_rn(__fmul_rn(beta, b.y), vz.y);
-        b.z = __fadd_rn(__fmul_rn(beta, b.z), vz.z);
-        b.w = __fadd_rn(__fmul_rn(beta, b.w), vz.w);
-        st4(p_out, i, b);
+      for (int j = 0; j < H; ++j)
+        if (c[h + j]) vp[j] = ld4_stream(ring.p[h + j], i);
+      if (H < kMaxRing) __builtin_amdgcn_sched_barrier(0);  // (the next half's loads stay behind this half's terms)
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (!c[h + j]) continue;
+        vx.x = __fadd_rn(vx.x, __fmul_rn(a[h + j], vp[j].x));
+        vx.y = __fadd_rn(vx.y, __fmul_rn(a[h + j], vp[j].y));
+        vx.z = __fadd_rn(vx.z, __fmul_rn(a[h + j], vp[j].z));
+        vx.w = __fadd_rn(vx.w, __fmul_rn(a[h + j], vp[j].w));
+        if (PUPD && h + j == m - 1) {  // (c[m - 1] = !done)
+          float4 b = vp[j];
+          b.x = __fadd_rn(__fmul_rn(beta, b.x), vz.x);
+          b.y = __fadd_rn(__fmul_rn(beta, b.y), vz.y);
+          b.z = __fadd_rn(__fmul_rn(beta, b.z), vz.z);
+          b.w = __fadd_rn(__fmul_rn(beta, b.w), vz.w);
+          st4(p_out, i, b);
+        }
       }
+      if (H < kMaxRing) __builtin_amdgcn_sched_barrier(0);
     }
     st4_stream(x, i, vx);
   }
@@ -585,6 +596,14 @@ __global__ void __launch_bounds__(kBlock) k_sum_to(const double *part, int g, do
 // ---- launchers -------------------------------------------------------------
 int vec_num_blocks(size_t n) { return vec_blocks(n); }
 
+bool cg_lockstep_env() {
+  static const bool on = [] {
+    const char *e = getenv("UNIRES_CG_LOCKSTEP");
+    return e ? e[0] != '0' : kLockstepDefault;
+  }();
+  return on;
+}
+
 void launch_residual_init(const float *b, const float *ax, const float *x, float *r, float *p,
                           size_t n, double *part_rr, double *part_obj, const float *M,
                           hipStream_t st) {
@@ -618,11 +637,18 @@ void launch_update_p_ring(CgState *s, const float *r, const float *p_in, float *
 }
 void launch_update_p_flush(CgState *s, const float *r, const RingPtrs &ring, int m, float *p_out, size_t n,
                            const float *M, float *x, hipStream_t st) {
-  hipLaunchKernelGGL(k_update_p_flush<true>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
+  if (cg_lockstep_env())
+    hipLaunchKernelGGL((k_update_p_flush<true, 4>), dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
+  else
+    hipLaunchKernelGGL((k_update_p_flush<true, kMaxRing>), dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, r, ring, m, p_out, n, M, x);
 }
 void launch_update_x_flush(CgState *s, const RingPtrs &ring, int m, size_t n, float *x, hipStream_t st) {
-  hipLaunchKernelGGL(k_update_p_flush<false>, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, (const float *)nullptr, ring, m,
-                     (float *)nullptr, n, (const float *)nullptr, x);
+  if (cg_lockstep_env())
+    hipLaunchKernelGGL((k_update_p_flush<false, 4>), dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, (const float *)nullptr,
+                       ring, m, (float *)nullptr, n, (const float *)nullptr, x);
+  else
+    hipLaunchKernelGGL((k_update_p_flush<false, kMaxRing>), dim3(vec_blocks(n)), dim3(kBlock), 0, st, s,
+                       (const float *)nullptr, ring, m, (float *)nullptr, n, (const float *)nullptr, x);
 }
 void launch_update_x(const CgState *s, const float *p, size_t n, float *x, hipStream_t st) {
   hipLaunchKernelGGL(k_update_x, dim3(vec_blocks(n)), dim3(kBlock), 0, st, s, p, n, x);
