@@ -177,5 +177,21 @@ def test_nothing_leaks_into_the_next_solve(dev, stop, k):
     assert it == 7 and used.cg_ring() == k and same_bits(x, ref) and cg_ends(used)[0]
 
 
+def test_every_solve_reports_its_own_path(dev):
+    """Whole (captured), chunked, whole again (replayed) on one plan: after each solve the plan reports that solve's
+    trim and ring size, not the one before's, and the replay gives the capture's bits."""
+    xg, yg, sett, bs, x0s, rho, lams = _setup(dev, 'tail')
+    plan = _plan(xg, yg, sett, 0, 3)
+    x1, it = _solve(plan, bs[0], x0s[0], rho, lams[0], 9)
+    assert it == 9 and cg_ends(plan)[0] and plan.cg_ring() == 3
+    x = x0s[0].clone()
+    plan.cg(bs[0], x, rho, lams[0], max_iter=9, tolerance=1e-3)
+    torch.cuda.synchronize()
+    assert not cg_ends(plan)[0] and plan.cg_ring() == 1
+    x3, it = _solve(plan, bs[0], x0s[0], rho, lams[0], 9)
+    assert it == 9 and cg_ends(plan)[0] and plan.cg_ring() == 3
+    assert same_bits(x1, x3)
+
+
 if __name__ == '__main__':
     child_main(reference)

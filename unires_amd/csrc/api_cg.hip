@@ -10,17 +10,60 @@
 
 using namespace unires;
 
-// UNIRES_CG_START_FUSED, read once per process: 0 keeps k_residual_init at the start of every solve
-static bool cg_start_fused_on() {
-  static const bool on = !(getenv("UNIRES_CG_START_FUSED") && getenv("UNIRES_CG_START_FUSED")[0] == '0');
-  return on;
+// The switches of the CG driver, read once per process, at its first solve (the ring's budget apart).
+//   UNIRES_CG_START_FUSED  0: k_residual_init at the start of every solve, never the operator's own push
+//   UNIRES_CG_TRIM         0: the last iteration of every solve is enqueued in full
+//   UNIRES_CG_GRAPH        0: plain launches, no solve is captured into a hipGraph
+//                          (these three are off only when set with '0' as the first character)
+//   UNIRES_CG_LOCKSTEP     the halved flush (`flush_halved`: cg.hip, through cg_lockstep_env) and the two-lane schedule of
+//                          several channels' fixed-iteration solves (`lockstep`): on when set and the first character is
+//                          not '0', else kLockstepDefault (cg.hpp).  The schedule's graph has two parallel branches,
+//                          which the runtime is known to mishandle with fewer than 4 hardware queues: it is never taken
+//                          when GPU_MAX_HW_QUEUES is set below 4
+//   UNIRES_CG_RING         K of the deferred iterate update (atoi; default 8; clamped by cg_ring_prepare)
+//   UNIRES_CG_RING_MB      the ring's budget in MiB (atof; unset: an eighth of the free device memory) - read by
+//                          ring_budget() at each plan's first deferred solve, not with the others
+//   UNIRES_CG_CHUNK        iterations per chunk of a solve that can stop early (atoi; default 2; chunk_size() clamps it
+//                          to 1 .. 64); 0: no chunked solves
+struct CgSwitches {
+  bool start_fused = not_off("UNIRES_CG_START_FUSED"), trim = not_off("UNIRES_CG_TRIM");
+  bool graphs = not_off("UNIRES_CG_GRAPH");
+  bool flush_halved = kLockstepDefault, lockstep = false;
+  int ring = 8, chunk = 2;
+  CgSwitches() {
+    if (const char *e = getenv("UNIRES_CG_LOCKSTEP")) flush_halved = e[0] != '0';
+    const char *q = getenv("GPU_MAX_HW_QUEUES");
+    lockstep = flush_halved && !(q && atoi(q) < 4);
+    if (const char *e = getenv("UNIRES_CG_RING")) ring = atoi(e);
+    if (const char *e = getenv("UNIRES_CG_CHUNK")) chunk = atoi(e);
+  }
+  int chunk_size() const { return std::max(1, std::min(chunk, 64)); }
+  static size_t ring_budget() {
+    if (const char *e = getenv("UNIRES_CG_RING_MB")) return (size_t)std::max(0.0, atof(e) * 1048576.0);
+    size_t free_b = 0, total_b = 0;
+    const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    (void)hipGetLastError();
+    return known ? free_b / 8 : 0;
+  }
+
+ private:
+  static bool not_off(const char *name) {
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+  }
+};
+static const CgSwitches &cg_switches() {
+  static const CgSwitches sw;
+  return sw;
 }
+bool unires::cg_lockstep_env() { return cg_switches().flush_halved; }
 
 // The solve is enqueued in two parts: the start (r = b - A x, p, r.z, obj[0]) and runs of iterations.
 // `dev_k`: the iteration index is the device state's own counter (a captured chunk of iterations then
 // serves any part of a solve); `hostw`: the scalar kernel that ends an iteration publishes the state's
-// (generation, done, iterations) to this host-mapped word.
-static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long long *hostw, hipStream_t st) {
+// (generation, done, iterations) to this host-mapped word.  Each part says what it did in `how` (CgHow,
+// api_internal.hpp); the entry point that finishes the solve puts that into the plan.
+static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long long *hostw, hipStream_t st, CgHow &how) {
   const size_t ny = pl->dy.numel();
   const bool check = s.tol != 0.0;
   CgState *S = pl->state;
@@ -33,10 +76,10 @@ static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long lon
   // same float32 terms in another order, and agree with the other route's to the rounding of such a sum.
   const bool want_obj0 = check && s.stop != UNIRES_STOP_RESIDUAL;
   StartResidual res = {s.b, pl->r, pl->p, s.M, pl->part0, want_obj0 ? pl->part1 : nullptr, false};
-  const bool ask = cg_start_fused_on() && !s.fft;
+  const bool ask = cg_switches().start_fused && !s.fft;
   int g0 = matvec(pl, s.rho, s.lam, s.x, pl->ap, nullptr, nullptr, st, nullptr, ask ? &res : nullptr);
-  pl->last_fused = ask && res.served;
-  if (!(ask && res.served)) {
+  how.fused = ask && res.served;
+  if (!how.fused) {
     launch_residual_init(s.b, pl->ap, s.x, pl->r, pl->p, ny, pl->part0, want_obj0 ? pl->part1 : nullptr, s.M, st);
     g0 = gv;
   }
@@ -52,12 +95,6 @@ static int cg_enqueue_start(unires_plan *pl, const CgSolve &s, unsigned long lon
 // slot j of the plan's direction ring (slot 0: the buffer the start writes p into)
 static float *ring_slot(unires_plan *pl, int j) {
   return j == 0 ? pl->p : pl->ring + (size_t)(j - 1) * (align_up(pl->dy.numel() * 4) / 4);
-}
-
-// UNIRES_CG_TRIM, read once per process: 0 enqueues the last iteration of every solve in full
-static bool cg_trim_on() {
-  static const bool on = !(getenv("UNIRES_CG_TRIM") && getenv("UNIRES_CG_TRIM")[0] == '0');
-  return on;
 }
 
 // Iterations k_first .. k_first + count - 1 of the solve.
@@ -79,15 +116,15 @@ struct CgIters {
 };
 
 static int cg_iters_begin(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
-                          unsigned long long *hostw, CgIters &it) {
+                          unsigned long long *hostw, CgIters &it, CgHow &how) {
   const bool check = s.tol != 0.0;
   const int ring = s.ring;
   if (ring > 1 && (check || s.fft || dev_k || ring > kMaxRing || ring - 1 > pl->ring_slots))
     return fail(UNIRES_ERR_ARG, "deferred iterate update outside its scope");  // (cg_ring_prepare decides; never here)
   it.k_first = k_first, it.count = count, it.dev_k = dev_k, it.hostw = hostw;
-  // (enqueued whole: this call IS the solve, so its last iteration is the solve's)
-  it.trim = cg_trim_on() && !check && !s.fft && !dev_k && k_first == 1 && count == s.max_iter;
-  pl->last_trim = it.trim && count > 0;
+  // (enqueued whole: this call IS the solve, so its last iteration is the solve's; a chunk - dev_k - never is)
+  it.trim = cg_switches().trim && !check && !s.fft && !dev_k && k_first == 1 && count == s.max_iter && count > 0;
+  how.ring = ring, how.trim = it.trim;
   it.rp = RingPtrs{};
   for (int j = 0; j < ring && ring > 1; ++j) it.rp.p[j] = ring_slot(pl, j);
   return UNIRES_OK;
@@ -185,9 +222,9 @@ static int cg_iter_rest(unires_plan *pl, const CgSolve &s, const CgIters &it, in
 }
 
 static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int count, bool dev_k,
-                            unsigned long long *hostw, hipStream_t st) {
+                            unsigned long long *hostw, hipStream_t st, CgHow &how) {
   CgIters it;
-  int rc = cg_iters_begin(pl, s, k_first, count, dev_k, hostw, it);
+  int rc = cg_iters_begin(pl, s, k_first, count, dev_k, hostw, it, how);
   for (int k = k_first; !rc && k < k_first + count; ++k) {
     const int g = cg_iter_operator(pl, s, it, k, st);
     rc = cg_iter_rest(pl, s, it, k, g, st);
@@ -196,10 +233,10 @@ static int cg_enqueue_iters(unires_plan *pl, const CgSolve &s, int k_first, int 
 }
 
 // Enqueues the whole solve (every kernel of nitorch's cg()) on `st`.
-static int cg_enqueue(unires_plan *pl, const CgSolve &s, hipStream_t st) {
-  const int rc = cg_enqueue_start(pl, s, nullptr, st);
+static int cg_enqueue(unires_plan *pl, const CgSolve &s, hipStream_t st, CgHow &how) {
+  const int rc = cg_enqueue_start(pl, s, nullptr, st, how);
   if (rc) return rc;
-  return cg_enqueue_iters(pl, s, 1, s.max_iter, false, nullptr, st);
+  return cg_enqueue_iters(pl, s, 1, s.max_iter, false, nullptr, st, how);
 }
 
 // K of the deferred iterate update for a solve that nothing reads x of before it ends (tol = 0, no FFT
@@ -210,26 +247,14 @@ static int cg_enqueue(unires_plan *pl, const CgSolve &s, hipStream_t st) {
 // requests get at most what was allocated then.  No room, a failed allocation, or a stream under capture at that
 // first solve: K = 1, the iterate updated every iteration.
 static int cg_ring_prepare(unires_plan *pl, hipStream_t st) {
-  static const int env_k = [] {
-    const char *e = getenv("UNIRES_CG_RING");
-    return e ? atoi(e) : 8;
-  }();
-  int want = pl->ring_req > 0 ? pl->ring_req : env_k;
+  int want = pl->ring_req > 0 ? pl->ring_req : cg_switches().ring;
   want = std::max(1, std::min(want, kMaxRing));
   if (want <= 1) return 1;
   if (!pl->ring_tried) {
     if (stream_capturing(st)) return 1;  // (no allocation inside a capture: decided at the next plain solve)
     pl->ring_tried = true;
     const size_t slot = align_up(pl->dy.numel() * 4);
-    size_t budget = 0;
-    if (const char *e = getenv("UNIRES_CG_RING_MB")) {
-      budget = (size_t)std::max(0.0, atof(e) * 1048576.0);
-    } else {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = free_b / 8;
-      (void)hipGetLastError();
-    }
-    const int n = (int)std::min<size_t>((size_t)(want - 1), budget / slot);
+    const int n = (int)std::min<size_t>((size_t)(want - 1), CgSwitches::ring_budget() / slot);
     if (n < 1) return 1;
     if (hipMalloc((void **)&pl->ring, (size_t)n * slot) != hipSuccess) {
       (void)hipGetLastError();
@@ -261,6 +286,7 @@ struct CgRun {
   unsigned gen = 0;     // generation of this solve
   bool finished = false;
   bool use_graph = false;
+  CgHow how;  // what the start and the chunks did, enqueued or replayed
 };
 
 // The host counts the solves it starts (cg_gen), k_sc_init counts the ones that run (state->gen); the chunked
@@ -273,16 +299,6 @@ static void cg_resync_gen(unires_plan *pl) {
   if (pl->state && hipMemcpy(&g, &pl->state->gen, sizeof(g), hipMemcpyDeviceToHost) == hipSuccess) pl->cg_gen = g;
   (void)hipGetLastError();
 }
-
-// UNIRES_CG_CHUNK, read once per process: iterations per chunk (default 2, at most 64); 0: no chunked solves
-static int cg_chunk_env() {
-  static const int v = [] {
-    const char *e = getenv("UNIRES_CG_CHUNK");
-    return e ? atoi(e) : 2;
-  }();
-  return v;
-}
-static int cg_chunk_size() { return std::max(1, std::min(cg_chunk_env(), 64)); }
 
 static int capture_graph(hipStream_t st, hipGraphExec_t *exec, const std::function<int()> &body) {
   *exec = nullptr;
@@ -311,10 +327,10 @@ static int cg_run_enqueue_chunk(CgRun &R) {
   unires_plan *pl = R.pl;
   const int n = std::min(R.s.chunk, R.s.max_iter - R.enqueued);
   if (n <= 0) return UNIRES_OK;
-  if (R.use_graph && n == R.s.chunk && pl->cg_chunk_exec) {
-    HIP_TRY(hipGraphLaunch(pl->cg_chunk_exec, R.st));
+  if (R.use_graph && n == R.s.chunk && pl->cg_chunks.chunk) {
+    HIP_TRY(hipGraphLaunch(pl->cg_chunks.chunk, R.st));
   } else {
-    const int rc = cg_enqueue_iters(pl, R.s, R.enqueued + 1, n, true, pl->progress_dev, R.st);
+    const int rc = cg_enqueue_iters(pl, R.s, R.enqueued + 1, n, true, pl->progress_dev, R.st, R.how);
     if (rc) return rc;
   }
   R.enqueued += n;
@@ -335,29 +351,29 @@ static int cg_run_start_impl(CgRun &R) {
   CgSolve key = R.s;
   key.max_iter = 0;
   key.pre = R.s.M ? UNIRES_PRECOND_JACOBI : UNIRES_PRECOND_IDENTITY;
-  if (R.use_graph && !(pl->cg_start_exec && pl->cg_chunk_exec && pl->cg_chunk_key.same_graph(key))) {
+  CgCaptured &G = pl->cg_chunks;
+  if (R.use_graph && !G.matches(key)) {
     drop_cg_chunk_graphs(pl);
-    int rc = capture_graph(R.st, &pl->cg_start_exec, [&] { return cg_enqueue_start(pl, R.s, pl->progress_dev, R.st); });
+    CgHow how;
+    int rc = capture_graph(R.st, &G.exec, [&] { return cg_enqueue_start(pl, R.s, pl->progress_dev, R.st, how); });
     if (rc > 0) return rc;
     if (rc == 0)
-      rc = capture_graph(R.st, &pl->cg_chunk_exec, [&] {
-        return cg_enqueue_iters(pl, R.s, 1, R.s.chunk, true, pl->progress_dev, R.st);
+      rc = capture_graph(R.st, &G.chunk, [&] {
+        return cg_enqueue_iters(pl, R.s, 1, R.s.chunk, true, pl->progress_dev, R.st, how);
       });
     if (rc > 0) return rc;
-    if (rc < 0 || !pl->cg_start_exec || !pl->cg_chunk_exec) {
+    if (rc < 0 || !G.exec || !G.chunk) {
       drop_cg_chunk_graphs(pl);
       R.use_graph = false;
     } else {
-      pl->cg_chunk_key = key;
-      pl->chunk_fused = pl->last_fused;
+      G.key = key, G.how = how;
     }
   }
-  pl->last_trim = 0;  // (a chunked solve is never trimmed)
   if (R.use_graph) {
-    pl->last_fused = pl->chunk_fused;
-    HIP_TRY(hipGraphLaunch(pl->cg_start_exec, R.st));
+    R.how = G.how;
+    HIP_TRY(hipGraphLaunch(G.exec, R.st));
   } else {
-    const int rc = cg_enqueue_start(pl, R.s, pl->progress_dev, R.st);
+    const int rc = cg_enqueue_start(pl, R.s, pl->progress_dev, R.st, R.how);
     if (rc) return rc;
   }
   // two chunks in flight
@@ -365,7 +381,6 @@ static int cg_run_start_impl(CgRun &R) {
   if (!rc) rc = cg_run_enqueue_chunk(R);
   if (rc) return rc;
   if (R.enqueued >= R.s.max_iter) R.finished = true;
-  pl->last_trim = 0;
   return UNIRES_OK;
 }
 
@@ -455,14 +470,9 @@ static int cg_check_args(unires_plan *plan, float rho, float lam, const float *b
   return UNIRES_OK;
 }
 
-static bool cg_graphs_on() {
-  static const bool on = !(getenv("UNIRES_CG_GRAPH") && getenv("UNIRES_CG_GRAPH")[0] == '0');
-  return on;
-}
-
 // chunked enqueue: solves that can stop early, unless switched off (UNIRES_CG_CHUNK=0: the full enqueue)
 static bool cg_chunked(double tol, int max_iter) {
-  const bool off = cg_chunk_env() == 0;
+  const bool off = cg_switches().chunk == 0;
   return tol != 0.0 && max_iter > 0 && (!off || max_iter > kMaxCgIter);
 }
 
@@ -479,8 +489,8 @@ static CgSolve cg_describe(const unires_plan *pl, float rho, float lam, const fl
 static CgRun cg_make_run(unires_plan *pl, CgSolve s, hipStream_t st) {
   CgRun R;
   R.pl = pl, R.s = s, R.st = st;
-  R.s.chunk = cg_chunk_size();
-  R.use_graph = cg_graphs_on() && !s.fft && !pl->timing;
+  R.s.chunk = cg_switches().chunk_size();
+  R.use_graph = cg_switches().graphs && !s.fft && !pl->timing;
   return R;
 }
 
@@ -497,66 +507,29 @@ static int cg_read_back(unires_plan *pl, int max_iter, double tol, int32_t *iter
   return UNIRES_OK;
 }
 
-extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const float *b, float *x,
-                               int32_t max_iter, double tol, int32_t stop_mode,
-                               int32_t precond_mode, int32_t *iters_out, double *obj_trace,
-                               void *stream) {
-  int rc = cg_check_args(plan, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  unires_plan *pl = plan;
-  CgSolve s = cg_describe(pl, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode);
-  mark_use(pl, st);  // (before anything is enqueued: a failed start or drive below is remembered too)
-  pl->last_lockstep = 0;
-
-  // (a stream under capture - e.g. the caller's torch.cuda.graph - runs nothing until the graph is launched: the
-  // chunk feeder would wait for progress that never comes.  The whole solve then joins the capture, as in r3;
-  // kernels after convergence return at entry.)
-  if (stream_capturing(st) && tol != 0.0 && max_iter > kMaxCgIter)
-    return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
-                                "(it is fed to the device chunk by chunk, following its progress)");
-  if (cg_chunked(tol, max_iter) && !(stream_capturing(st) && max_iter <= kMaxCgIter)) {
-    pl->last_ring = 1;
-    std::vector<CgRun> runs(1, cg_make_run(pl, s, st));
-    if ((rc = cg_run_start(runs[0]))) return rc;
-    if ((rc = cg_runs_drive(runs))) return rc;
-    mark_use(pl, st);
-    CHECK_LAUNCH();
-    return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
-  }
+// One solve enqueued whole on `st`.  hipGraph replay (UNIRES_CG_GRAPH=0 disables): the ~8 launches per iteration of a
+// solve are captured once and re-launched as one graph while the arguments stay the same.  In order: replay the plan's
+// captured solve if it serves this one; else drop it, capture this one, and launch that; capture refused, or the solve
+// not one to capture: plain launches.  `how`: what the enqueue did - now, or when the graph was captured.
+static int cg_solve_whole(unires_plan *pl, const CgSolve &s, hipStream_t st, CgHow &how) {
   ++pl->cg_gen;  // (k_sc_init counts every solve)
-  // deferred iterate update: only where nothing reads x before the solve ends
-  s.ring = tol == 0.0 && !s.fft && max_iter > 0 ? cg_ring_prepare(pl, st) : 1;
-  pl->last_ring = s.ring;
-
-  // hipGraph replay (UNIRES_CG_GRAPH=0 disables): the ~8 launches per iteration of a solve are
-  // captured once and re-launched as one graph while the arguments stay the same
-  const bool graphable = cg_graphs_on() && !s.fft && max_iter > 0 && !pl->timing;  // (events go with plain launches)
-  if (graphable && pl->cg_exec && pl->cg_key.same_graph(s)) {
-    pl->last_trim = pl->graph_trim, pl->last_fused = pl->graph_fused;
-    HIP_TRY(hipGraphLaunch(pl->cg_exec, st));
-  } else {
-    if (graphable && pl->cg_exec) drop_cg_graph(pl);
-    rc = graphable ? capture_graph(st, &pl->cg_exec, [&] { return cg_enqueue(pl, s, st); }) : -1;
-    if (rc > 0) {
-      cg_resync_gen(pl);
-      return rc;
-    }
-    if (rc == 0) {
-      pl->cg_key = s;
-      pl->graph_trim = pl->last_trim, pl->graph_fused = pl->last_fused;
-      if (hipGraphLaunch(pl->cg_exec, st) != hipSuccess) {
-        cg_resync_gen(pl);
-        return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
-      }
-    } else if ((rc = cg_enqueue(pl, s, st))) {
-      cg_resync_gen(pl);
-      return rc;
-    }
+  const bool graphable = cg_switches().graphs && !s.fft && s.max_iter > 0 && !pl->timing;  // (events go with plain launches)
+  CgCaptured &G = pl->cg_whole;
+  const bool replay = graphable && G.matches(s);
+  int rc = -1;
+  if (graphable && !replay) {
+    if (G.exec) drop_cg_graph(pl);
+    rc = capture_graph(st, &G.exec, [&] { return cg_enqueue(pl, s, st, how); });
+    if (rc == 0) G.key = s, G.how = how;
   }
-  mark_use(pl, st);
-  CHECK_LAUNCH();
-  return iters_out ? cg_read_back(pl, max_iter, tol, iters_out, obj_trace, st) : UNIRES_OK;
+  if (replay || rc == 0) {
+    how = G.how;
+    rc = hipGraphLaunch(G.exec, st) == hipSuccess ? UNIRES_OK : fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
+  } else if (rc < 0) {
+    rc = cg_enqueue(pl, s, st, how);
+  }
+  if (rc) cg_resync_gen(pl);
+  return rc;
 }
 
 // --------------------------------------------------------------------------
@@ -575,11 +548,10 @@ extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const 
 namespace {
 struct Lockstep {
   std::vector<unires_plan *> plans;
-  std::vector<CgSolve> keys;
+  CgCaptured graph;            // the one executable graph all channels share (no key of its own)
+  std::vector<CgCaptured> ch;  // per channel: the solve it was captured for and what a replay reports (no graph)
   std::vector<unsigned long long> epochs;
-  std::vector<int> trim, fused;  // what unires_plan_cg_ends reports for a replay
   std::vector<hipEvent_t> joins;  // one per channel stream, and the graph's end
-  hipGraphExec_t exec = nullptr;
 };
 std::vector<Lockstep> g_lockstep;
 std::mutex g_lockstep_mutex;
@@ -588,9 +560,9 @@ constexpr size_t kMaxLockstep = 4;  // sets of plans with a captured schedule (a
 void lockstep_destroy(Lockstep &L, bool wait) {
   if (wait)
     for (unires_plan *pl : L.plans) await_use(pl);  // (a launch of the graph may still be in flight)
-  if (L.exec) (void)hipGraphExecDestroy(L.exec);
+  L.graph.destroy();
   for (hipEvent_t e : L.joins) (void)hipEventDestroy(e);
-  L.exec = nullptr, L.joins.clear();
+  L.ch.clear(), L.joins.clear();
 }
 }  // namespace
 
@@ -604,21 +576,10 @@ void unires::cg_lockstep_forget(unires_plan *pl) {
     }
 }
 
-// UNIRES_CG_LOCKSTEP (cg_lockstep_env, cg.hpp) off: one free-running chain per channel.  GPU_MAX_HW_QUEUES, read once:
-// the schedule's graph has two parallel branches, which the runtime is known to mishandle with fewer than 4 hardware
-// queues - then never.
-static bool cg_lockstep_on() {
-  static const bool on = [] {
-    const char *q = getenv("GPU_MAX_HW_QUEUES");
-    return cg_lockstep_env() && !(q && atoi(q) < 4);
-  }();
-  return on;
-}
-
 // The whole schedule on lanes lm (operators) and lv (everything else); called under capture of lm.  `ev`: fresh
-// events, one per edge.
+// events, one per edge.  how[c]: what channel c's start and iterations did.
 static int cg_lockstep_enqueue(int n, unires_plan *const *plans, const std::vector<CgSolve> &s, hipStream_t lm,
-                               hipStream_t lv, const std::vector<hipEvent_t> &ev) {
+                               hipStream_t lv, const std::vector<hipEvent_t> &ev, std::vector<CgHow> &how) {
   size_t ne = 0;
   auto edge = [&](hipStream_t from, hipStream_t to) -> int {
     hipEvent_t e = ev[ne++];
@@ -629,8 +590,8 @@ static int cg_lockstep_enqueue(int n, unires_plan *const *plans, const std::vect
   int rc = edge(lm, lv);  // fork: lane V joins the capture
   std::vector<CgIters> it((size_t)n);
   for (int c = 0; c < n && !rc; ++c) {
-    rc = cg_enqueue_start(plans[c], s[c], nullptr, lm);
-    if (!rc) rc = cg_iters_begin(plans[c], s[c], 1, s[c].max_iter, false, nullptr, it[c]);
+    rc = cg_enqueue_start(plans[c], s[c], nullptr, lm, how[c]);
+    if (!rc) rc = cg_iters_begin(plans[c], s[c], 1, s[c].max_iter, false, nullptr, it[c], how[c]);
   }
   const int N = s[0].max_iter;
   std::vector<hipEvent_t> vdone((size_t)n, nullptr);
@@ -655,7 +616,7 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
                              const float *const *b, float *const *x, int max_iter, double tol, int stop_mode,
                              int precond_mode, void *const *streams, bool *taken) {
   *taken = false;
-  if (!cg_lockstep_on() || !cg_graphs_on() || n < 2 || tol != 0.0 || max_iter < 1 ||
+  if (!cg_switches().lockstep || !cg_switches().graphs || n < 2 || tol != 0.0 || max_iter < 1 ||
       precond_mode == UNIRES_PRECOND_FFT)
     return UNIRES_OK;
   hipStream_t lm = (hipStream_t)streams[0], lv = nullptr;
@@ -674,9 +635,9 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
   Lockstep *L = nullptr;
   for (Lockstep &e : g_lockstep)
     if (e.plans == std::vector<unires_plan *>(plans, plans + n)) L = &e;
-  bool fresh = !L || !L->exec;
+  bool fresh = !L || !L->graph.exec;
   for (int c = 0; L && !fresh && c < n; ++c)
-    fresh = !L->keys[c].same_graph(s[c]) || L->epochs[c] != plans[c]->cg_epoch;
+    fresh = !L->ch[c].matches(s[c]) || L->epochs[c] != plans[c]->cg_epoch;
   if (fresh) {
     if (L) {
       lockstep_destroy(*L, true);
@@ -694,10 +655,11 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
     for (hipEvent_t &e : ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     L->joins.assign((size_t)n + 1, nullptr);
     for (hipEvent_t &e : L->joins) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    std::vector<CgHow> how((size_t)n);
     int rc = -1;
     if (ok) {
       for (int c = 0; c < n; ++c) plans[c]->lockstep = true;  // (the operators' grids are this mode's: cap_s2_ls)
-      rc = capture_graph(lm, &L->exec, [&] { return cg_lockstep_enqueue(n, plans, s, lm, lv, ev); });
+      rc = capture_graph(lm, &L->graph.exec, [&] { return cg_lockstep_enqueue(n, plans, s, lm, lv, ev, how); });
       for (int c = 0; c < n; ++c) plans[c]->lockstep = false;
     }
     for (hipEvent_t e : ev)
@@ -710,11 +672,10 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
         for (int c = 0; c < n; ++c) cg_resync_gen(plans[c]);
       return rc > 0 ? rc : UNIRES_OK;
     }
-    L->keys = s;
-    L->epochs.clear(), L->trim.clear(), L->fused.clear();
+    L->ch.assign((size_t)n, CgCaptured()), L->epochs.clear();
     for (int c = 0; c < n; ++c) {
+      L->ch[c].key = s[c], L->ch[c].how = how[c], L->ch[c].how.lockstep = 1;
       L->epochs.push_back(plans[c]->cg_epoch);
-      L->trim.push_back(plans[c]->last_trim), L->fused.push_back(plans[c]->last_fused);
     }
   }
   // the right-hand sides were enqueued on the channels' streams: the launch stream waits for every one of them, and
@@ -724,18 +685,15 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
       HIP_TRY(hipEventRecord(L->joins[c], (hipStream_t)streams[c]));
       HIP_TRY(hipStreamWaitEvent(lm, L->joins[c], 0));
     }
-  for (int c = 0; c < n; ++c) {
-    ++plans[c]->cg_gen;  // (k_sc_init counts every solve)
-    plans[c]->last_ring = s[c].ring, plans[c]->last_trim = L->trim[c], plans[c]->last_fused = L->fused[c];
-  }
-  if (hipGraphLaunch(L->exec, lm) != hipSuccess) {
+  for (int c = 0; c < n; ++c) ++plans[c]->cg_gen;  // (k_sc_init counts every solve)
+  if (hipGraphLaunch(L->graph.exec, lm) != hipSuccess) {
     for (int c = 0; c < n; ++c) cg_resync_gen(plans[c]);
     return fail(UNIRES_ERR_HIP, "hipGraphLaunch failed");
   }
   HIP_TRY(hipEventRecord(L->joins[n], lm));
   for (int c = 0; c < n; ++c) {
     if ((hipStream_t)streams[c] != lm) HIP_TRY(hipStreamWaitEvent((hipStream_t)streams[c], L->joins[n], 0));
-    plans[c]->last_lockstep = 1;
+    plans[c]->last = L->ch[c].how;
     mark_use(plans[c], (hipStream_t)streams[c]);
   }
   *taken = true;
@@ -743,26 +701,33 @@ static int cg_lockstep_solve(int n, unires_plan *const *plans, const float *rho,
   return UNIRES_OK;
 }
 
-// Several channels' solves at once, each on its own plan and stream (unires/_update.py:122-150 loops over
-// the channels; they do not couple inside the y-update): the chunks of all of them are fed from one host
-// loop, so that the channels still overlap on the device where they run on separate streams.
-extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, const float *rho, const float *lam,
-                                    const float *const *b, float *const *x, int32_t max_iter, double tol,
-                                    int32_t stop_mode, int32_t precond_mode, int32_t *iters_out,
-                                    double *obj_trace, void *const *streams) {
-  if (n < 1 || !plans || !rho || !lam || !b || !x || !streams) return fail(UNIRES_ERR_NULL, "null argument");
+// One or several solves, each on its own plan and stream (unires/_update.py:122-150 loops over the channels; they do
+// not couple inside the y-update).  Solves that can stop early are enqueued in chunks, the chunks of all of them fed from
+// one host loop, so that the channels still overlap on the device where they run on separate streams; the others whole,
+// one after the other, or - fixed-iteration solves of several channels, where switched on - as one two-lane schedule.
+static int cg_solve_n(int n, unires_plan *const *plans, const float *rho, const float *lam, const float *const *b,
+                      float *const *x, int max_iter, double tol, int stop_mode, int precond_mode, int32_t *iters_out,
+                      double *obj_trace, void *const *streams) {
   for (int c = 0; c < n; ++c) {
     const int rc = cg_check_args(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode);
     if (rc) return rc;
     for (int d = 0; d < c; ++d)
       if (plans[d] == plans[c]) return fail(UNIRES_ERR_ARG, "one plan per solve");
   }
+  auto stream = [&](int c) { return (hipStream_t)streams[c]; };
   bool capturing = false;
-  for (int c = 0; c < n; ++c) capturing = capturing || stream_capturing((hipStream_t)streams[c]);
+  for (int c = 0; c < n; ++c) capturing = capturing || stream_capturing(stream(c));
+  // (a stream under capture - e.g. the caller's torch.cuda.graph - runs nothing until the graph is launched: the
+  // chunk feeder would wait for progress that never comes.  The whole solve then joins the capture, as in r3;
+  // kernels after convergence return at entry.)
   if (capturing && tol != 0.0 && max_iter > kMaxCgIter)
     return fail(UNIRES_ERR_ARG, "a solve with a tolerance and more than 4096 iterations cannot join a stream capture "
                                 "(it is fed to the device chunk by chunk, following its progress)");
-  for (int c = 0; c < n; ++c) mark_use(plans[c], (hipStream_t)streams[c]);  // (before anything is enqueued)
+  // (before anything is enqueued: a failed start or drive below is remembered too)
+  for (int c = 0; c < n; ++c) mark_use(plans[c], stream(c));
+  auto describe = [&](int c) {
+    return cg_describe(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode);
+  };
   bool lockstep = false;
   if (!capturing) {
     const int rc = cg_lockstep_solve(n, plans, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode, streams, &lockstep);
@@ -770,33 +735,51 @@ extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, cons
   }
   if (lockstep) {
     // (enqueued as one schedule across the channels' streams)
-  } else if (!cg_chunked(tol, max_iter) || (capturing && max_iter <= kMaxCgIter)) {  // nothing to steer: each solve is enqueued whole
-    for (int c = 0; c < n; ++c) {
-      const int rc = unires_cg_solve(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode, precond_mode,
-                                     nullptr, nullptr, streams[c]);
-      if (rc) return rc;
-    }
-  } else {
+  } else if (cg_chunked(tol, max_iter) && !(capturing && max_iter <= kMaxCgIter)) {
     std::vector<CgRun> runs;
-    for (int c = 0; c < n; ++c) plans[c]->last_ring = 1, plans[c]->last_lockstep = 0;
-    for (int c = 0; c < n; ++c)
-      runs.push_back(cg_make_run(plans[c], cg_describe(plans[c], rho[c], lam[c], b[c], x[c], max_iter, tol, stop_mode,
-                                                       precond_mode), (hipStream_t)streams[c]));
+    for (int c = 0; c < n; ++c) runs.push_back(cg_make_run(plans[c], describe(c), stream(c)));
     for (CgRun &R : runs) {
       const int rc = cg_run_start(R);
       if (rc) return rc;
     }
     const int rc = cg_runs_drive(runs);
     if (rc) return rc;
-    for (int c = 0; c < n; ++c) mark_use(plans[c], (hipStream_t)streams[c]);
+    for (int c = 0; c < n; ++c) plans[c]->last = runs[c].how, mark_use(plans[c], stream(c));
     CHECK_LAUNCH();
+  } else {  // nothing to steer: each solve is enqueued whole
+    for (int c = 0; c < n; ++c) {
+      CgSolve s = describe(c);
+      // deferred iterate update: only where nothing reads x before the solve ends
+      s.ring = tol == 0.0 && !s.fft && max_iter > 0 ? cg_ring_prepare(plans[c], stream(c)) : 1;
+      CgHow how;
+      const int rc = cg_solve_whole(plans[c], s, stream(c), how);
+      if (rc) return rc;
+      plans[c]->last = how;
+      mark_use(plans[c], stream(c));
+      CHECK_LAUNCH();
+    }
   }
   if (iters_out)
     for (int c = 0; c < n; ++c) {
       const int rc = cg_read_back(plans[c], max_iter, tol, iters_out + c,
                                   obj_trace ? obj_trace + (size_t)c * (std::min(max_iter, kMaxCgIter) + 1) : nullptr,
-                                  (hipStream_t)streams[c]);
+                                  stream(c));
       if (rc) return rc;
     }
   return UNIRES_OK;
+}
+
+extern "C" int unires_cg_solve(unires_plan_t *plan, float rho, float lam, const float *b, float *x,
+                               int32_t max_iter, double tol, int32_t stop_mode,
+                               int32_t precond_mode, int32_t *iters_out, double *obj_trace,
+                               void *stream) {
+  return cg_solve_n(1, &plan, &rho, &lam, &b, &x, max_iter, tol, stop_mode, precond_mode, iters_out, obj_trace, &stream);
+}
+
+extern "C" int unires_cg_solve_many(int32_t n, unires_plan_t *const *plans, const float *rho, const float *lam,
+                                    const float *const *b, float *const *x, int32_t max_iter, double tol,
+                                    int32_t stop_mode, int32_t precond_mode, int32_t *iters_out,
+                                    double *obj_trace, void *const *streams) {
+  if (n < 1 || !plans || !rho || !lam || !b || !x || !streams) return fail(UNIRES_ERR_NULL, "null argument");
+  return cg_solve_n(n, plans, rho, lam, b, x, max_iter, tol, stop_mode, precond_mode, iters_out, obj_trace, streams);
 }

@@ -201,6 +201,31 @@ struct CgSolve {
   }
 };
 
+// How a solve went: what unires_plan_cg_ring, unires_plan_cg_ends and unires_plan_cg_lockstep report of the plan's last
+// one.  The enqueue functions (api_cg.hip) say it of what they enqueue, a captured solve keeps it for its replays, and
+// the entry point that finishes a solve puts it into the plan.
+struct CgHow {
+  int ring = 1;      // K of the deferred iterate update (1: the iterate updated every iteration)
+  int trim = 0;      // the last iteration was the operator, alpha and the iterate alone
+  int fused = 0;     // the start's residual was written by the operator's push
+  int lockstep = 0;  // the solve ran inside the channels' two-lane schedule
+};
+
+// A captured solve: the executable graph(s), the solve they were captured for, and what a replay of them reports.
+// Empty (no graph, a key that no solve has) until a capture succeeds and again after destroy().
+struct CgCaptured {
+  hipGraphExec_t exec = nullptr;   // the whole solve; of a chunked solve, the start
+  hipGraphExec_t chunk = nullptr;  // a chunked solve's `key.chunk` iterations
+  CgSolve key;
+  CgHow how;
+  bool matches(const CgSolve &s) const { return key.same_graph(s); }
+  void destroy() {  // (the caller has waited for launches in flight where there may be any)
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (chunk) (void)hipGraphExecDestroy(chunk);
+    *this = CgCaptured();
+  }
+};
+
 }  // namespace unires
 
 struct unires_plan {
@@ -227,11 +252,11 @@ struct unires_plan {
   size_t cap_g = 0, cap_x = 0;
   // the whole CG solve as one hipGraph, re-launched while (b, x, rho, lam, options) stay the
   // same - the ADMM loop calls it with identical arguments until the schedule changes
-  unires::CgSolve cg_key;
-  hipGraphExec_t cg_exec = nullptr;
-  // chunked solves: start + chunk graphs, the host-mapped progress word and the solve counter
-  unires::CgSolve cg_chunk_key;
-  hipGraphExec_t cg_start_exec = nullptr, cg_chunk_exec = nullptr;
+  unires::CgCaptured cg_whole;
+  // chunked solves: start + chunk graphs (keyed without max_iter: they serve a solve of any length), the host-mapped
+  // progress word and the solve counter
+  unires::CgCaptured cg_chunks;
+  unires::CgHow last;  // how the plan's last solve went
   unsigned long long *progress = nullptr, *progress_dev = nullptr;
   unsigned cg_gen = 0;
   float *precM = nullptr;  // Jacobi diagonal (own allocation, made by unires_precond_build)
@@ -241,10 +266,6 @@ struct unires_plan {
   int ring_slots = 0;
   bool ring_tried = false;  // the allocation was decided (made, refused by the budget, or failed)
   int ring_req = 0;         // unires_plan_cg_ring: K asked for (0: UNIRES_CG_RING or the default)
-  int last_ring = 1;        // K of the plan's last solve (1: the iterate updated every iteration)
-  // unires_plan_cg_ends: whether the plan's last solve had its last iteration trimmed / its start's residual written by
-  // the push (api_cg.hip); graph_*: the same for the captured solves, which a replay reports
-  int last_trim = 0, last_fused = 0, graph_trim = 0, graph_fused = 0, chunk_fused = 0;  // (chunk_: of cg_start_exec)
   unires::FftPre fft;      // FFT-diagonal preconditioner (plans + buffers, made on demand)
   float prec_rho = 0.f, prec_lam = 0.f;
   int prec_mode = UNIRES_PRECOND_IDENTITY;
@@ -262,12 +283,10 @@ struct unires_plan {
   int cap_s2 = 0, cap_f1 = 0;
   // the two-lane schedule of several channels' solves (api_cg.hip: cg_lockstep_solve).  cap_s2_ls: k_splat2's grid
   // cap in that mode, taken while `lockstep` is up (the schedule is being enqueued); cg_epoch: moved by drop_cg_graph,
-  // unique among all plans of the process - a schedule captured at another epoch is stale; last_lockstep: whether
-  // the plan's last solve ran in the schedule (unires_plan_cg_lockstep)
+  // unique among all plans of the process - a schedule captured at another epoch is stale
   int cap_s2_ls = 0;
   bool lockstep = false;
   unsigned long long cg_epoch = 0;
-  int last_lockstep = 0;
 };
 
 namespace unires {

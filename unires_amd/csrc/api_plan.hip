@@ -82,27 +82,24 @@ void unires::await_use(unires_plan *pl) {
 }
 
 void unires::drop_cg_chunk_graphs(unires_plan *pl) {
-  if (!pl->cg_start_exec && !pl->cg_chunk_exec) return;
+  if (!pl->cg_chunks.exec && !pl->cg_chunks.chunk) return;
   await_use(pl);
-  if (pl->cg_start_exec) (void)hipGraphExecDestroy(pl->cg_start_exec);
-  if (pl->cg_chunk_exec) (void)hipGraphExecDestroy(pl->cg_chunk_exec);
-  pl->cg_start_exec = pl->cg_chunk_exec = nullptr;
+  pl->cg_chunks.destroy();
 }
 
-// Drop the captured CG solves.  A launch of one may still be in flight (the ADMM loop never syncs):
-// wait for the plan's last use before destroying the executable graph.
 unsigned long long unires::next_cg_epoch() {
   static std::atomic<unsigned long long> epoch{0};
   return ++epoch;
 }
 
+// Drop the captured CG solves.  A launch of one may still be in flight (the ADMM loop never syncs):
+// wait for the plan's last use before destroying the executable graph.
 void unires::drop_cg_graph(unires_plan *pl) {
   pl->cg_epoch = next_cg_epoch();  // (the channels' joint schedule, kept in api_cg.hip, is stale from here on)
   drop_cg_chunk_graphs(pl);
-  if (!pl->cg_exec) return;
+  if (!pl->cg_whole.exec) return;
   await_use(pl);
-  (void)hipGraphExecDestroy(pl->cg_exec);
-  pl->cg_exec = nullptr;
+  pl->cg_whole.destroy();
 }
 
 // --------------------------------------------------------------------------
@@ -505,9 +502,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->precM) (void)hipFree(plan->precM);
   if (plan->ring) (void)hipFree(plan->ring);
   cg_lockstep_forget(plan);
-  if (plan->cg_exec) (void)hipGraphExecDestroy(plan->cg_exec);
-  if (plan->cg_start_exec) (void)hipGraphExecDestroy(plan->cg_start_exec);
-  if (plan->cg_chunk_exec) (void)hipGraphExecDestroy(plan->cg_chunk_exec);
+  plan->cg_whole.destroy(), plan->cg_chunks.destroy();
   if (plan->progress) (void)hipHostFree(plan->progress);
   if (plan->last_use) (void)hipEventDestroy(plan->last_use);
   drop_timing(plan);
@@ -535,16 +530,16 @@ extern "C" int unires_plan_cg_ring(unires_plan_t *plan, int32_t k, int32_t *last
     if (v != plan->ring_req) drop_cg_graph(plan);  // (a captured solve has its ring baked in)
     plan->ring_req = v;
   }
-  if (last) *last = plan->last_ring;
+  if (last) *last = plan->last.ring;
   return UNIRES_OK;
 }
 
-extern "C" int unires_plan_cg_lockstep(unires_plan_t *plan) { return plan ? plan->last_lockstep : 0; }
+extern "C" int unires_plan_cg_lockstep(unires_plan_t *plan) { return plan ? plan->last.lockstep : 0; }
 
 extern "C" int unires_plan_cg_ends(unires_plan_t *plan, int32_t *trimmed, int32_t *start_fused) {
   if (!plan) return fail(UNIRES_ERR_NULL, "null argument");
-  if (trimmed) *trimmed = plan->last_trim;
-  if (start_fused) *start_fused = plan->last_fused;
+  if (trimmed) *trimmed = plan->last.trim;
+  if (start_fused) *start_fused = plan->last.fused;
   return UNIRES_OK;
 }
 

@@ -20,6 +20,9 @@ static inline int vec_blocks(size_t n) {
   return (int)(b < cap ? b : cap);
 }
 
+// grid of the flat helper kernels (k_scale_shift, k_fill, k_divide, k_axpy), which take one element per thread and trip
+static inline int flat_blocks(size_t n) { return vec_blocks(n) * 4 > 4096 ? 4096 : vec_blocks(n) * 4; }
+
 #define GRID_STRIDE_VEC4(n)                                                   \
   const size_t n4 = (n) / 4;                                                  \
   const size_t stride = (size_t)gridDim.x * blockDim.x;                       \
@@ -54,8 +57,6 @@ __device__ __forceinline__ void st4_stream(float *p, size_t i, float4 v) {
 #endif
 }
 
-// obj term of nitorch cg for stop != 'e': (A(x) - 2b) * x, rounded like
-
 // z = precond(r): identity (M == nullptr) or Jacobi r / M (unires/_update.py:80-102: x / M)
 __device__ __forceinline__ float4 zval4(float4 r, const float *__restrict__ M, size_t i) {
   if (!M) return r;
@@ -65,6 +66,27 @@ __device__ __forceinline__ float4 zval4(float4 r, const float *__restrict__ M, s
 }
 __device__ __forceinline__ float zval1(float r, const float *__restrict__ M, size_t i) {
   return M ? __fdiv_rn(r, M[i]) : r;
+}
+
+// The roundings of the vector updates, each stated once (per lane; no FMA contraction).
+// x = fl(x + fl(a p))
+__device__ __forceinline__ void axpy4(float4 &x, float a, float4 p) {
+  x.x = __fadd_rn(x.x, __fmul_rn(a, p.x));
+  x.y = __fadd_rn(x.y, __fmul_rn(a, p.y));
+  x.z = __fadd_rn(x.z, __fmul_rn(a, p.z));
+  x.w = __fadd_rn(x.w, __fmul_rn(a, p.w));
+}
+// p = fl(fl(b p) + z)
+__device__ __forceinline__ void xpby4(float4 &p, float b, float4 z) {
+  p.x = __fadd_rn(__fmul_rn(b, p.x), z.x);
+  p.y = __fadd_rn(__fmul_rn(b, p.y), z.y);
+  p.z = __fadd_rn(__fmul_rn(b, p.z), z.z);
+  p.w = __fadd_rn(__fmul_rn(b, p.w), z.w);
+}
+// the float64 sum, x to w, of the four products, each rounded to float32
+__device__ __forceinline__ double dot4(float4 a, float4 b) {
+  return (double)__fmul_rn(a.x, b.x) + (double)__fmul_rn(a.y, b.y) + (double)__fmul_rn(a.z, b.z) +
+         (double)__fmul_rn(a.w, b.w);
 }
 
 // r = b - A(x); z = precond(r); p = z; partial[0..G) = sum r*z; partial2 = sum (Ax-2b)*x (optional)
@@ -85,8 +107,7 @@ __global__ void __launch_bounds__(kBlock)
     st4(r, i, vr);
     const float4 vz = zval4(vr, M, i);
     st4(p, i, vz);
-    rr += (double)__fmul_rn(vr.x, vz.x) + (double)__fmul_rn(vr.y, vz.y) +
-          (double)__fmul_rn(vr.z, vz.z) + (double)__fmul_rn(vr.w, vz.w);
+    rr += dot4(vr, vz);
     if (part_obj) {
       const float4 vx = ld4(x, i);
       ob += (double)obj_term(va.x, vb.x, vx.x) + (double)obj_term(va.y, vb.y, vx.y) +
@@ -118,8 +139,7 @@ __global__ void __launch_bounds__(kBlock)
   double acc = 0.0;
   for (size_t i = tid0; i < n4; i += stride) {
     const float4 va = ld4(a, i), vb = ld4(b, i);
-    acc += (double)__fmul_rn(va.x, vb.x) + (double)__fmul_rn(va.y, vb.y) +
-           (double)__fmul_rn(va.z, vb.z) + (double)__fmul_rn(va.w, vb.w);
+    acc += dot4(va, vb);
   }
   for (size_t i = n4 * 4 + tid0; i < n; i += stride) acc += (double)__fmul_rn(a[i], b[i]);
   const double t = block_sum(acc);
@@ -147,10 +167,7 @@ __global__ void __launch_bounds__(kBlock)
     if (XUPD) {
       const float4 vp = ld4(p, i);
       vx = ld4(x, i);
-      vx.x = __fadd_rn(vx.x, __fmul_rn(alpha, vp.x));
-      vx.y = __fadd_rn(vx.y, __fmul_rn(alpha, vp.y));
-      vx.z = __fadd_rn(vx.z, __fmul_rn(alpha, vp.z));
-      vx.w = __fadd_rn(vx.w, __fmul_rn(alpha, vp.w));
+      axpy4(vx, alpha, vp);
       st4(x, i, vx);
     }
     vr.x = __fsub_rn(vr.x, __fmul_rn(alpha, va.x));
@@ -159,8 +176,7 @@ __global__ void __launch_bounds__(kBlock)
     vr.w = __fsub_rn(vr.w, __fmul_rn(alpha, va.w));
     st4(r, i, vr);
     const float4 vz = zval4(vr, M, i);
-    rr += (double)__fmul_rn(vr.x, vz.x) + (double)__fmul_rn(vr.y, vz.y) +
-          (double)__fmul_rn(vr.z, vz.z) + (double)__fmul_rn(vr.w, vz.w);
+    rr += dot4(vr, vz);
     if (XUPD && part_obj) {
       const float4 vb = ld4(b, i);
       ob += (double)__fmul_rn(vx.x, __fadd_rn(vb.x, vr.x)) +
@@ -201,16 +217,10 @@ __global__ void __launch_bounds__(kBlock)
     float4 vp = ld4(p, i);
     if (XUPD) {
       float4 vx = ld4_stream(x, i);
-      vx.x = __fadd_rn(vx.x, __fmul_rn(alpha, vp.x));
-      vx.y = __fadd_rn(vx.y, __fmul_rn(alpha, vp.y));
-      vx.z = __fadd_rn(vx.z, __fmul_rn(alpha, vp.z));
-      vx.w = __fadd_rn(vx.w, __fmul_rn(alpha, vp.w));
+      axpy4(vx, alpha, vp);
       st4_stream(x, i, vx);
     }
-    vp.x = __fadd_rn(__fmul_rn(beta, vp.x), vr.x);
-    vp.y = __fadd_rn(__fmul_rn(beta, vp.y), vr.y);
-    vp.z = __fadd_rn(__fmul_rn(beta, vp.z), vr.z);
-    vp.w = __fadd_rn(__fmul_rn(beta, vp.w), vr.w);
+    xpby4(vp, beta, vr);
     st4(p, i, vp);
   }
   for (size_t i = n4 * 4 + tid0; i < n; i += stride) {
@@ -246,10 +256,7 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t i = tid0; i < n4; i += stride) {
     const float4 vz = zval4(ld4(r, i), M, i);
     float4 vp = ld4_stream(p_in, i);  // (see below)
-    vp.x = __fadd_rn(__fmul_rn(beta, vp.x), vz.x);
-    vp.y = __fadd_rn(__fmul_rn(beta, vp.y), vz.y);
-    vp.z = __fadd_rn(__fmul_rn(beta, vp.z), vz.z);
-    vp.w = __fadd_rn(__fmul_rn(beta, vp.w), vz.w);
+    xpby4(vp, beta, vz);
     st4(p_out, i, vp);
   }
   for (size_t i = n4 * 4 + tid0; i < n; i += stride)
@@ -300,16 +307,10 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
       for (int j = 0; j < H; ++j) {
         if (!c[h + j]) continue;
-        vx.x = __fadd_rn(vx.x, __fmul_rn(a[h + j], vp[j].x));
-        vx.y = __fadd_rn(vx.y, __fmul_rn(a[h + j], vp[j].y));
-        vx.z = __fadd_rn(vx.z, __fmul_rn(a[h + j], vp[j].z));
-        vx.w = __fadd_rn(vx.w, __fmul_rn(a[h + j], vp[j].w));
+        axpy4(vx, a[h + j], vp[j]);
         if (PUPD && h + j == m - 1) {  // (c[m - 1] = !done)
           float4 b = vp[j];
-          b.x = __fadd_rn(__fmul_rn(beta, b.x), vz.x);
-          b.y = __fadd_rn(__fmul_rn(beta, b.y), vz.y);
-          b.z = __fadd_rn(__fmul_rn(beta, b.z), vz.z);
-          b.w = __fadd_rn(__fmul_rn(beta, b.w), vz.w);
+          xpby4(b, beta, vz);
           st4(p_out, i, b);
         }
       }
@@ -341,10 +342,7 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t i = tid0; i < n4; i += stride) {
     const float4 vp = ld4_stream(p, i);
     float4 vx = ld4_stream(x, i);
-    vx.x = __fadd_rn(vx.x, __fmul_rn(alpha, vp.x));
-    vx.y = __fadd_rn(vx.y, __fmul_rn(alpha, vp.y));
-    vx.z = __fadd_rn(vx.z, __fmul_rn(alpha, vp.z));
-    vx.w = __fadd_rn(vx.w, __fmul_rn(alpha, vp.w));
+    axpy4(vx, alpha, vp);
     st4_stream(x, i, vx);
   }
   for (size_t i = n4 * 4 + tid0; i < n; i += stride) x[i] = __fadd_rn(x[i], __fmul_rn(alpha, p[i]));
@@ -596,14 +594,6 @@ __global__ void __launch_bounds__(kBlock) k_sum_to(const double *part, int g, do
 // ---- launchers -------------------------------------------------------------
 int vec_num_blocks(size_t n) { return vec_blocks(n); }
 
-bool cg_lockstep_env() {
-  static const bool on = [] {
-    const char *e = getenv("UNIRES_CG_LOCKSTEP");
-    return e ? e[0] != '0' : kLockstepDefault;
-  }();
-  return on;
-}
-
 void launch_residual_init(const float *b, const float *ax, const float *x, float *r, float *p,
                           size_t n, double *part_rr, double *part_obj, const float *M,
                           hipStream_t st) {
@@ -660,16 +650,14 @@ __global__ void __launch_bounds__(kBlock) k_scale_shift(float a, float c, float 
     y[i] = __fadd_rn(__fmul_rn(a, y[i]), c);
 }
 void launch_scale_shift(float a, float c, float *y, size_t n, hipStream_t st) {
-  hipLaunchKernelGGL(k_scale_shift, dim3(vec_blocks(n) * 4 > 4096 ? 4096 : vec_blocks(n) * 4),
-                     dim3(kBlock), 0, st, a, c, y, n);
+  hipLaunchKernelGGL(k_scale_shift, dim3(flat_blocks(n)), dim3(kBlock), 0, st, a, c, y, n);
 }
 __global__ void __launch_bounds__(kBlock) k_fill(float v, float *__restrict__ y, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = v;
 }
 void launch_fill(float v, float *y, size_t n, hipStream_t st) {
-  hipLaunchKernelGGL(k_fill, dim3(vec_blocks(n) * 4 > 4096 ? 4096 : vec_blocks(n) * 4), dim3(kBlock), 0,
-                     st, v, y, n);
+  hipLaunchKernelGGL(k_fill, dim3(flat_blocks(n)), dim3(kBlock), 0, st, v, y, n);
 }
 __global__ void __launch_bounds__(kBlock)
     k_divide(const float *__restrict__ a, const float *__restrict__ m, float *__restrict__ y, size_t n) {
@@ -678,12 +666,10 @@ __global__ void __launch_bounds__(kBlock)
     y[i] = __fdiv_rn(a[i], m[i]);
 }
 void launch_div(const float *a, const float *m, float *y, size_t n, hipStream_t st) {
-  hipLaunchKernelGGL(k_divide, dim3(vec_blocks(n) * 4 > 4096 ? 4096 : vec_blocks(n) * 4), dim3(kBlock), 0,
-                     st, a, m, y, n);
+  hipLaunchKernelGGL(k_divide, dim3(flat_blocks(n)), dim3(kBlock), 0, st, a, m, y, n);
 }
 void launch_axpy(float a, const float *x, float *y, size_t n, hipStream_t st) {
-  hipLaunchKernelGGL(k_axpy, dim3(vec_blocks(n) * 4 > 4096 ? 4096 : vec_blocks(n) * 4),
-                     dim3(kBlock), 0, st, a, x, y, n);
+  hipLaunchKernelGGL(k_axpy, dim3(flat_blocks(n)), dim3(kBlock), 0, st, a, x, y, n);
 }
 void launch_sc_init(CgState *s, const double *part_rr, const double *part_obj, int g, int mode,
                     int check, unsigned long long *hostw, hipStream_t st) {

@@ -32,9 +32,10 @@ __host__ __device__ inline unsigned long long cg_progress_word(unsigned gen, int
   return ((unsigned long long)gen << 32) | (done ? 0x80000000ull : 0ull) | (unsigned)(iters & 0x7fffffff);
 }
 
-// UNIRES_CG_LOCKSTEP, read once per process: 1 takes the two-lane schedule of several channels' fixed-iteration solves
-// (api_cg.hip) and what makes room for it - the flush applied in two halves.  Off unless asked for: measured, every
-// kernel takes about twice as long under the other lane's and the job is 4 - 12 % slower (experiments/E20).
+// UNIRES_CG_LOCKSTEP, read once per process with the other switches of the CG driver (api_cg.hip: CgSwitches, which
+// defines cg_lockstep_env): 1 takes the two-lane schedule of several channels' fixed-iteration solves and what makes
+// room for it - the flush applied in two halves.  Off unless asked for: measured, every kernel takes about twice as long
+// under the other lane's and the job is 4 - 12 % slower (experiments/E20).
 constexpr bool kLockstepDefault = false;
 bool cg_lockstep_env();
 int vec_num_blocks(size_t n);  // grid (= number of partials) of the vector kernels
