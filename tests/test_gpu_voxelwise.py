@@ -151,6 +151,79 @@ sep2_gauss_noyx, sep2_gauss_march 0.730 (A^T v; A^T A p 0.297 in all three), sep
 0.111, sep2_z1032 0.138, sep3_x150 0.203, sep3_x150_nopull2 0.203.  With a non-forward D: sep2_gauss q 0.026 / 0.050, b
 0.391 / 0.412; sep2_rect q 0.076 / 0.153, b 0.391 / 0.391.  No case failed: no kernel is wrong across a seam.
 
+The one-kernel matvec forms (``ONE_KERNEL_CASES``; shift.hip, aligned.hip).  Which instantiation holds the whole matvec
+is decided by shape and alignment alone (launch_ata_shift, shift_nl, shift_xr, shift_fast, shift_build; launch_lines,
+launch_ata_aligned, launch_dtd_lines) and repeat_info only says that the shift tables exist.  With
+UNIRES_MATVEC_VERBOSE=1 the child reports on stderr every instantiation it launches ([matvec] lines: the name with its
+template arguments - k_ata_shift_m<NL, DOT, OBJ, FAST>, k_ata_shift2 / k_ata_shift<DOT, OBJ>, k_ata_aligned<NP, DOT, OBJ>,
+k_ata_aligned4<NP4, DOT, OBJ>, k_ata_aligned4x2<DOT, OBJ> - the grid, and the run-time facts that select code inside it); a
+case's ``matvec`` entry names the form that must run, a condition on those facts, and for aligned.hip the caller; any
+other one-kernel launch is drift, like ``expect``.  The one-kernel forms serve the matvec only (A p, A^T v and A^T A p of
+proj_apply run the general kernels: the combs and the adjoint identity check those, on these geometries), so for
+these cases the child also assembles b = plan.rhs and runs the two one-iteration solves of the non-forward table with
+forward differences: the matvec with its dot is the <.., 1, 0> instantiation, entry 0 of a 'max_gain' solve comes from a
+stored <.., 0, 0> matvec, entry 1 of a 'max_gain_fresh' solve is the <.., 1, 1> one (the data term read from registers,
+nothing stored); both objectives are held to ``obj_check``'s bound with ref64's bound_matvec as the float64 side, and
+all three instantiations must be among the [matvec] lines.  Every case: thick slices along z, no rotation, an exact
+translation (make_problem(shift=): at thick 6 the first point of the trimmed grid the kernels run on lies at z =
+shift_z - 3, and oz is its floor), seed 11, scl 0.1; comb tile (4, 2, 64): the x run, the pair of lines, the 4-voxel lane.  No voxel of any case is a FOV tie.
+
+| case            | dim_y, thick, shift            | there for                              | [matvec] observed on an MI355X (the <.., 1, 0> line)           |
+|-----------------|--------------------------------|----------------------------------------|----------------------------------------------------------------|
+| tr_yodd         | 41x37x60, 6, (.3, -.6, .4)     | odd y: NL = 1 (shift_nl)               | k_ata_shift_m<1,1,0,0> grid 102 xr 4 lw 1 padl 4 padr 0 nf 8   |
+| tr_yodd_z256    | 12x9x256, 6, (.3, -.6, 2.4)    | NL = 1, FAST (256-voxel lines)         | k_ata_shift_m<1,1,0,1> grid 7 xr 4 lw 1 padl 4 padr 0 nf 8     |
+| int_yodd_z256   | 10x11x256, 6, (2, -1, 3)       | integer weights through it (tried      | k_ata_shift_m<1,1,0,1> grid 9 xr 4 lw 1 padl 0 padr 0 nf 8     |
+|                 |                                | before the aligned kernel)             |                                                                |
+| tr_thick2       | 20x18x40, 2, (.3, -.6, .4)     | stride 2, nf = 4; shift_build finds    | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 1 nf 4    |
+|                 |                                | four-entry lane windows: lw 1          |                                                                |
+| tr_thick3       | 20x18x48, 3, the same          | nf = 6 (five taps: see below)          | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 1 nf 6    |
+| tr_thick4       | 20x18x48, 4, the same          | nf = 6                                 | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 0 nf 6    |
+| tr_xdz128       | 12x10x256, 2, the same         | xd.z = 128 > 64: no lane window (lw    | k_ata_shift_m<2,1,0,0> grid 4 xr 4 lw 0 padl 4 padr 1 nf 4     |
+|                 |                                | 0), zline_taps, its k0 loop twice      |                                                                |
+| tr_zpos         | 20x18x60, 6, (.3, -.6, 9.6)    | right apron (oz 6, padr 8)             | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 0 padr 8 nf 8    |
+| tr_zneg         | 20x18x60, 6, (.3, -.6, -7.4)   | left apron (oz -11), empty e / e4 rows | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 12 padr 0 nf 8   |
+| tr_xyout        | 20x18x60, 6, (-3.3, 4.6, .4)   | masked rows of cx / cy, planes and     | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 0 nf 8    |
+|                 |                                | lines wholly outside                   |                                                                |
+| tr_z8           | 9x6x8, 2, (.3, -.6, .4)        | the shortest line, two live lanes      | k_ata_shift_m<2,1,0,0> grid 3 xr 4 lw 1 padl 4 padr 1 nf 4     |
+| tr_x3           | 3x4x8, 2, the same             | dim_y.x < 4 <= xr: one run, both faces | k_ata_shift_m<2,1,0,0> grid 1 xr 4 lw 1 padl 4 padr 1 nf 4     |
+| tr_z260         | 9x6x260, 6, the same           | just outside (z > 256): shift False    | none: the general pair                                         |
+| tr_x1028        | 1028x6x8, 2, the same          | x > 1024 (shift_xr 0), even y          | k_ata_shift2<1,0> grid 1542 xr 0 lw 1 padl 4 padr 1 nf 4       |
+| tr_x1028_yodd   | 1028x5x8, 2, the same          | the same, odd y                        | k_ata_shift<1,0> grid 1285 xr 0 lw 1 padl 4 padr 1 nf 4        |
+| tr_tri4         | 20x18x48, 4, prof_tp 1, (.3,   | nine taps at stride 4: fan-in 3, which | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 2 nf 10   |
+|                 | -.6, .4)                       | shift_build's triples hold             |                                                                |
+| int_tri4        | the same, (2, -1, 3)           | launch_ata_aligned declines (fan-in >  | k_ata_shift_m<2,1,0,0> grid 12 xr 4 lw 1 padl 4 padr 5 nf 10   |
+|                 |                                | 2); the shift kernel takes it          |                                                                |
+| int_yodd_z60    | 41x37x60, 6, (2, -1, 3)        | 16-byte form, odd y                    | k_ata_aligned4<1,1,0> grid 380 ata padl 4 padr 1 nk 7 s 6      |
+| int_z300        | 9x8x300, 6, the same           | two 256-voxel passes per line          | k_ata_aligned4<2,1,0> grid 18 ata padl 4 padr 1 nk 7 s 6       |
+| int_z203 / _323 | 9x8x203 / 323 / 451, the same  | the dword form at 4 / 6 / 8 passes     | k_ata_aligned<4,1,0> / <6,1,0> / <8,1,0> grid 18 ata padl 1    |
+| / _451          |                                |                                        | padr 1 nk 7 s 6                                                |
+| int_z512 / _516 | 9x8x512 / 516, the same        | either side of the limit               | k_ata_aligned4<2,1,0> (as int_z300) / none: the general pair   |
+| int_zneg        | 20x18x61, 6, (2, -1, -5)       | left apron (oz -8)                     | k_ata_aligned<2,1,0> grid 90 ata padl 8 padr 1 nk 7 s 6        |
+| int_zpos        | 20x18x61, 6, (2, -1, 9)        | right apron (oz 6)                     | k_ata_aligned<2,1,0> grid 90 ata padl 1 padr 6 nk 7 s 6        |
+| id_z203 / _323  | 9x8x203 / 323 / 451, A = I,    | the line stencil at npt 4 / 6 / 8      | k_ata_aligned<4,1,0> / <6,1,0> / <8,1,0> grid 18 dtd padl 1    |
+| / _451          | UNIRES_NO_FLAT=1               |                                        | padr 1 nk 1 s 1                                                |
+| id_z516         | 9x8x516, the same              | past launch_dtd_lines' 512             | none: k_dtd                                                    |
+
+Each case with A != I also showed the <.., 0, 0> and <.., 1, 1> lines of the same instantiation with the same facts.
+Expectations the code settled otherwise than first written down: tr_thick3 was put down for nf = 5, but a rect
+profile's taps are symmetric about their centre and so odd in number - 3, 5, 5, 7 at ratio 2, 3, 4, 6 (trim_taps keeps all
+of them) - so ratio 3 runs on five taps like ratio 4, nf = 6, and no rect profile gives nf = 5; the tap counts that are
+no multiple of four are 6 and the triangle's 10.  tr_thick2 was expected on the per-voxel triples (stride below 4); shift_build
+tests the windows themselves, and at stride 2 with three taps the four rows of every lane span at most four x-space
+entries, so lw 1: the triple form (lw 0) is reached through xd.z > 64 alone (tr_xdz128).
+
+Observed on an MI355X (largest err / tol over every check of the case; no voxel excluded in any): tr_yodd 0.028,
+tr_yodd_z256 0.037, int_yodd_z256 0.030, tr_thick2 0.018, tr_thick3 0.024, tr_thick4 0.024, tr_xdz128 0.022, tr_zpos 0.035,
+tr_zneg 0.044, tr_xyout 0.041, tr_z8 0.025, tr_x3 0.019, tr_z260 0.025, tr_x1028 0.027, tr_x1028_yodd 0.023, tr_tri4 0.022,
+int_tri4 0.020, int_yodd_z60 0.024, int_z300 0.023, int_z203 0.018, int_z323 0.026, int_z451 0.031, int_z512 0.023, int_z516
+0.025, int_zneg 0.028, int_zpos 0.029, id_z203 0.110, id_z323 0.148, id_z451 0.189, id_z516 0.138; the objectives at most
+0.003 of their bound.  One kernel bug found and fixed: k_ata_aligned4<2> (int_z300, int_z512: q off by up to 1e4 times
+its tolerance in the two voxels z = 255 and 256 of every line, 144 voxels a case).  Its lanes take the z neighbour across
+the seam of the two 256-voxel passes from the other pass' register with __builtin_amdgcn_readlane; the builtin is
+declared on int, so handed a float it returned the neighbour truncated to an integer, and the stencil's z differences
+at the seam were off by the neighbour's fraction.  aligned.hip now passes the bits (a4_readlane).  The norm gates
+could not see two voxels in 300.
+
 The table with a non-forward D (``DIFF_CASES``, ``test_every_form_per_voxel_with_backward_and_central_differences``).
 A plan with sett.diff = 'backward' / 'central' composes its matvec differently (api_operator.hip, matvec):
 every AtA kernel runs without its stencil epilogue, and one pass - k_dtd_flat_w<W, ACC>, or k_dtd<W, ACC> where the
@@ -173,6 +246,20 @@ sep2_gauss and sep2_rect: without the stencil epilogue the accumulating stores b
 | int_shift_z256     | (2, -1, 3); thick 6 along z                     | only), tried first by a one-repeat plan             |
 | z_unaligned,       | z_thick's / denoise's, out= a view 1, 2, 3      | head, the per-voxel tail and ld4_safe(rq) of the    |
 | dn_unaligned       | floats into a sentinel-padded buffer            | ACC pass; pads unchanged, every voxel written       |
+| tr_yodd, tr_x1028, | ONE_KERNEL_CASES' by name                       | the <.., 0, 0> instantiations of k_ata_shift_m<1>,  |
+| tr_x1028_yodd,     |                                                 | k_ata_shift2, k_ata_shift, the triple form (lw 0),  |
+| tr_xdz128, tr_zpos,|                                                 | a right apron, k_ata_aligned4<1>, <2> and           |
+| int_yodd_z60,      |                                                 | k_ata_aligned<6>: zero stencil weights, no partials,|
+| int_z300, int_z323 |                                                 | stencil_close behind them                           |
+| translate_unaligned| translate's, out= as z_unaligned                | launch_ata_shift declines an unaligned q: the       |
+|                    |                                                 | general pair, no [matvec] line before the solves    |
+| int_z60_unaligned  | int_shift_z60's, out= as z_unaligned            | launch_lines leaves k_ata_aligned4x2 for the dword  |
+|                    |                                                 | form k_ata_aligned<2,0,0>                           |
+
+With a non-forward D every one-kernel launch must be a <.., 0, 0> instantiation (``matvec_drift``), the case's among them.
+The two unaligned cases state the form of the matvecs into the unaligned ``out``; the child marks on stderr where its
+first right-hand side and solve begin ([phase]), which run on aligned vectors of their own and so on the 16-byte
+forms (observed: k_ata_shift_m<2,0,0,0> / k_ata_aligned4x2<0,0>, both only after the mark).
 
 int_shift_z60 does not reach the shift kernel's fast form (shift_fast wants 256-voxel lines): at z = 60 an integer
 shift runs aligned.hip's 16-byte form; the two z256 cases are there for that branch.
@@ -184,7 +271,10 @@ Observed on an MI355X (err / tol, backward / central; no voxel excluded in any c
 (translate_noshift), 0.024 / 0.025 (int_shift, int_shift_noalign), 0.029 / 0.029 (int_shift_z60), 0.114 / 0.123
 (identity), 0.040 / 0.073 (orient_9), 0.083 / 0.089 (z_aniso), 0.094 / 0.134 (dn_aniso), 0.104 / 0.223 (sr_2rep),
 0.119 / 0.176 (dn_2rep), 0.009 / 0.010 (dn_under64), 0.045 / 0.079 (dn_nz3), 0.031 / 0.024
-(translate_z256), 0.024 / 0.024 (int_shift_z256); the right-hand side b 0.014 - 0.563
+(translate_z256), 0.024 / 0.024 (int_shift_z256), 0.028 / 0.023 (tr_yodd), 0.027 / 0.017 (tr_x1028), 0.020 / 0.015
+(tr_x1028_yodd), 0.017 / 0.013 (tr_xdz128), 0.035 / 0.040 (tr_zpos), 0.024 / 0.026 (int_yodd_z60), 0.021 / 0.023 (int_z300),
+0.024 / 0.026 (int_z323), 0.037 / 0.033 (translate_unaligned, all three offsets), 0.029 / 0.029 (int_z60_unaligned); the
+right-hand side b 0.014 - 0.563
 (largest: iso2_gauss 0.530 / 0.563, identity 0.454 / 0.478, z_aniso 0.406 / 0.409); the objectives at most 0.022 of
 their bound (dn_under64, central; 0.005 and below elsewhere); every dot inside the float64 summation's slack.  No
 case failed: the table found no kernel bug.
@@ -206,12 +296,23 @@ SENT = -7.75e37  # sentinel of the pads around an unaligned output
 NONFWD = ('backward', 'central')
 
 
-def _c(kw, env=None, conc=1, expect=None, light=False, seed=11, unaligned=False, conv=None, tile=None, spacing=None):
+def _c(kw, env=None, conc=1, expect=None, light=False, seed=11, unaligned=False, conv=None, tile=None, spacing=None,
+       matvec=None):
     """``conv``: (kernels of conv.hip that must launch, those only A p alone launches, those that must not), by name
     with or without template arguments; ``tile``: where ``comb`` puts its deltas (default: the splat tile);
-    ``spacing``: the y-space comb spacing where ``spacings`` is too narrow for the case's taps."""
+    ``spacing``: the y-space comb spacing where ``spacings`` is too narrow for the case's taps; ``matvec``: the
+    one-kernel matvec form the case must run (``_mv``), checked by ``matvec_drift`` - a case that has one also runs
+    the forward objectives."""
     return dict(kw=kw, env=env or {}, conc=conc, expect=expect, light=light, seed=seed, unaligned=unaligned,
-                conv=conv, tile=tile, spacing=spacing)
+                conv=conv, tile=tile, spacing=spacing, matvec=matvec)
+
+
+def _mv(kernel, where=None, src='ata'):
+    """A ``matvec`` entry.  ``kernel``: the instantiation's [matvec] name with '{}' where its DOT, OBJ arguments
+    stand ('k_ata_shift_m<1,{},0>': NL = 1, not FAST), or None: no one-kernel form may launch; ``where``: a condition
+    on the run-time facts of its line (a dict: grid, xr, lw, padl, padr, nf / padl, padr, nk, s); ``src``: the caller
+    launch_lines reports ('ata': launch_ata_aligned, 'dtd': launch_dtd_lines; lines of shift.hip carry none)."""
+    return dict(kernel=kernel, where=where, src=src)
 
 
 _Z = dict(dim_y=(41, 38, 61), thick=6, thick_axes=[2], rot=0.1, trans=2.0, scl=0.1)
@@ -331,6 +432,66 @@ SEAM_CASES = {
 }
 CASES.update(SEAM_CASES)
 
+# Every one-kernel matvec form (shift.hip, aligned.hip) and the edges of their domains: the table in the module
+# docstring.  Thick slices along z, no rotation, an exact translation (make_problem(shift=)), seed 11, scl 0.1.  The
+# expected instantiation is read off launch_ata_shift / shift_nl / shift_xr / shift_fast / shift_build and launch_lines /
+# launch_ata_aligned / launch_dtd_lines; the child's [matvec] lines (UNIRES_MATVEC_VERBOSE=1) must show it.
+_FRAC, _INT = (0.3, -0.6, 0.4), (2.0, -1.0, 3.0)
+_OKT = (4, 2, 64)  # the kernels' own seams: the x run (xr = 4 at these sizes), the pair of lines, the 4-voxel lane
+
+
+def _ok(dim_y, thick, shift, matvec, expect=None, **kw):
+    spacing = kw.pop('spacing', None)
+    return _c(dict(dim_y=dim_y, thick=thick, thick_axes=[2], shift=shift, scl=0.1, **kw), expect=expect, tile=_OKT,
+              spacing=spacing, matvec=matvec)
+
+
+def _id(nz, matvec):
+    return _c(dict(dim_y=(9, 8, nz), regime='id'), {'UNIRES_NO_FLAT': '1'}, expect=lambda i: i['regime'] == 'identity',
+              tile=_OKT, matvec=matvec)
+
+
+_shift, _noshift = (lambda i: i['shift']), (lambda i: not i['shift'])
+_M2, _M1 = 'k_ata_shift_m<2,{},0>', 'k_ata_shift_m<1,{},0>'
+ONE_KERNEL_CASES = {
+    'tr_yodd': _ok((41, 37, 60), 6, _FRAC, _mv(_M1), _shift),
+    'tr_yodd_z256': _ok((12, 9, 256), 6, (0.3, -0.6, 2.4), _mv('k_ata_shift_m<1,{},1>', lambda f: f['lw'] == 1), _shift),
+    'int_yodd_z256': _ok((10, 11, 256), 6, _INT, _mv('k_ata_shift_m<1,{},1>', lambda f: f['lw'] == 1), _shift),
+    'tr_thick2': _ok((20, 18, 40), 2, _FRAC, _mv(_M2, lambda f: f['nf'] == 4), _shift),
+    # (a rect profile's taps are symmetric about their centre, so their count is odd: 3, 5, 5, 7 at ratio 2, 3, 4, 6 -
+    # ratio 3 keeps five taps like ratio 4, nf = 6; no rect profile gives nf = 5.  nf = 6 and the triangle's 10 are the
+    # counts that are no multiple of four)
+    'tr_thick3': _ok((20, 18, 48), 3, _FRAC, _mv(_M2, lambda f: f['nf'] == 6), _shift),
+    'tr_thick4': _ok((20, 18, 48), 4, _FRAC, _mv(_M2, lambda f: f['nf'] == 6), _shift),
+    'tr_xdz128': _ok((12, 10, 256), 2, _FRAC, _mv(_M2, lambda f: f['lw'] == 0), _shift),
+    'tr_zpos': _ok((20, 18, 60), 6, (0.3, -0.6, 9.6), _mv(_M2, lambda f: f['padr'] > 0), _shift),
+    'tr_zneg': _ok((20, 18, 60), 6, (0.3, -0.6, -7.4), _mv(_M2, lambda f: f['padl'] >= 12), _shift),
+    'tr_xyout': _ok((20, 18, 60), 6, (-3.3, 4.6, 0.4), _mv(_M2), _shift),
+    'tr_z8': _ok((9, 6, 8), 2, _FRAC, _mv(_M2), _shift),
+    'tr_x3': _ok((3, 4, 8), 2, _FRAC, _mv(_M2, lambda f: f['xr'] == 4), _shift),
+    'tr_z260': _ok((9, 6, 260), 6, _FRAC, _mv(None), _noshift),
+    'tr_x1028': _ok((1028, 6, 8), 2, _FRAC, _mv('k_ata_shift2<{}>', lambda f: f['xr'] == 0), _shift),
+    'tr_x1028_yodd': _ok((1028, 5, 8), 2, _FRAC, _mv('k_ata_shift<{}>', lambda f: f['xr'] == 0), _shift),
+    # (nine taps at stride 4: a fan-in of three x-space voxels - launch_ata_aligned declines (> 2), shift_build's
+    # triples hold it; the default spacing (15, 15, 33) is wider than the nine taps' 2 (9 + 1) + 1 = 21, and is stated)
+    'tr_tri4': _ok((20, 18, 48), 4, _FRAC, _mv(_M2, lambda f: f['nf'] == 10), _shift, prof_tp=1, spacing=(15, 15, 33)),
+    'int_tri4': _ok((20, 18, 48), 4, _INT, _mv(_M2, lambda f: f['nf'] == 10), _shift, prof_tp=1, spacing=(15, 15, 33)),
+    'int_yodd_z60': _ok((41, 37, 60), 6, _INT, _mv('k_ata_aligned4<1,{}>'), _shift),
+    'int_z300': _ok((9, 8, 300), 6, _INT, _mv('k_ata_aligned4<2,{}>'), _noshift),
+    'int_z203': _ok((9, 8, 203), 6, _INT, _mv('k_ata_aligned<4,{}>'), _noshift),
+    'int_z323': _ok((9, 8, 323), 6, _INT, _mv('k_ata_aligned<6,{}>'), _noshift),
+    'int_z451': _ok((9, 8, 451), 6, _INT, _mv('k_ata_aligned<8,{}>'), _noshift),
+    'int_z512': _ok((9, 8, 512), 6, _INT, _mv('k_ata_aligned4<2,{}>'), _noshift),
+    'int_z516': _ok((9, 8, 516), 6, _INT, _mv(None), _noshift),
+    'int_zneg': _ok((20, 18, 61), 6, (2.0, -1.0, -5.0), _mv('k_ata_aligned<2,{}>', lambda f: f['padl'] > 1), _noshift),
+    'int_zpos': _ok((20, 18, 61), 6, (2.0, -1.0, 9.0), _mv('k_ata_aligned<2,{}>', lambda f: f['padr'] > 1), _noshift),
+    'id_z203': _id(203, _mv('k_ata_aligned<4,{}>', src='dtd')),
+    'id_z323': _id(323, _mv('k_ata_aligned<6,{}>', src='dtd')),
+    'id_z451': _id(451, _mv('k_ata_aligned<8,{}>', src='dtd')),
+    'id_z516': _id(516, _mv(None)),
+}
+CASES.update(ONE_KERNEL_CASES)
+
 # The rotation sweep: the form each geometry runs at each angle, as observed on an MI355X: (pull2, splat2 axis,
 # k_ata1, schedule build).  Without any env switch: from 0.3 rad on, a tile overflows its 128-entry staging slot
 # and the schedule takes the two-pass build (up to 48 instructions per tile); at 0.7 rad a tile needs more than
@@ -392,6 +553,15 @@ DIFF_CASES.update({
     'z_unaligned': _c(_Z, expect=_z_form, unaligned=True),
     'dn_unaligned': _c(_DN, expect=lambda i: i['fused'], unaligned=True),
 })
+# the one-kernel forms under a non-forward D: zero stencil weights, no partials (the <0,0> instantiations),
+# stencil_close behind them - the marching kernel with one line per wave, the two fallbacks of x > 1024, the triple
+# form of the z operator, a right apron, and three instantiations of aligned.hip
+for _n in ('tr_yodd', 'tr_x1028', 'tr_x1028_yodd', 'tr_xdz128', 'tr_zpos', 'int_yodd_z60', 'int_z300', 'int_z323'):
+    DIFF_CASES[_n] = ONE_KERNEL_CASES[_n]
+# q 4, 8 and 12 bytes off a 16-byte boundary: launch_ata_shift declines (the fractional shift then takes the general
+# pair: no one-kernel line) and launch_lines leaves its 16-byte forms for the dword one
+DIFF_CASES['translate_unaligned'] = dict(CASES['translate'], unaligned=True, matvec=_mv(None))
+DIFF_CASES['int_z60_unaligned'] = dict(CASES['int_shift_z60'], unaligned=True, matvec=_mv('k_ata_aligned<2,{}>'))
 
 _CHILD = r'''
 import json, sys
@@ -403,6 +573,7 @@ from oracle import nitorch_restated as N
 from unires_amd._project import _channel_plan
 kw, conc, light, out = %(kw)r, %(conc)r, %(light)r, sys.argv[1]
 seed, diffs, unaligned, tile, spacing = %(seed)r, %(diffs)r, %(unaligned)r, %(tile)r, %(spacing)r
+fwd_obj = %(fwd_obj)r
 if 'orient' in kw:
     kw = dict(kw, orient=[SIGNED_PERMS[kw['orient']]])
 prob = make_problem(seed=seed, **kw)
@@ -435,11 +606,12 @@ if 'forward' in diffs:
     torch.cuda.synchronize()
     res['dot'] = np.array(dot.item())
 for which in diffs:
-    if which == 'forward':
+    if which == 'forward' and not (fwd_obj and prob['do_proj']):
         continue
-    plan.set_diff(which)
+    if which != 'forward':
+        plan.set_diff(which)
     # out=: a view 1, 2, 3 floats into a sentinel-padded buffer (q 4, 8, 12 bytes off a 16-byte boundary), else None
-    for off in ((1, 2, 3) if unaligned else (0,)):
+    for off in (() if which == 'forward' else (1, 2, 3) if unaligned else (0,)):
         tag = '%%s_off%%d' %% (which, off) if unaligned else which
         dot = torch.zeros((), dtype=torch.float64, device='cuda:0')
         buf = torch.full((n + 8,), SENT, dtype=torch.float32, device='cuda:0')
@@ -450,6 +622,7 @@ for which in diffs:
         res['dot_' + tag] = np.array(dot.item())
         if unaligned:
             res['pads_' + tag] = np.array(bool((buf[:off] == SENT).all()) and bool((buf[off + n:] == SENT).all()))
+    print('[phase] solve', file=sys.stderr, flush=True)  # (what follows runs on 16-byte aligned vectors of its own)
     b = plan.rhs([xn.dat for xn in xg[0]], d(prob['w'][0]), d(prob['z'][0]), rho, lam)
     res['b_' + which] = b.cpu().numpy()
     if prob['do_proj']:
@@ -524,16 +697,80 @@ def _run_child(tmp_path, name, case, diffs=('forward',), timeout=300):
     env.update(case['env'])
     env['UNIRES_SPLAT2_VERBOSE'] = '1'
     env['UNIRES_CONV_VERBOSE'] = '1'
+    env['UNIRES_MATVEC_VERBOSE'] = '1'
     r = subprocess.run([sys.executable, '-c', _CHILD % dict(root=ROOT, kw=case['kw'], conc=case['conc'],
                                                             light=case['light'], seed=case['seed'],
                                                             diffs=tuple(diffs), unaligned=case['unaligned'],
-                                                            tile=case['tile'] or TILE, spacing=case['spacing']), path],
+                                                            tile=case['tile'] or TILE, spacing=case['spacing'],
+                                                            fwd_obj=case['matvec'] is not None), path],
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])
     res = dict(np.load(path))
     builds = re.findall(r'\[splat2\].*build (\S+), max instructions per tile (\d+)', r.stderr)
     convs = set(re.findall(r'^\[conv\] (\S+)', r.stderr, re.M))
-    return res, (builds[-1] if builds else None), convs
+    return res, (builds[-1] if builds else None), convs, matvec_lines(r.stderr)
+
+
+def matvec_lines(stderr):
+    """The [matvec] lines of a child (UNIRES_MATVEC_VERBOSE=1), in order: (name, facts) with the name as printed
+    ('k_ata_shift_m<1,1,0,1>') and the facts a dict of the integers beside it, 'src' the caller launch_lines names,
+    'solve' whether the child had reached its first right-hand side and solve (a line is printed once, where its
+    instantiation first launches: the matvecs into an unaligned ``out`` of the first difference come before)."""
+    out, solve = [], False
+    for kind, line in re.findall(r'^\[(matvec|phase)\] (.*)$', stderr, re.M):
+        if kind == 'phase':
+            solve = True
+            continue
+        tok = line.split()
+        facts, i = {'src': None, 'solve': solve}, 1
+        while i < len(tok):
+            if tok[i] in ('ata', 'dtd'):
+                facts['src'], i = tok[i], i + 1
+            else:
+                facts[tok[i]], i = int(tok[i + 1]), i + 2
+        out.append((tok[0], facts))
+    return out
+
+
+def matvec_drift(case, lines, forward=True, proj=True):
+    """The case's ``matvec`` expectation against the [matvec] lines of its child: a list of misses.  With forward
+    differences the named form must have run with the dot (DOT, OBJ = 1, 0) and, where the child solves (A != I), as
+    the fresh objective (1, 1); with a non-forward D every one-kernel launch must be the plain form (0, 0: zero
+    stencil weights, no partials - stencil_close finishes the matvec), the named one among them.  Every launch of
+    the named form must meet ``where`` and come from ``src``; no other one-kernel form may launch.  An ``unaligned``
+    case states the form of its matvecs into the unaligned ``out``: the expectation holds for the lines from before
+    the first solve, and the solves (on aligned vectors, so on the aligned forms) must still be plain."""
+    mv = case['matvec']
+    if mv is None:
+        return []
+    if case['unaligned']:
+        late = [('run in a solve', n) for n, f in lines if f['solve'] and not re.search(r'<(\d,)?0,0(,\d)?>$', n)]
+        return late + matvec_drift(dict(case, unaligned=False), [l for l in lines if not l[1]['solve']], forward, proj)
+    if mv['kernel'] is None:
+        return [('run', n) for n, _ in lines]
+    want = (['1,0', '1,1'] if proj else ['1,0']) if forward else ['0,0']
+    allowed = ['1,0', '1,1', '0,0'] if forward else ['0,0']
+    names = [n for n, _ in lines]
+    miss = [('not run', mv['kernel'].format(a)) for a in want if mv['kernel'].format(a) not in names]
+    for n, facts in lines:
+        if n not in [mv['kernel'].format(a) for a in allowed]:
+            miss.append(('run', n))
+        elif mv['where'] is not None and not mv['where'](facts):
+            miss.append(('facts', n, facts))
+        elif n.startswith('k_ata_aligned') and facts['src'] != mv['src']:
+            miss.append(('caller', n, facts['src']))
+    return miss
+
+
+def obj_check(name, key, got, x, b64, q_ref, q_tol, q_err_ties):
+    """An objective 0.5 sum_v obj_term(q_v, b_v, x_v) against float64 (``_check_diff`` derives the bound): asserts, and
+    returns err / tol."""
+    from tests import ref64
+    x64 = x.double().abs()
+    want = 0.5 * float(((q_ref - 2 * b64) * x.double()).sum())
+    tol = 0.5 * float((x64 * (q_tol + 3 * ref64.U * (q_ref.abs() + 2 * b64.abs()))).sum()) + 0.5 * q_err_ties
+    assert abs(got - want) <= tol, (name, key, got, want, tol)
+    return abs(got - want) / tol
 
 
 def conv_drift(case, convs, forward=True):
@@ -604,6 +841,18 @@ def _check(name, case, res):
     rep['matvec'] = r['max_ratio']
     # the float64 dot epilogue: <p, q> within sum |p| tol_q (+ the actual error in tied voxels)
     assert dot_ok(refq, tolq, myy), (name, 'dot')
+    if case['matvec'] is not None:
+        # the forward objectives of the one-kernel forms (``_check_diff``'s entries 0 and 1, with forward differences:
+        # entry 1 of the 'max_gain_fresh' solve is the kernel's own OBJ instantiation, the data term from registers)
+        b64 = torch.from_numpy(res['b_forward']).double()
+        ties = float((p64.abs() * (q.double() - refq).abs())[myy].sum())
+        rep['obj0'] = obj_check(name, 'obj0_forward', float(res['obj0_forward']), p, b64, refq, tolq, ties)
+        assert 'obj1_forward' in res, (name, 'the solve ran no iteration')
+        x1 = torch.from_numpy(res['x1_forward'])
+        ref1, tol1 = op.bound_matvec(x1, xc[0].tau, rho, yc.lam, vx)
+        tie1 = float((x1.double().abs() * (torch.from_numpy(res['q1_forward']).double() - ref1).abs())[myy].sum())
+        rep['obj1'] = obj_check(name, 'obj1_forward', float(res['obj1_forward']), x1, b64, ref1, tol1, tie1)
+        del ref1, tol1
     del refq, tolq
     if not case['light']:
         refAt, tolAt = op.bound_At(v)
@@ -635,7 +884,7 @@ def _check(name, case, res):
 def test_every_form_per_voxel_against_float64(tmp_path):
     drift = []
     for name, case in CASES.items():
-        res, build, convs = _run_child(tmp_path, name, case)
+        res, build, convs, mvs = _run_child(tmp_path, name, case)
         info = json.loads(str(res['info']))
         info['perm'], info['flip'] = tuple(info['perm']), tuple(info['flip'])
         form = (info['pull2'], info['splat2_axis'], info['fused'], build[0] if build else None)
@@ -647,9 +896,17 @@ def test_every_form_per_voxel_against_float64(tmp_path):
             drift.append((name, form, SWEEP_FORMS[name]))
         if conv_drift(case, convs):
             drift.append((name, conv_drift(case, convs), sorted(convs)))
+        mdrift = matvec_drift(case, mvs, proj=info['regime'] != 'identity')
+        if mdrift:
+            drift.append((name, mdrift, mvs))
         rep, excluded, R = _check(name, case, res)
         print('%-20s %s build %s conv %s max err/tol %.3f excluded %d R %.0f'
               % (name, info, build, ' '.join(sorted(convs)) or '-', max(rep.values()), excluded, R), flush=True)
+        for n, facts in mvs:
+            print('%-20s [matvec] %s %s' % (name, n, ' '.join('%s %s' % kv for kv in facts.items() if kv[1] not in (None, True, False))),
+                  flush=True)
+        if case['matvec'] is not None and 'obj0' in rep:
+            print('%-20s obj0 %.4f obj1 %.4f of their bound' % (name, rep['obj0'], rep['obj1']), flush=True)
     assert not drift, drift
 
 
@@ -758,22 +1015,13 @@ def _check_diff(name, case, res, R):
         if not proj:
             continue
         b64 = b.double()
-
-        def obj_check(key, x, q_ref, q_tol, q_err_ties):
-            x64 = x.double().abs()
-            want = 0.5 * float(((q_ref - 2 * b64) * x.double()).sum())
-            tol = 0.5 * float((x64 * (q_tol + 3 * ref64.U * (q_ref.abs() + 2 * b64.abs()))).sum()) + 0.5 * q_err_ties
-            got = float(res[key])
-            assert abs(got - want) <= tol, (name, key, got, want, tol)
-            return abs(got - want) / tol
-
         ties = float((p64.abs() * (q.double() - refq).abs())[myy].sum())
-        rep['obj0 ' + which] = obj_check('obj0_' + which, p, refq, tolq, ties)
+        rep['obj0 ' + which] = obj_check(name, 'obj0_' + which, float(res['obj0_' + which]), p, b64, refq, tolq, ties)
         assert 'obj1_' + which in res, (name, 'the solve ran no iteration', which)
         x1 = torch.from_numpy(res['x1_' + which])
         ref1, tol1 = ref64.bound_matvec_reps(ops, taus, x1, rho, lam, vx, which)
         tie1 = float((x1.double().abs() * (torch.from_numpy(res['q1_' + which]).double() - ref1).abs())[myy].sum())
-        rep['obj1 ' + which] = obj_check('obj1_' + which, x1, ref1, tol1, tie1)
+        rep['obj1 ' + which] = obj_check(name, 'obj1_' + which, float(res['obj1_' + which]), x1, b64, ref1, tol1, tie1)
     assert not torch.equal(qs['backward'], qs['central']), name
     return rep, int(myy.sum()), int(my.sum())
 
@@ -789,7 +1037,7 @@ def test_every_form_per_voxel_with_backward_and_central_differences(tmp_path, na
     assert not _DIFF_DEAD, ('an earlier case\'s child died: not started', _DIFF_DEAD)
     case = DIFF_CASES[name]
     try:
-        res, build, convs = _run_child(tmp_path, name, case, diffs=NONFWD, timeout=120)
+        res, build, convs, mvs = _run_child(tmp_path, name, case, diffs=NONFWD, timeout=120)
     except (AssertionError, subprocess.TimeoutExpired) as e:
         _DIFF_DEAD.append((name, repr(e)[:300]))
         raise
@@ -804,6 +1052,8 @@ def test_every_form_per_voxel_with_backward_and_central_differences(tmp_path, na
              n_y), flush=True)
     assert case['expect'] is None or case['expect'](info), (name, info)
     assert not conv_drift(case, convs, forward=False), (name, conv_drift(case, convs, forward=False), sorted(convs))
+    print('diff %-18s [matvec] %s' % (name, ', '.join('%s %s' % (n, f) for n, f in mvs) or '-'), flush=True)
+    assert not matvec_drift(case, mvs, forward=False), (name, matvec_drift(case, mvs, forward=False), mvs)
     assert not (case.get('one_pass') and build is not None and build[0] != 'one-pass'), (name, build)
 
 

@@ -3,7 +3,9 @@ float32 implementation of the same operator, passes it for A, At, AtA and the ma
 10x its tolerance, one 8x4x30 tile off by 1e-3 and one non-zero value outside the operator's support all fail it,
 while the relative-L2 gates of the GPU parity tests pass the first two; one x-space row at a block seam of the
 stride-2 conv kernels off by 1e-3 fails it too).  The cases of tests/test_gpu_voxelwise.py are held to their
-conditions here, on the reference alone: the tie cap, and a comb spacing wider than the footprint of their taps."""
+conditions here, on the reference alone: the tie cap, and a comb spacing wider than the footprint of their taps; and
+where a one-kernel case is there for the right apron of its z lines, the last x-space slice's share of A^T A p, taken
+out of the float32 oracle's result, fails the bound."""
 import pytest
 import torch
 
@@ -11,7 +13,8 @@ from oracle import nitorch_restated as N
 from oracle import unires_restated as O
 from tests import ref64
 from tests.helpers import make_problem, oracle_structs, rel_err
-from tests.test_gpu_voxelwise import DIFF_CASES, SEAM_CASES, diff_reference, inputs, spacings, tie_cap_ok
+from tests.test_gpu_voxelwise import (DIFF_CASES, ONE_KERNEL_CASES, SEAM_CASES, diff_reference, inputs, spacings,
+                                      tie_cap_ok)
 
 PROBLEMS = {
     'small_thick3': dict(dim_y=(16, 14, 12), thick=3, rot=0.1, trans=0.7),
@@ -321,3 +324,52 @@ def test_tie_cap_and_comb_spacing_of_the_seam_cases(name):
     kept = [int(k.sum()) for k in ref64.trimmed_taps(po.smo_ker_1d)]
     sy, _ = spacings(case['kw'], case['spacing'])
     assert all(s >= 2 * (n - 1 + 2) + 1 for s, n in zip(sy, kept)), (name, sy, kept)
+
+
+_OK_PROJ = [n for n, c in ONE_KERNEL_CASES.items() if c['kw'].get('regime', 'sr') != 'id']
+
+
+def _one_kernel_setup(name):
+    case = ONE_KERNEL_CASES[name]
+    prob = make_problem(seed=case['seed'], **case['kw'])
+    xs, _ = oracle_structs(prob)
+    po = xs[0][0].po
+    return case, prob, po, ref64.Operator64(po, prob['method'])
+
+
+@pytest.mark.parametrize('name', _OK_PROJ)
+def test_tie_cap_and_comb_spacing_of_the_one_kernel_cases(name):
+    """Conditions on ONE_KERNEL_CASES of tests/test_gpu_voxelwise.py (A != I), met by the reference alone, as for the
+    seam cases: fewer than 1 % of the voxels excluded as FOV ties in x space (A) and in y space (A^T, A^T A), and a
+    y-space comb spacing of at least the footprint of A^T A, 2 (taps - 1 + 2) + 1 for the taps the plan keeps."""
+    case, prob, po, op = _one_kernel_setup(name)
+    mx, my, myy, _ = op.tie_masks(po)
+    print('ties %s: %d (A) %d (At) %d (AtA)' % (name, int(mx.sum()), int(my.sum()), int(myy.sum())))
+    assert int(mx.sum()) < 0.01 * mx.numel() and int(my.sum()) < 0.01 * my.numel() and int(myy.sum()) < 0.01 * myy.numel()
+    kept = [int(k.sum()) for k in ref64.trimmed_taps(po.smo_ker_1d)]
+    sy, _ = spacings(case['kw'], case['spacing'])
+    assert all(s >= 2 * (n - 1 + 2) + 1 for s, n in zip(sy, kept)), (name, sy, kept)
+
+
+@pytest.mark.parametrize('name, last', [('tr_zpos', 8), ('int_zpos', 9)])
+def test_comparator_catches_a_lost_last_slice_at_the_right_apron(name, last):
+    """tr_zpos / int_zpos translate the observation up along z, so that the taps of its last x-space slices reach past
+    the end of the z line: what the one-kernel forms read from their right apron (padr > 0).  The float32 oracle's
+    A^T A p passes the per-voxel bound; the same product without the last live x-space slice - what a kernel forms
+    whose apron is a slice short - fails it, in most of the z lines.  ``last``: that slice.  int_zpos: slice 9 of 10,
+    whose grid points lie at z 59 .. 65 of 61, two of them inside.  tr_zpos: slice 9 (z 59.6 .. 65.6 of 60) lies wholly
+    outside the FOV and the oracle returns exact zeros for it, so taking it out changes nothing; the last live slice is
+    8 (z 53.6 .. 59.6), whose window of the blended line ends at z = 60, one past the line."""
+    case, prob, po, op = _one_kernel_setup(name)
+    _, _, myy, _ = op.tie_masks(po)
+    p = inputs(prob['dim_y'], po.dim_x)[0]
+    ref, tol = op.bound_AtA(p)
+    m = prob['method']
+    assert ref64.compare(_oracle32('AtA', p, po, m), ref, tol, myy)['ok']
+    mid = _oracle32('A', p, po, m)
+    live = [k for k in range(mid.shape[2]) if float(mid[:, :, k].abs().max()) > 0.0]
+    assert live[-1] == last, (name, live)
+    mid[:, :, last] = 0.0
+    r = ref64.compare(_oracle32('At', mid, po, m), ref, tol, myy)
+    print('apron plant %s: slice %d, n_bad %d max err/tol %.3g' % (name, last, r['n_bad'], r['max_ratio']))
+    assert not r['ok'] and r['n_bad'] >= prob['dim_y'][0] * prob['dim_y'][1] // 2, (name, r)

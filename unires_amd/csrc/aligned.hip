@@ -18,9 +18,13 @@
 // goes through readfirstlane; loads and stores are scalar base + lane offset), everything that
 // depends on the lane but not on the line is hoisted out of the line loop, and the LDS line
 // carries a zero apron so that no tap needs a bounds check.
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <mutex>
+#include <set>
+#include <string>
 #include <type_traits>
 
 #include "aligned.hpp"
@@ -234,6 +238,12 @@ __device__ __forceinline__ float a4_lower(float v) {  // lane l gets lane l - 1'
 __device__ __forceinline__ float a4_upper(float v) {  // lane l gets lane l + 1's value (lane 63: 0)
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
+// one lane's value, bit for bit (the builtin is declared on int: handed a float it returns the value TRUNCATED to an
+// integer - the z neighbours across the seam of k_ata_aligned4<2>'s two passes, z = 255 | 256, were that until the
+// per-voxel table reached the form)
+__device__ __forceinline__ float a4_readlane(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
 
 #ifndef UNIRES_ALIGNED4_WAVES
 #define UNIRES_ALIGNED4_WAVES 6
@@ -341,13 +351,13 @@ __global__ void __launch_bounds__(kBlock, NP4 == 1 ? UNIRES_ALIGNED4_WAVES : 4)
         // across passes through readlane; the line's first voxel has no backward term (zlo := c)
         float zlo = a4_lower(rc[u].w), zhi = a4_upper(rc[u].x);
         if (u > 0) {
-          const float prev = __builtin_amdgcn_readlane(rc[u > 0 ? u - 1 : 0].w, kWave - 1);
+          const float prev = a4_readlane(rc[u > 0 ? u - 1 : 0].w, kWave - 1);
           zlo = lane == 0 ? prev : zlo;
         } else {
           zlo = lane == 0 ? rc[0].x : zlo;
         }
         if (u + 1 < NP4) {
-          const float next = __builtin_amdgcn_readlane(rc[u + 1 < NP4 ? u + 1 : 0].x, 0);
+          const float next = a4_readlane(rc[u + 1 < NP4 ? u + 1 : 0].x, 0);
           zhi = lane == kWave - 1 ? next : zhi;
         }
         const float c4[4] = {rc[u].x, rc[u].y, rc[u].z, rc[u].w};
@@ -577,12 +587,32 @@ bool affine_is_integer_shift(const Affine &A, int off[3]) {
   return true;
 }
 
-// Launches the line kernel for filled-in arguments (npt = 2, 4, 6 or 8 z-passes per line).
-static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, hipStream_t st) {
+// The line UNIRES_MATVEC_VERBOSE=1 prints (aligned.hpp), once per distinct line: an instantiation is reported again
+// where its grid or the facts beside it differ.
+void matvec_note(const char *fmt, ...) {
+  static std::mutex mu;
+  static std::set<std::string> seen;
+  char line[192];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(line, sizeof(line), fmt, ap);
+  va_end(ap);
+  std::lock_guard<std::mutex> lock(mu);
+  if (!seen.insert(line).second) return;
+  fprintf(stderr, "[matvec] %s\n", line);
+}
+
+// Launches the line kernel for filled-in arguments (npt = 2, 4, 6 or 8 z-passes per line).  `from`: the caller, as
+// the launch note names it ("ata": launch_ata_aligned, "dtd": launch_dtd_lines).
+static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, hipStream_t st, const char *from) {
   const Dim3i dd = G.dd;
   const double *partials = G.partials;
   const float *objb = G.objb;
   const dim3 grid(aligned_blocks(dd)), block(kWave, kLinesPerBlock);
+  const int dot = partials ? 1 : 0, obj = objb ? 1 : 0;  // (the DOT, OBJ template arguments of what is launched)
+#define ALIGNED_NOTE(A, name, ...)                                                                                  \
+  MATVEC_NOTE(name " grid %u %s padl %d padr %d nk %d s %d", __VA_ARGS__, grid.x, from, (A).padl, (A).padr, (A).nk, \
+              (A).s)
   // 16-byte form: lines that are whole vectors (nz % 4 == 0, 16-byte aligned volumes), <= 512 long
   static const bool no_v4 = getenv("UNIRES_ALIGNED_V4") && getenv("UNIRES_ALIGNED_V4")[0] == '0';
   const uintptr_t al = (uintptr_t)G.p | (uintptr_t)G.q | (uintptr_t)(objb ? objb : G.p);
@@ -596,6 +626,7 @@ static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, h
     static const bool no_x2 = getenv("UNIRES_ALIGNED_X2") && getenv("UNIRES_ALIGNED_X2")[0] == '0';
     const size_t lds42 = ((size_t)4 * 4 * kWave + kAlignedMaxTaps + (size_t)2 * kLinesPerBlock * V.wave_floats) * sizeof(float);
     if (!no_x2 && np4 == 1 && dd.y % 2 == 0 && lds42 <= 64 * 1024) {
+      ALIGNED_NOTE(V, "k_ata_aligned4x2<%d,%d>", dot, obj);
       if (objb)
         hipLaunchKernelGGL((k_ata_aligned4x2<true, true>), grid, block, lds42, st, V, done);
       else if (partials)
@@ -614,6 +645,7 @@ static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, h
     else                                                                                        \
       hipLaunchKernelGGL((k_ata_aligned4<NPV, false, false>), grid, block, lds4, st, V, done);  \
   } while (0)
+      ALIGNED_NOTE(V, "k_ata_aligned4<%d,%d,%d>", np4, dot, obj);
       if (np4 == 1)
         LAUNCH_ALIGNED4(1);
       else
@@ -631,6 +663,7 @@ static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, h
     else                                                                                     \
       hipLaunchKernelGGL((k_ata_aligned<NPV, false, false>), grid, block, lds, st, G, done); \
   } while (0)
+  ALIGNED_NOTE(G, "k_ata_aligned<%d,%d,%d>", npt, dot, obj);
   if (npt == 2)
     LAUNCH_ALIGNED(2);
   else if (npt == 4)
@@ -640,6 +673,7 @@ static void launch_lines(AlignedArgs &G, int npt, size_t lds, const int *done, h
   else
     LAUNCH_ALIGNED(8);
 #undef LAUNCH_ALIGNED
+#undef ALIGNED_NOTE
 }
 
 // Regime A = I: q = a0 p + c DtD p (+ dot / objective) with the same line kernel (no AtA term).
@@ -662,7 +696,7 @@ int launch_dtd_lines(const float *p, float *q, Dim3i dd, float a0, float cx, flo
   G.prof = nullptr;
   const size_t lds =
       ((size_t)4 * npt * kWave + kAlignedMaxTaps + (size_t)kLinesPerBlock * G.wave_floats) * sizeof(float);
-  launch_lines(G, npt, lds, done, st);
+  launch_lines(G, npt, lds, done, st, "dtd");
   return 0;
 }
 
@@ -709,7 +743,7 @@ int launch_ata_aligned(const float *p, float *q, Dim3i dd, Dim3i gd, Dim3i xd, c
   (void)hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), st);
   G.prof = prof;
 #endif
-  launch_lines(G, npt, lds, done, st);
+  launch_lines(G, npt, lds, done, st, "ata");
 #ifdef UNIRES_ALIGNED_PROF
   {
     unsigned long long h[8];

@@ -1,8 +1,24 @@
 // aligned.hpp - one-kernel CG matvec for grid-aligned observations (aligned.hip).
 #pragma once
+#include <stdlib.h>
+
 #include "common.hpp"
 
 namespace unires {
+
+// UNIRES_MATVEC_VERBOSE=1: one line on stderr the first time each instantiation of a one-kernel matvec form
+// (aligned.hip, shift.hip) is launched in the process - its name with the template arguments, the grid, and the
+// run-time facts that select code inside the kernel (which form ran is decided by shape alone and is not visible in
+// the plan).  Host code only.  Unset: one branch per launch, nothing else.
+inline bool matvec_verbose() {
+  static const bool v = getenv("UNIRES_MATVEC_VERBOSE") && atoi(getenv("UNIRES_MATVEC_VERBOSE")) != 0;
+  return v;
+}
+__attribute__((format(printf, 1, 2))) void matvec_note(const char *fmt, ...);  // (the line without its "[matvec] ")
+#define MATVEC_NOTE(...)                              \
+  do {                                                \
+    if (matvec_verbose()) matvec_note(__VA_ARGS__);   \
+  } while (0)
 
 bool affine_is_integer_shift(const Affine &A, int off[3]);
 int aligned_blocks(Dim3i dd);

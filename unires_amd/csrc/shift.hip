@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "aligned.hpp"  // (MATVEC_NOTE)
 #include "shift.hpp"
 
 namespace unires {
@@ -855,6 +856,11 @@ int launch_ata_shift(const ShiftPlan &S, const float *p, float *q, Dim3i dd, con
   (void)hipMemsetAsync(prof_dev, 0, (size_t)4096 * kShiftLines * 8 * sizeof(unsigned long long), st);
   G.prof = prof_dev;
 #endif
+  // UNIRES_MATVEC_VERBOSE=1 (aligned.hpp): the instantiation launched and what selects code inside it
+  const int dot = partials ? 1 : 0, obj = objb ? 1 : 0;  // (the DOT, OBJ template arguments of what is launched)
+#define SHIFT_NOTE(name, ...)                                                                                     \
+  MATVEC_NOTE(name " grid %u xr %d lw %d padl %d padr %d nf %d", __VA_ARGS__, grid.x, G.xr, G.lw, G.padl, G.padr, \
+              G.nf)
   static const size_t pad_lds = getenv("UNIRES_SHIFT_PADLDS") ? (size_t)atoi(getenv("UNIRES_SHIFT_PADLDS")) : 0;  // (measurement: fewer workgroups per CU)
   if (G.xr > 0 && lds_m <= 64 * 1024) {
 #define SHIFT_M_LAUNCH(NLV, FASTV)                                                                             \
@@ -867,6 +873,7 @@ int launch_ata_shift(const ShiftPlan &S, const float *p, float *q, Dim3i dd, con
       hipLaunchKernelGGL((k_ata_shift_m<NLV, false, false, FASTV>), grid, block, lds_m + pad_lds, st, G, done); \
   } while (0)
     const bool fast = shift_fast(S, dd) && G.lw && G.dbg == 0 && G.defer == 0;
+    SHIFT_NOTE("k_ata_shift_m<%d,%d,%d,%d>", nl, dot, obj, fast ? 1 : 0);
     if (nl == 2 && fast)
       SHIFT_M_LAUNCH(2, true);
     else if (nl == 2)
@@ -900,6 +907,7 @@ int launch_ata_shift(const ShiftPlan &S, const float *p, float *q, Dim3i dd, con
     return 0;
   }
   if (!no_x2 && dd.y % 2 == 0 && lds2 <= 64 * 1024) {
+    SHIFT_NOTE("k_ata_shift2<%d,%d>", dot, obj);
     if (objb)
       hipLaunchKernelGGL((k_ata_shift2<true, true>), grid, block, lds2, st, G, done);
     else if (partials)
@@ -908,6 +916,8 @@ int launch_ata_shift(const ShiftPlan &S, const float *p, float *q, Dim3i dd, con
       hipLaunchKernelGGL((k_ata_shift2<false, false>), grid, block, lds2, st, G, done);
     return 0;
   }
+  SHIFT_NOTE("k_ata_shift<%d,%d>", dot, obj);
+#undef SHIFT_NOTE
   if (objb)
     hipLaunchKernelGGL((k_ata_shift<true, true>), grid, block, lds, st, G, done);
   else if (partials)
