@@ -292,6 +292,22 @@ int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const float *x, void
  * the canonical axis behind `axis` and its direction follow the new orientation).  Errors: a bad n or axis
  * UNIRES_ERR_ARG; UNIRES_REGIME_IDENTITY UNIRES_ERR_UNSUPPORTED, as for the mask. */
 int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int32_t axis, const float *u_dev, void *stream);
+/* Per-voxel weights of repeat n's data term (no counterpart in the reference): g_dev = dim_x float32 ON THE DEVICE, one
+ * per x-space voxel in the caller's layout (the observation's).  The data term becomes
+ * 1/2 tau_n sum_v g(v) u[s(v)] m(v) (x - A y)^2(v) and the plan applies A_n^T diag(g . u . m) A_n wherever it applied
+ * A_n^T diag(u . m) A_n (u: the weights of unires_plan_set_slice_weights, m: the mask of unires_plan_set_missing, or 1;
+ * all three in one pass): the matvec of unires_ata_matvec and of the CG solves, the Jacobi diagonal, the mean diagonal
+ * of the FFT preconditioner's symbol.  unires_rhs_assemble and unires_atx_assemble accumulate tau_n A_n^T (g . u . x_n),
+ * made in the plan's scratch (the observation is not written).  unires_proj_apply keeps the unweighted A, A^T and
+ * A^T A.  The values are not checked: g >= 0 is the caller's contract and keeps the system symmetric positive definite.
+ * The plan copies the weights into a buffer it owns - and, where it relabels the observation, into a second one in its
+ * canonical layout - whose addresses do not change while the repeat is weighted; copy and permute are enqueued on
+ * `stream` and not waited for.  A first set or a clear (g_dev == NULL) rebuilds the repeat's tables where its kernel
+ * family changes, waits for the plan's earlier launches and drops the captured CG graphs.  New VALUES rebuild nothing
+ * and wait for nothing: a captured solve is kept and reads the new values when it is replayed.  Every set drops the
+ * built preconditioner.  unires_plan_set_repeat keeps the weights (the new descriptor must have the same dim_x) and
+ * re-permutes them.  Errors: a bad n UNIRES_ERR_ARG; UNIRES_REGIME_IDENTITY UNIRES_ERR_UNSUPPORTED, as for the mask. */
+int unires_plan_set_voxel_weights(unires_plan_t *plan, int32_t n, const float *g_dev, void *stream);
 /* Bytes of device workspace the plan owns. */
 int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
 /* Which kernels repeat n's operator runs on (no counterpart in the reference, whose _proj_apply
@@ -301,7 +317,7 @@ int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
  * j is reversed, info[4] = 1 if the LDS-window pull serves it, info[5] = 0 if the schedule-driven
  * splat does not serve it, else 2 + its conv_up axis (1: grid-space source, 2..4: along x / y / z, 5: all), info[6] bit 0 = the translation-only one-kernel
  * matvec serves it, bit 1 = the single-pass AtA kernel of the denoising regime does (ata1.hip), bit 2 = the repeat is masked (unires_plan_set_missing:
- * bits 0 and 1 are then clear), bit 3 = the repeat is weighted (unires_plan_set_slice_weights: bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
+ * bits 0 and 1 are then clear), bit 3 = the repeat is weighted (unires_plan_set_slice_weights: bits 0 and 1 are then clear), bit 4 = the repeat is voxel-weighted (unires_plan_set_voxel_weights: bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
 int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int32_t info[8]);
 /* The relabelling a plan applies to an operator with grid -> output affine M (host arithmetic only, no device
  * call): perm[j] = caller's voxel axis behind canonical axis j, flip[j] = 1 where it is reversed, chosen so that
@@ -459,6 +475,31 @@ int unires_masked_sse(const float *x, const float *ay, int64_t n, double *out_de
  * entries is written.  out_dev: 2 S doubles on the device. */
 int unires_slice_sums(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick, double *out_dev,
                       void *stream);
+
+/* The slice sums weighted per voxel (no counterpart in the reference): g an x-space volume `dim` of weights >= 0.
+ *   out_dev[s]     = sum_{v in slice s, x != 0} g(v) (x - ay)^2     terms fl(g fl(r r)), r = fl(x - ay), float32
+ *   out_dev[S + s] = sum_{v in slice s, x != 0} g(v)                the slice's effective count
+ * float64 sums in unires_slice_sums' fixed order (no atomics: the same bits every run; with g = 1 its bits).  The one
+ * statement of a voxel-weighted repeat's data term: 1/2 tau sum_s u_s out_dev[s].  out_dev: 2 S doubles on the device. */
+int unires_voxel_sums(const float *x, const float *ay, const float *g, const int32_t dim[3], int32_t dim_thick,
+                      double *out_dev, void *stream);
+
+/* The pass a voxel-weighted repeat runs between the forward half of A^T A and its push, on its own (no counterpart in
+ * the reference): over a z-fastest volume `dim`
+ *   dst[v] = g[v] src[v]                      (u == NULL; one float32 product)
+ *   dst[v] = fl32(fl64(g[v] u[s(v)]) src[v])  (u: one weight per slice along `axis`, counted from the far end where
+ *                                              flip != 0; g u is exact in float64, one rounding to float32 at the end)
+ * and +0 where mask[v] == 0 (mask: one byte per voxel, or NULL).  dst == src: in place; dst != src: src is only read.
+ * done: a device word, or NULL - the pass returns at entry where *done != 0, as inside a CG solve.  All device
+ * pointers; buffers off a 16-byte boundary (mask: 4-byte) are served voxel by voxel. */
+int unires_voxel_apply(const float *src, float *dst, const float *g, const uint8_t *mask, const float *u,
+                       const int32_t dim[3], int32_t axis, int32_t flip, const int32_t *done, void *stream);
+
+/* The Huber weights of a residual (no counterpart in the reference): over n voxels
+ *   g_out[v] = prior[v] h(v)   (prior == NULL: h(v)),   h = 1 where x == 0 or |r| <= c, else fl(c / |r|),  r = fl(x - ay)
+ * in float32, c > 0.  One streaming pass; g_out may be prior. */
+int unires_voxel_huber(const float *x, const float *ay, const float *prior, float c, int64_t n, float *g_out,
+                       void *stream);
 
 /* Gradient and Hessian sums of one rigid Gauss-Newton step (_update_rigid_channel,
  * _update.py:622-650) in one pass over the grid: gr3 (dim,3) = grid_grad of the pulled image,

@@ -241,6 +241,41 @@ def _read_data(data, sett):
     return x
 
 
+def _read_weights(x, sett):
+    """``sett.weight`` -> ``x[c][n].weight``: per-voxel weight maps of the data term, a nested list shaped like the
+    data (channels, then repeats; a channel of one repeat may give its entry without the inner list), each entry the
+    path of a NIfTI (read through ``nifti.map_file``; non-finite values become 0, the way a mask written with NaN
+    outside means it), a tensor / array, or None.  A map has its observation's shape - ValueError otherwise; whether
+    its values are >= 0 is ``fit()``'s check.  ``sett.force_inplane_res`` resamples the observation and would leave
+    the map behind: the combination is refused by name."""
+    weight = getattr(sett, 'weight', None)
+    if weight is None:
+        return x
+    if sett.force_inplane_res:
+        raise NotImplementedError('sett.weight with sett.force_inplane_res: the observation is resampled in plane, '
+                                  'resampling its weight map is not built')
+    if isinstance(weight, str) or hasattr(weight, 'shape') or len(weight) != len(x):
+        raise ValueError('sett.weight must be a list with one entry per channel (%d)' % len(x))
+    for c, wc in enumerate(weight):
+        if wc is None:
+            continue
+        if isinstance(wc, str) or hasattr(wc, 'shape'):
+            wc = [wc]
+        if len(wc) != len(x[c]):
+            raise ValueError('sett.weight[%d] must have one entry per repeat (%d)' % (c, len(x[c])))
+        for n, src in enumerate(wc):
+            if src is None:
+                continue
+            g = nifti.map_file(src).fdata() if isinstance(src, str) else torch.as_tensor(src)
+            if tuple(g.shape) != tuple(x[c][n].dat.shape):
+                raise ValueError('sett.weight[%d][%d] has shape %s, its observation %s'
+                                 % (c, n, tuple(g.shape), tuple(x[c][n].dat.shape)))
+            if isinstance(src, str):
+                g = torch.nan_to_num(g.float(), nan=0.0, posinf=0.0, neginf=0.0)
+            x[c][n].weight = g.to(x[c][n].dat.device)
+    return x
+
+
 def _fix_affine(x, sett):
     """The reference resets the origin of CT observations here (unires/_core.py:145-168, nitorch's
     ``reset_origin``); that is not built, so the combination is refused."""

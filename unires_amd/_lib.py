@@ -76,6 +76,7 @@ SIGNATURES = {
     'unires_plan_set_diff': (C.c_int, [C.c_void_p, C.c_int32]),
     'unires_plan_set_missing': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_plan_set_slice_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_plan_set_voxel_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_plan_workspace_bytes': (C.c_int64, [C.c_void_p]),
     'unires_orient_of': (C.c_int, [c_f32x12, c_i32x3, c_i32x3]),
     'unires_plan_repeat_info': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32 * 8]),
@@ -123,6 +124,10 @@ SIGNATURES = {
     'unires_clean_fov': (C.c_int, [C.c_void_p, c_i32x3, c_f32x12, c_i32x3, C.c_void_p]),
     'unires_masked_sse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'unires_slice_sums': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_voxel_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_voxel_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
+    'unires_voxel_huber':(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),
     'unires_mark_create': (C.c_int, [C.POINTER(C.c_void_p)]),
     'unires_mark_destroy': (C.c_int, [C.c_void_p]),
     'unires_mark_signal': (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -81,6 +81,7 @@ class ChannelPlan:
         self.mask_zeros = False  # the setting the plan was last fetched with (_project._channel_plan)
         self._slice_w = [None] * len(repeats)  # per repeat: (weak reference, version, axis) of the weight tensor the plan holds, or None
         self.weights = False  # whether the plan was last fetched with the observations' slice weights (_channel_plan)
+        self._voxel_w = [None] * len(repeats)  # per repeat: (weak reference, version) of the voxel-weight tensor the plan holds, or None
         check(self.lib.unires_plan_create(C.byref(self._h), i3(self.dim_y), f3(vx_y), self.regime,
                                           len(repeats), arr, fov_tol))
         self.dims_x = [self.dim_y if self.regime == REGIME_IDENTITY else tuple(po.dim_x)
@@ -111,16 +112,19 @@ class ChannelPlan:
 
     def repeat_info(self, n):
         """Which kernels repeat n runs on and how its voxel axes were relabelled
-        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused, masked, weighted);
+        (``unires_plan_repeat_info``): dict(perm, flip, pull2, splat2_axis, shift, separable, fused, masked, weighted,
+        voxel_weighted);
         ``fused``: the single-pass AtA kernel (denoising regime, ata1.hip) serves the CG matvec; ``masked``: the
         repeat has a validity mask (:meth:`set_missing`), ``weighted``: per-slice weights
-        (:meth:`set_slice_weights`) - ``shift`` and ``fused`` are then False."""
+        (:meth:`set_slice_weights`), ``voxel_weighted``: per-voxel weights (:meth:`set_voxel_weights`) - ``shift`` and
+        ``fused`` are then False."""
         info = (C.c_int32 * 8)()
         check(self.lib.unires_plan_repeat_info(self._h, int(n), info))
         v = list(info)
         return dict(perm=tuple(v[:3]), flip=tuple((v[3] >> j) & 1 for j in range(3)), pull2=bool(v[4]),
                     splat2_axis=None if v[5] == 0 else v[5] - 2, shift=bool(v[6] & 1), separable=bool(v[7]),
-                    fused=bool(v[6] & 2), masked=bool(v[6] & 4), weighted=bool(v[6] & 8))
+                    fused=bool(v[6] & 2), masked=bool(v[6] & 4), weighted=bool(v[6] & 8),
+                    voxel_weighted=bool(v[6] & 16))
 
     @on_device
     def time_matvecs(self, on=True):
@@ -234,8 +238,51 @@ class ChannelPlan:
             self.set_slice_weights(n, axis, t)
 
     def _slice_key(self):
-        """The weights' part of :meth:`rhs_cached`'s key: (object, version) per repeat."""
-        return tuple(None if k is None else (id(k[0]()), k[1]) for k in self._slice_w)
+        """The weights' part of :meth:`rhs_cached`'s key: (object, version) per repeat, slice weights then voxel
+        weights."""
+        return (tuple(None if k is None else (id(k[0]()), k[1]) for k in self._slice_w),
+                tuple(None if k is None else (id(k[0]()), k[1]) for k in self._voxel_w))
+
+    @on_device
+    def set_voxel_weights(self, n, g):
+        """Per-voxel weights of repeat n's data term (``unires_plan_set_voxel_weights``): ``g`` a float32 device tensor
+        of the observation's shape with weights >= 0 (not checked here: ``fit`` validates the user's once).  The
+        plan's AtA_n becomes A_n^T diag(g) A_n - on top of a mask and slice weights, where the repeat has them, in
+        one pass - in the matvec, the CG solves and the preconditioners, and its right-hand side term A_n^T (g . x_n);
+        A and At of :meth:`proj_apply` stay unweighted.  ``g=None`` clears.  The plan keeps a copy: call again when
+        the values change (that rebuilds nothing, a captured solve reads the new values; a first set or a clear
+        changes the repeat's kernels)."""
+        import weakref
+        n = int(n)
+        if not 0 <= n < self.n_repeats:
+            raise ValueError('unires_amd: repeat index out of range')
+        if g is not None and (not g.is_cuda or g.dtype != torch.float32
+                              or tuple(g.shape) != tuple(int(d) for d in self.dims_x[n])):
+            raise ValueError('unires_amd: voxel weights must be a float32 device tensor of shape %s'
+                             % (tuple(int(d) for d in self.dims_x[n]),))
+        self._voxel_w[n] = None
+        self._atx = None  # (sum tau At (g . x) follows the weights)
+        if g is None:
+            check(self.lib.unires_plan_set_voxel_weights(self._h, n, None, _stream()))
+            return
+        gc = g.contiguous()
+        check(self.lib.unires_plan_set_voxel_weights(self._h, n, _ptr(gc), _stream()))
+        self._voxel_w[n] = (weakref.ref(g), g._version)
+
+    def sync_voxel_weights(self, gs):
+        """:meth:`set_voxel_weights` for every repeat whose weights are not the tensor, at the version, the plan holds
+        (``gs``: per repeat a tensor or None for a repeat without voxel weights; ``gs=None``: clear all).  Free when
+        nothing changed.  Runs on the current stream, like :meth:`sync_slice_weights`."""
+        for n in range(self.n_repeats):
+            t = None if gs is None else gs[n]
+            key = self._voxel_w[n]
+            if t is None:
+                if key is not None:
+                    self.set_voxel_weights(n, None)
+                continue
+            if key is not None and key[0]() is t and key[1] == t._version:
+                continue
+            self.set_voxel_weights(n, t)
 
     def set_concurrency(self, n):
         """Tell the plan that ``n`` solves run on the device at once (the channels of a y-update on streams of their

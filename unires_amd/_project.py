@@ -209,6 +209,13 @@ def _slice_weights(x):
     return ws if any(w is not None for w in ws) else None
 
 
+def _voxel_weights(x):
+    """Per repeat the voxel weights ``xn.weight`` or None, as ``ChannelPlan.sync_voxel_weights`` takes them; None when
+    no repeat of the channel has some."""
+    gs = [getattr(xn, 'weight', None) for xn in x]
+    return gs if any(g is not None for g in gs) else None
+
+
 def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weights=None):
     """Fused per-channel plan, cached on the output struct and rebuilt when any
     operator parameter (rigid, scl, tau, dims) changed.  ``diff``: the difference of the plan's D
@@ -218,19 +225,22 @@ def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weigh
     as it is (callers that apply A or A^T only, which no mask changes).
     ``weights``: True - the plan's A^T A and right-hand side carry the per-slice weights ``xn.slice_w`` of the repeats
     that have some (``ChannelPlan.set_slice_weights``; they follow the weight tensors and their versions); False -
-    the unweighted operator; None leaves the plan as it is."""
+    the unweighted operator; None leaves the plan as it is.  The per-voxel weights ``xn.weight``
+    (``ChannelPlan.set_voxel_weights``) go with them."""
     cached = getattr(y, '_plan', None)
     if mask_zeros is None:
         mask_zeros = cached[1].mask_zeros if cached is not None else False
     if weights is None:
         weights = cached[1].weights if cached is not None else False
     ws = _slice_weights(x) if weights else None
-    # (regime A = I has no x-space intermediate for either pass: the denoising regime with the identity affine)
-    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros) or ws is not None)
+    gs = _voxel_weights(x) if weights else None
+    # (regime A = I has no x-space intermediate for any of the passes: the denoising regime with the identity affine)
+    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros) or ws is not None or gs is not None)
     if diff is not None:
         plan.set_diff(diff)
     plan.sync_missing([xn.dat for xn in x] if mask_zeros else None)
     plan.sync_slice_weights(ws)
+    plan.sync_voxel_weights(gs)
     plan.mask_zeros, plan.weights = bool(mask_zeros), bool(weights)
     return plan
 

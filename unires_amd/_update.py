@@ -208,25 +208,71 @@ def _update_zw(y, z, w, rho, tmp, sett):
     return z, w, tmp
 
 
+def _voxel_robust(sett):
+    """sett.voxel_robust (False where the settings object has none): per-voxel weights of every observation are
+    re-estimated from its residuals after each ADMM iteration (``_update_voxel_weights``)."""
+    return bool(getattr(sett, 'voxel_robust', False))
+
+
 @on_device
-def _slice_sums(x, y, sett):
-    """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice weights: SSE_s = sum_{v in s, x != 0}
-    (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick`` (``unires_slice_sums``; float32 terms,
-    float64 sums in a fixed order).  A y is computed once per repeat; the result serves the objective
-    (``_compute_nll``) and the rule (``_update_slice_weights``).  Nothing is read back."""
+def _slice_sums(x, y, sett, ays=None):
+    """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights: SSE_s = sum_{v in s,
+    x != 0} (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick`` (``unires_slice_sums``; float32
+    terms, float64 sums in a fixed order); for a repeat with voxel weights ``xn.weight`` both sums carry g(v)
+    (``unires_voxel_sums``: sum g (x - A y)^2 and the effective count sum g).  A y is computed once per repeat; the
+    result serves the objective (``_compute_nll``) and the rules (``_update_slice_weights``; ``_update_voxel_weights``
+    takes the A y itself from ``ays``, a dict filled here with (c, n): A y of the voxel-weighted repeats).  Nothing is
+    read back."""
     lib = _lib.load()
     out = {}
     for c in range(len(x)):
         for n, xn in enumerate(x[c]):
-            if getattr(xn, 'slice_w', None) is None:
+            g = getattr(xn, 'weight', None)
+            if getattr(xn, 'slice_w', None) is None and g is None:
                 continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = xn.dat.contiguous()
             a = _slice_axis(xn)
             sums = torch.empty(2 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
-            check(lib.unires_slice_sums(_ptr(xd), _ptr(Ay), i3(xd.shape), a, _ptr(sums), _stream()))
+            if g is None:
+                check(lib.unires_slice_sums(_ptr(xd), _ptr(Ay), i3(xd.shape), a, _ptr(sums), _stream()))
+            else:
+                check(lib.unires_voxel_sums(_ptr(xd), _ptr(Ay), _ptr(g.contiguous()), i3(xd.shape), a, _ptr(sums),
+                                            _stream()))
+                if ays is not None:
+                    ays[(c, n)] = Ay
             out[(c, n)] = sums
     return out
+
+
+@on_device
+def _update_voxel_weights(x, y, sett, ays=None):
+    """Re-estimates the voxel weights of every observation that has some by the Huber rule: ``xn.weight`` <- prior . h,
+    h = 1 where x == 0 or |x - A y| <= c, else c / |x - A y|, with c = sett.voxel_k / sqrt(tau) - voxel_k noise
+    standard deviations (``unires_voxel_huber``; ``ays``: what ``_slice_sums`` kept of A y for this y, computed here
+    where missing).  ``prior`` is the private clone ``fit()`` keeps of a user's ``_input.weight`` (None: ones), so a
+    weight of 0 stays 0.  The weight tensors are written in place and their version counters bumped: they tell the
+    plans (``sync_voxel_weights``, at the next y-update's plan fetch) and the cached sum tau At (g . x).  One
+    streaming pass per repeat, no read-back."""
+    lib = _lib.load()
+    k = float(getattr(sett, 'voxel_k', 3.0))
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            g = getattr(xn, 'weight', None)
+            if g is None:
+                continue
+            if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+                raise ValueError('unires_amd: x[%d][%d].weight must be a contiguous float32 device tensor, as fit() '
+                                 'leaves it' % (c, n))
+            Ay = None if ays is None else ays.get((c, n))
+            if Ay is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            xd = xn.dat.contiguous()
+            prior = getattr(xn, '_weight_prior', None)
+            check(lib.unires_voxel_huber(_ptr(xd), _ptr(Ay), None if prior is None else _ptr(prior),
+                                         k / float(xn.tau) ** 0.5, xd.numel(), _ptr(g), _stream()))
+            torch.autograd.graph.increment_version(g)
+    return x
 
 
 def slice_rule(sums, k):
@@ -259,6 +305,8 @@ def _update_slice_weights(x, y, sett, sums=None):
     sums = _slice_sums(x, y, sett) if sums is None else sums
     k = float(getattr(sett, 'slice_k', 3.0))
     for (c, n), s in sums.items():
+        if getattr(x[c][n], 'slice_w', None) is None:  # (voxel weights alone: nothing per slice to estimate)
+            continue
         x[c][n].slice_w.copy_(slice_rule(s, k))
     return x
 
@@ -267,15 +315,19 @@ def _slice_ll(tau, w, sums):
     """1/2 tau sum_s u_s SSE_s of one weighted repeat: ``w`` its (S,) weights, ``sums`` its ``unires_slice_sums``
     ((2 S,) float64: SSE_s, then N_s).  A float64 dot product on the device, no read-back.  The one statement of a
     weighted repeat's data term: the objective (``_compute_nll``) and the rigid update's line search take it from
-    here."""
+    here.  ``w`` None: a repeat with voxel weights alone, u = 1 - ``sums`` are ``unires_voxel_sums``' then, which
+    carry g."""
+    if w is None:
+        return 0.5 * float(tau) * sums[:sums.numel() // 2].sum()
     return 0.5 * float(tau) * (w.double() * sums[:w.numel()]).sum()
 
 
 @on_device
 def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     """Negative model log-likelihood (unires/_update.py:396-427); returns 0-d float64
-    device tensors (nll_yx, nll_xy, nll_y) without synchronising.  A repeat with slice weights contributes
-    1/2 tau sum_s u_s SSE_s (``slice_sums``: ``_slice_sums``' result for this y, computed here when None)."""
+    device tensors (nll_yx, nll_xy, nll_y) without synchronising.  A repeat with slice or voxel weights contributes
+    1/2 tau sum_s u_s SSE_s (``slice_sums``: ``_slice_sums``' result for this y, computed here when None; SSE_s
+    carries g for a voxel-weighted repeat)."""
     dev = y[0].dat.device
     if slice_sums is None:
         slice_sums = _slice_sums(x, y, sett)
@@ -286,7 +338,7 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     for c in range(len(x)):
         for n in range(len(x[c])):
             if (c, n) in slice_sums:
-                nll_xy = nll_xy + _slice_ll(x[c][n].tau, x[c][n].slice_w, slice_sums[(c, n)])
+                nll_xy = nll_xy + _slice_ll(x[c][n].tau, getattr(x[c][n], 'slice_w', None), slice_sums[(c, n)])
                 continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = x[c][n].dat.contiguous()
@@ -382,13 +434,17 @@ def _update_admm(x, y, z, w, rho, tmp, obj, n_iter, sett, info=None):
     joint-TV shrinkage image."""
     y = _update_y(x, y, z, w, rho, tmp, sett, info)
     want_obj = obj is not None and sett.tolerance > 0
-    # (the per-slice residual sums of the weighted repeats: once, for the objective and for the rule)
-    sums = _slice_sums(x, y, sett) if want_obj or _slice_robust(sett) else None
+    # (the per-slice residual sums of the weighted repeats: once, for the objective and for the rules; A y of the
+    # voxel-weighted repeats is kept for the Huber rule)
+    ays = {} if _voxel_robust(sett) else None
+    sums = _slice_sums(x, y, sett, ays) if want_obj or _slice_robust(sett) else None
     if want_obj:
         obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums)
     z, w, tmp = _update_zw(y, z, w, rho, tmp, sett)
     if _slice_robust(sett):  # (after the objective: each iteration's is taken with the weights its y-update used)
         _update_slice_weights(x, y, sett, sums)
+    if _voxel_robust(sett):  # (likewise; A y is computed there where the sums above were not wanted)
+        _update_voxel_weights(x, y, sett, ays)
     # An iteration is enqueue-only (no read-back): a host loop would run ahead until the hardware queue is
     # full and then spin inside every launch call.  The pacer parks the thread - sleeping between looks at a
     # stream mark (_host.StreamMark) - until the device is at most `host_pace` iterations behind (settings.host_pace; 0: off).

@@ -521,6 +521,40 @@ extern "C" int unires_slice_sums(const float *x, const float *ay, const int32_t 
   return UNIRES_OK;
 }
 
+extern "C" int unires_voxel_sums(const float *x, const float *ay, const float *g, const int32_t dim[3],
+                                 int32_t dim_thick, double *out_dev, void *stream) {
+  if (!x || !ay || !g || !dim || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (dim_thick < 0 || dim_thick > 2) return fail(UNIRES_ERR_ARG, "bad dim_thick");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  const size_t cols = 2 * (size_t)dim[dim_thick];
+  if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), dim_thick), &part)) return rc;
+  launch_voxel_sums(x, ay, g, mk(dim), dim_thick, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_voxel_apply(const float *src, float *dst, const float *g, const uint8_t *mask, const float *u,
+                                  const int32_t dim[3], int32_t axis, int32_t flip, const int32_t *done, void *stream) {
+  if (!src || !dst || !g || !dim) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "slice axis: 0, 1 or 2");
+  launch_voxel_apply(src, dst, g, mask, u, mk(dim), axis, flip != 0, done, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_voxel_huber(const float *x, const float *ay, const float *prior, float c, int64_t n,
+                                  float *g_out, void *stream) {
+  if (!x || !ay || !g_out) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n < 0) return fail(UNIRES_ERR_DIM, "bad length");
+  if (!(c > 0.f)) return fail(UNIRES_ERR_ARG, "the Huber threshold must be positive");
+  launch_voxel_huber(x, ay, prior, c, (size_t)n, g_out, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 extern "C" int unires_rigid_resid(const float *x, const float *ay, const int32_t dim[3], int32_t axis,
                                   const float *u_dev, float *out, void *stream) {
   if (!x || !ay || !dim || !out) return fail(UNIRES_ERR_NULL, "null argument");

@@ -24,6 +24,7 @@
 #include "shift.hpp"
 #include "slice.hpp"
 #include "splat2.hpp"
+#include "voxel.hpp"
 
 namespace unires {
 
@@ -164,12 +165,24 @@ struct RepeatWeights {
   size_t w_cap = 0;  // entries
 };
 
-struct Repeat : RepeatDesc, RepeatTables, RepeatMask, RepeatWeights {
+// Per-voxel weights (unires_plan_set_voxel_weights): g, one float per x-space voxel (voxel.hip).  As the mask: g_u is in
+// the caller's layout and kept so that a new orientation (unires_plan_set_repeat) can be served without the caller's
+// map; g_c, only where the plan relabels the observation, is its canonical-layout copy.  Neither address changes while
+// the repeat is weighted - a captured solve reads the values they hold when it runs.  Freed with the plan.
+struct RepeatVoxel {
+  bool voxw = false;
+  float *g_u = nullptr, *g_c = nullptr;
+  size_t g_cap = 0;  // entries of either allocation
+};
+
+struct Repeat : RepeatDesc, RepeatTables, RepeatMask, RepeatWeights, RepeatVoxel {
+  // the voxel weights in the layout the x-space intermediate of A^T A has
+  const float *vox() const { return oriented ? g_c : g_u; }
   // the mask in the layout the x-space intermediate of A^T A has
   const uint8_t *mask() const { return oriented ? mask_c : mask_u; }
-  // a pass runs on the x-space intermediate of A^T A (mask, weights or both): the intermediate has to exist, so the
-  // one-kernel matvecs, the single-pass AtA kernel and the hybrid forms are declined
-  bool mid() const { return masked || weighted; }
+  // a pass runs on the x-space intermediate of A^T A (mask, slice weights, voxel weights or any of them together): the
+  // intermediate has to exist, so the one-kernel matvecs, the single-pass AtA kernel and the hybrid forms are declined
+  bool mid() const { return masked || weighted || voxw; }
   // the canonical axis the slices of w_axis run along, and whether the plan reversed it
   int w_caxis() const {
     for (int j = 0; j < 3; ++j)

@@ -65,7 +65,10 @@ static void forward(unires_plan *pl, const Repeat &R, const float *in, const Sca
 // diag(m) and commutes with it and with S.  `weights` false: the repeat's unweighted operator (unires_proj_apply's
 // UNIRES_OP_ATA, which stays the reference's).
 static void mid_pass(const Repeat &R, float *buf, bool weights, const int *done, hipStream_t st) {
-  if (R.weighted && weights)
+  if (R.voxw && weights)  // (voxel weights: slice weights and mask in the same pass, voxel.hip)
+    launch_voxel_apply(buf, buf, R.vox(), R.masked ? R.mask() : nullptr, R.weighted ? R.w_dev : nullptr, R.dim_x,
+                       R.w_caxis(), R.w_flip(), done, st);
+  else if (R.weighted && weights)
     launch_slice_apply(buf, buf, R.masked ? R.mask() : nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), done, st);
   else if (R.masked)
     launch_mask_apply(buf, R.mask(), R.dim_x.numel(), done, st);
@@ -219,9 +222,16 @@ static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, floa
     return;
   }
   const bool w = weights && R.weighted;
+  const bool v = weights && R.voxw;  // (g . u . x of a voxel-weighted repeat: one pass for both kinds of weight)
   if (R.oriented) {  // the caller's voxel layout -> the plan's
     launch_to_canonical(R.orient, x, R.dim_xu, pl->xperm, st);
-    if (w) launch_slice_apply(pl->xperm, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
+    if (v)
+      launch_voxel_apply(pl->xperm, pl->xperm, R.g_c, nullptr, w ? R.w_dev : nullptr, R.dim_x, R.w_caxis(), R.w_flip(),
+                         nullptr, st);
+    else if (w) launch_slice_apply(pl->xperm, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
+    x = pl->xperm;
+  } else if (v) {
+    launch_voxel_apply(x, pl->xperm, R.g_u, nullptr, w ? R.w_dev : nullptr, R.dim_x, R.w_axis, false, nullptr, st);
     x = pl->xperm;
   } else if (w) {
     launch_slice_apply(x, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_axis, false, nullptr, st);

@@ -407,6 +407,24 @@ static void free_weights(RepeatWeights &R) {
   R.w_cap = 0, R.weighted = false;
 }
 
+static void free_voxel(RepeatVoxel &R) {
+  if (R.g_u) (void)hipFree(R.g_u);
+  if (R.g_c) (void)hipFree(R.g_c);
+  R.g_u = R.g_c = nullptr;
+  R.g_cap = 0, R.voxw = false;
+}
+
+// the canonical-layout copy of a voxel-weighted, relabelled repeat's weights, for the orientation the repeat has now
+static int canonical_voxel(Repeat &R, hipStream_t st) {
+  if (!R.voxw || !R.oriented) return UNIRES_OK;
+  if (!R.g_c && hipMalloc((void **)&R.g_c, R.g_cap * sizeof(float)) != hipSuccess) {
+    R.g_c = nullptr;
+    return fail(UNIRES_ERR_ALLOC, "hipMalloc voxel weights");
+  }
+  launch_voxel_permute(R.g_u, R.orient, R.dim_xu, R.g_c, st);
+  return UNIRES_OK;
+}
+
 // the canonical-layout copy of a masked, relabelled repeat's mask, for the orientation the repeat has now
 static int canonical_mask(Repeat &R, hipStream_t st) {
   if (!R.masked || !R.oriented) return UNIRES_OK;
@@ -507,7 +525,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->last_use) (void)hipEventDestroy(plan->last_use);
   drop_timing(plan);
   fftpre_destroy(plan->fft);
-  for (Repeat &R : plan->reps) free_tables(R), free_mask(R), free_weights(R);
+  for (Repeat &R : plan->reps) free_tables(R), free_mask(R), free_weights(R), free_voxel(R);
   delete plan;
   return UNIRES_OK;
 }
@@ -588,6 +606,8 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   // them and its direction are read from the new orientation at every launch, no device work here)
   if (plan->reps[n].weighted && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
     return fail(UNIRES_ERR_DIM, "a weighted repeat keeps its observation's dims (clear the weights first)");
+  if (plan->reps[n].voxw && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
+    return fail(UNIRES_ERR_DIM, "a voxel-weighted repeat keeps its observation's dims (clear the weights first)");
   if (plan->regime != UNIRES_REGIME_IDENTITY &&
       (tmp.dim_g.numel() > plan->cap_g || tmp.dim_x.numel() > plan->cap_x))
     return fail(UNIRES_ERR_DIM, "new repeat exceeds the plan's workspace");
@@ -626,6 +646,11 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
   // and waited for, like the tables above
   if (!rc && R.masked && R.oriented) {
     rc = canonical_mask(R, nullptr);
+    if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  // ... and so do the voxel weights and their canonical copy
+  if (!rc && R.voxw && R.oriented) {
+    rc = canonical_voxel(R, nullptr);
     if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
   }
   return rc;
@@ -760,6 +785,67 @@ extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int
   return UNIRES_OK;
 }
 
+// Per-voxel weights of repeat n's data term: g_dev holds one float per x-space voxel in the caller's layout, on the
+// device; the plan copies them into a buffer of its own (and, where it relabels the observation, permutes that into a
+// canonical-layout copy, as for the mask) and its A^T A becomes A^T diag(g . u . m) A (api_operator.hip: mid_pass), its
+// right-hand side term A^T (g . u . x).  Two kinds of call, as for the slice weights:
+//   a first set or a clear: the repeat's forms change (choose_family, the gates of api_operator.hip), so the plan's
+//     earlier launches are waited for, the captured solves go, and the tables are rebuilt where the family differs;
+//   new values: nothing is rebuilt and nothing waited for.  Copy and permute are enqueued on `stream`; a captured solve
+//     is KEPT - it has the buffers' addresses baked in, which do not change, and reads the values there when it is
+//     replayed (sett.voxel_robust changes the values every ADMM iteration).
+// The built preconditioner is dropped either way.  The values are not looked at: g >= 0 is the caller's contract.
+extern "C" int unires_plan_set_voxel_weights(unires_plan_t *plan, int32_t n, const float *g_dev, void *stream) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null plan");
+  if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
+  if (plan->regime == UNIRES_REGIME_IDENTITY)
+    return fail(UNIRES_ERR_UNSUPPORTED,
+                "regime A = I has no x-space intermediate to weight: build the plan in the denoising regime with the "
+                "identity affine");
+  Repeat &R = plan->reps[n];
+  if (!g_dev && !R.voxw) return UNIRES_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool was = R.voxw, was_mid = R.mid();
+  const bool values_only = g_dev && was;
+  plan->prec_ready = false;
+  if (!values_only) {
+    await_use(plan);
+    drop_cg_graph(plan);
+  }
+  if (g_dev) {
+    // every allocation first: a failure leaves the repeat as it was
+    const size_t nx = R.dim_xu.numel();
+    if (R.g_cap < nx) {  // (never while the repeat is weighted: its dims are kept, and the buffers were sized for them)
+      free_voxel(R);
+      if (hipMalloc((void **)&R.g_u, nx * sizeof(float)) != hipSuccess) {
+        R.g_u = nullptr;
+        return fail(UNIRES_ERR_ALLOC, "hipMalloc voxel weights");
+      }
+      R.g_cap = nx;
+    }
+    if (R.oriented && !R.g_c && hipMalloc((void **)&R.g_c, R.g_cap * sizeof(float)) != hipSuccess) {
+      R.g_c = nullptr;
+      return fail(UNIRES_ERR_ALLOC, "hipMalloc voxel weights");
+    }
+    mark_use(plan, st);
+    HIP_TRY(hipMemcpyAsync(R.g_u, g_dev, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
+    R.voxw = true;
+    (void)canonical_voxel(R, st);  // (its buffer exists: nothing left to fail)
+  } else {
+    R.voxw = false;
+  }
+  if (was_mid != R.mid()) {  // (a masked or slice-weighted repeat has the two-kernel family already)
+    if (int rc = refamily(plan, R)) {
+      // the tables of the new family could not be built: back to the state before the call
+      R.voxw = was;
+      (void)refamily(plan, R);
+      return rc;
+    }
+  }
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 // How many solves of OTHER plans the caller keeps in flight next to this one's (the channels of a y-update, each
 // on a stream of its own: unires/_update.py:122-150 has no cross-channel term).  The matvec's persistent kernels
 // (k_splat2, k_ata1) normally take every wave slot / register the chip has - a channel's kernels then run one
@@ -833,7 +919,7 @@ extern "C" int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int
   info[5] = R.sched.valid ? 2 + R.sched.axis : 0;
   // (the forms the matvec takes: a masked or weighted repeat skips the one-kernel matvec and the single-pass AtA kernel)
   info[6] = (R.shift.valid && !R.mid() ? 1 : 0) | (R.f1.valid && !R.mid() ? 2 : 0) | (R.masked ? 4 : 0) |
-            (R.weighted ? 8 : 0);
+            (R.weighted ? 8 : 0) | (R.voxw ? 16 : 0);
   info[7] = R.sep ? 1 : 0;
   return UNIRES_OK;
 }

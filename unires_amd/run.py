@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._core import (_estimate_hyperpar, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
-                    _not_built, _proj_info_add, _read_data, _resample_inplane, _write_data)
+                    _not_built, _proj_info_add, _read_data, _read_weights, _resample_inplane, _write_data)
 from ._host import wait_blocking
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
@@ -77,6 +77,48 @@ def _init_slice_weights(x, sett, dev):
             xn.slice_w = w.clone() if w is xn.slice_w else w
 
 
+def _init_voxel_weights(x, sett, dev):
+    """The observations' voxel weights as the iterations take them: a user's ``_input.weight`` validated (the
+    observation's shape, real, finite, >= 0 - the one read-back) and moved to the device as contiguous float32.  With
+    ``sett.voxel_robust`` a private clone of it is kept as the rule's prior (``xn._weight_prior``; None: ones) and
+    every observation starts from its prior, or from ones where it has none, so that the plans' kernels do not change
+    mid-fit.  The scaling and rigid Gauss-Newton updates do not carry voxel weights yet: they are refused by name
+    rather than left to minimise another data term."""
+    robust = bool(getattr(sett, 'voxel_robust', False))
+    if robust and not float(getattr(sett, 'voxel_k', 3.0)) > 0:
+        raise ValueError('sett.voxel_k must be positive')
+    any_w = robust
+    for c, xc in enumerate(x):
+        for n, xn in enumerate(xc):
+            xn._weight_prior = None
+            g = getattr(xn, 'weight', None)
+            if g is None:
+                if robust:
+                    xn.weight = torch.ones(tuple(xn.dat.shape), dtype=torch.float32, device=dev)
+                continue
+            any_w = True
+            g = given = torch.as_tensor(g)
+            if tuple(g.shape) != tuple(xn.dat.shape):
+                raise ValueError('x[%d][%d].weight has shape %s, expected %s: one weight per voxel of the observation'
+                                 % (c, n, tuple(g.shape), tuple(xn.dat.shape)))
+            if g.is_complex() or g.dtype == torch.bool:
+                raise ValueError('x[%d][%d].weight must be real numbers' % (c, n))
+            g = g.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if not bool((torch.isfinite(g) & (g >= 0)).all()):
+                raise ValueError('x[%d][%d].weight must be finite and >= 0' % (c, n))
+            if robust:
+                # (a conversion above made a copy already; a tensor that needed none still shares the user's memory)
+                xn._weight_prior = g.clone() if g.data_ptr() == given.data_ptr() else g
+                xn.weight = xn._weight_prior.clone()
+            else:
+                xn.weight = g
+    if any_w:
+        for name in ('scaling', 'unified_rigid'):
+            if getattr(sett, name, False):
+                raise NotImplementedError('sett.%s with voxel weights (_input.weight, sett.voxel_robust): the '
+                                          'Gauss-Newton updates do not carry per-voxel weights' % name)
+
+
 @on_device
 def fit(x, y, sett):
     """Fit model (unires/run.py:24-207).  ``x[c][n]`` / ``y[c]`` are the _input / _output
@@ -87,7 +129,8 @@ def fit(x, y, sett):
     output affine, the rigid matrices (N, 4, 4) and a dict with the objective trace
     ``obj`` (n_iter, 3), the iteration count, the regularisation schedule and ``slice_w``: per channel a list with
     each repeat's final slice weights (a CPU float32 tensor, one per slice along ``po.dim_thick``) or None for a
-    repeat without weights.
+    repeat without weights, and ``voxel_w``: likewise each repeat's final voxel weights (``_input.weight``,
+    ``sett.voxel_robust``) as the DEVICE float32 tensor the iterations used, or None.
 
     Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
@@ -97,6 +140,7 @@ def fit(x, y, sett):
     with torch.no_grad():
         dev = y[0].dat.device
         _init_slice_weights(x, sett, dev)
+        _init_voxel_weights(x, sett, dev)
         N = sum(len(xc) for xc in x)
         sett = _get_sched(N, sett)
         cnt_scl = 0
@@ -148,7 +192,9 @@ def fit(x, y, sett):
         R = torch.stack([xn.po.rigid.double().cpu() for xc in x for xn in xc])
         dat_y = torch.stack([yc.dat for yc in y], dim=-1)
         slice_w = [[None if getattr(xn, 'slice_w', None) is None else xn.slice_w.detach().cpu() for xn in xc] for xc in x]
-        info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w)
+        voxel_w = [[getattr(xn, 'weight', None) for xn in xc] for xc in x]
+        info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w,
+                    voxel_w=voxel_w)
         return dat_y, y[0].mat, R, info
 
 
@@ -169,6 +215,7 @@ def init(data, sett=None):
     with torch.no_grad():
         x = _read_data(data, sett)
         del data
+        x = _read_weights(x, sett)
         if sett.max_iter > 0:
             x = _estimate_hyperpar(x, sett)
         x = _fix_affine(x, sett)

@@ -26,6 +26,11 @@ class _input:
         # and the scaling and rigid Gauss-Newton updates (sett.scaling, sett.unified_rigid) all minimise it - a slice
         # of weight 0 reaches none of them
         self.slice_w = None
+        # per-voxel weights of the data term, float32 (X, Y, Z) like dat, >= 0: None - every voxel has weight 1.  Set
+        # before fit() to distrust known voxels (a defect mask, a confidence map; fit() validates them once and moves
+        # them to the device); with sett.voxel_robust they are the prior the Huber weights multiply, so a 0 stays 0.
+        # They enter the y-update and the objective; sett.scaling and sett.unified_rigid are refused with them
+        self.weight = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
         self.fname = None
@@ -93,6 +98,17 @@ class settings:
         # nobody has tuned on real data.  Off: every slice has weight 1 unless the user set _input.slice_w.
         self.slice_robust = False
         self.slice_k = 3.0
+        # build-side knobs: robust voxel outlier rejection.  voxel_robust: after every ADMM iteration each voxel of each
+        # observation gets the Huber weight of its residual r = x - A y (_update._update_voxel_weights): 1 unless |r|
+        # exceeds voxel_k noise standard deviations, c = voxel_k / sqrt(tau), then c / |r|; times the user's
+        # _input.weight where there is one.  The data term becomes 1/2 tau sum_v g(v) (x - A y)^2(v) in the y-update
+        # (ChannelPlan.set_voxel_weights) and the objective.  voxel_k = 3 is a modelling default nobody has tuned on
+        # real data.  Off: every voxel has weight 1 unless the user set _input.weight.
+        self.voxel_robust = False
+        self.voxel_k = 3.0
+        # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
+        # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
+        self.weight = None
         self.gap = 0.0
         self.interpolation = 'linear'
         self.method = None
