@@ -534,6 +534,17 @@ int unires_scaling_sums(const float *x, const float *ay, const int32_t dim[3], i
 int unires_scaling_sums_w(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
                           const float *u_dev, double *out_dev, void *stream);
 
+/* The same five sums of the data term with per-voxel weights, 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - ay)^2 (no
+ * counterpart in the reference): every term of unires_scaling_sums times W(v) = g(v), or g(v) u[s(v)] where u_dev is
+ * given.  g_dev: a DEVICE volume `dim` in the caller's layout, NULL is UNIRES_ERR_NULL; u_dev: a DEVICE pointer to
+ * dim[dim_thick] floats, or NULL.  The float32 term is unires_scaling_sums'; W is formed in float64, where g u is exact;
+ * the summand fl64(W t) is exact without u and rounded once with it.  float64 sums in unires_scaling_sums' fixed order,
+ * no atomics: the same bits every run; with g = 1 the bits of unires_scaling_sums_w (u_dev given) or of
+ * unires_scaling_sums (u_dev NULL), with g constant on every slice and u_dev NULL those of unires_scaling_sums_w with
+ * these constants as u. */
+int unires_scaling_sums_g(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick, const float *g_dev,
+                          const float *u_dev, double *out_dev, void *stream);
+
 /* The x-space residual of one rigid Gauss-Newton step (_rigid_match, _update.py:515-519) in one pass:
  *   out[v] = u[s(v)] * (ay[v] - x[v])  where x[v] != 0 and ay[v] != 0, else +0
  * x, ay, out: volumes `dim`; s(v) = v's index along `axis`; u_dev: a DEVICE pointer to dim[axis] floats, or NULL
@@ -541,6 +552,15 @@ int unires_scaling_sums_w(const float *x, const float *ay, const int32_t dim[3],
  * out == ay is allowed; x is only read. */
 int unires_rigid_resid(const float *x, const float *ay, const int32_t dim[3], int32_t axis, const float *u_dev,
                        float *out, void *stream);
+
+/* The same residual on the data term with per-voxel weights (no counterpart in the reference):
+ *   out[v] = fl32(W(v) r(v)),  r = fl32(ay[v] - x[v]),  where x[v] != 0 and ay[v] != 0, else +0
+ * with W = g (u_dev == NULL: one float32 product) or W = g[v] u[s(v)] (exact in float64, times r, rounded to float32
+ * once) - unires_voxel_apply's rounding.  g: a DEVICE volume `dim` of weights; u_dev: dim[axis] floats on the device,
+ * or NULL.  g = 1 gives the bits of unires_rigid_resid with the same u_dev.  out == ay is allowed; x and g are only
+ * read, and out == g is UNIRES_ERR_ARG.  Buffers off a 16-byte boundary are served voxel by voxel. */
+int unires_rigid_resid_g(const float *x, const float *ay, const float *g, const int32_t dim[3], int32_t axis,
+                         const float *u_dev, float *out, void *stream);
 
 /* ------------------------------------------------------------------------
  * Stream marks: following a stream from the host by reading memory.

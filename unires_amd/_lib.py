@@ -119,6 +119,10 @@ SIGNATURES = {
     'unires_scaling_sums_w': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     'unires_rigid_resid': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_scaling_sums_g': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    'unires_rigid_resid_g': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     'unires_rigid_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_float * 72,
                                     C.c_void_p, C.c_void_p]),
     'unires_clean_fov': (C.c_int, [C.c_void_p, c_i32x3, c_f32x12, c_i32x3, C.c_void_p]),

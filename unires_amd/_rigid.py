@@ -24,7 +24,7 @@ from ._host import light_host
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
 from ._project import _apply_scaling, _proj_info, _slice_axis, _taps, _thick_axis
-from ._update import _slice_ll
+from ._update import _gn_weight, _slice_ll
 from .spatial import _m12
 
 _F64 = torch.float64
@@ -87,9 +87,14 @@ def _logq(rigid, basis):
     po.rigid."""
     import numpy as np
     from scipy.linalg import logm
-    L = torch.from_numpy(np.real(logm(torch.as_tensor(rigid, dtype=_F64).cpu().numpy())))
-    A = basis.to('cpu', _F64).reshape(basis.shape[0], -1).T  # (16, num_q)
-    return torch.linalg.lstsq(A, L.reshape(-1, 1)).solution[:, 0]
+    L = np.real(logm(torch.as_tensor(rigid, dtype=_F64).cpu().numpy()))
+    A = basis.to('cpu', _F64).reshape(basis.shape[0], -1).T.contiguous().numpy()  # (16, num_q)
+    # numpy's least squares, not torch's: torch.linalg.lstsq on this 16 x 6 system returns different last bits from one
+    # call to the next (13 distinct results in 300 calls on the same matrix; the logarithm above does not vary), and
+    # two rigid updates of the same data then differ in every bit that follows.  numpy's gave one result in 500 calls,
+    # within 6e-17 of torch's.
+    q = np.linalg.lstsq(A, np.ascontiguousarray(L).reshape(-1), rcond=None)[0]
+    return torch.from_numpy(np.array(q, dtype=np.float64))
 
 
 def _grid_matrix(po, rigid, method):
@@ -99,7 +104,7 @@ def _grid_matrix(po, rigid, method):
 
 
 @on_device
-def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None):
+def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None, weight=None):
     """ll and, if ``diff``, the raw ingredients of the derivatives: gr3 (dim,3) = grid_grad,
     dg (dim) = residual in grid space.
 
@@ -107,7 +112,13 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     ``dat_x`` - already decimated where ``dat_x`` is), or None.  With weights the terms are those of the weighted data
     term 1/2 tau sum_v u[s(v)] [x != 0] (x - A y)^2: ll = 1/2 tau sum_s u_s SSE_s from ``unires_slice_sums``
     (``_update._slice_ll``, the objective's own expression) and the x-space residual u[s(v)] (A y - x), masked, in one
-    pass (``unires_rigid_resid``).  Without, the code path is what it was."""
+    pass (``unires_rigid_resid``).  Without, the code path is what it was.
+
+    ``weight``: the repeat's voxel weights (float32, on the device, the shape of ``dat_x`` - already decimated where
+    ``dat_x`` is), or None; ``axis`` is then the repeat's slice axis whether or not it has slice weights.  The terms are
+    those of 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - A y)^2: ll = 1/2 tau sum_s u_s SSE_s with SSE_s from
+    ``unires_voxel_sums``, which carries g - the statement ``_compute_nll`` takes a voxel-weighted repeat's term from -
+    and the residual g u[s(v)] (A y - x), masked, in one pass (``unires_rigid_resid_g``)."""
     method = sett.method
     lib = _lib.load()
     mat, dim = _grid_matrix(po, rigid, method)
@@ -117,7 +128,19 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
         scl = float(po.scl)
         dat_yx = _ops.conv_down(dat_yx, _taps(po), po.ratio, scl, po.dim_thick)
     dat_yx = dat_yx.reshape(tuple(dat_x.shape))
-    if slice_w is None:
+    if weight is not None:
+        dat_x, dat_yx, weight = dat_x.contiguous(), dat_yx.contiguous(), weight.contiguous()
+        if weight.dtype != torch.float32 or tuple(weight.shape) != tuple(dat_x.shape):
+            raise ValueError('weight: one float32 weight per voxel of dat_x')
+        if slice_w is not None:
+            slice_w = slice_w.contiguous()
+            if slice_w.dtype != torch.float32 or slice_w.numel() != dat_x.shape[axis]:
+                raise ValueError('slice_w: one float32 weight per slice of dat_x along axis %d' % axis)
+        sums = torch.empty(2 * int(dat_x.shape[axis]), dtype=_F64, device=dat_x.device)
+        check(lib.unires_voxel_sums(_ptr(dat_x), _ptr(dat_yx), _ptr(weight), i3(dat_x.shape), axis, _ptr(sums),
+                                    _stream()))
+        ll = _slice_ll(tau, slice_w, sums)
+    elif slice_w is None:
         sse = torch.zeros((), dtype=_F64, device=dat_x.device)
         check(lib.unires_masked_sse(_ptr(dat_x), _ptr(dat_yx), dat_x.numel(), _ptr(sse), _stream()))
         ll = 0.5 * float(tau) * sse
@@ -131,7 +154,11 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     if not diff:
         return ll, None, None
     gr3 = _ops.pull_grad_affine(dat_y, M, dim).reshape(dim + (3,))
-    if slice_w is None:
+    if weight is not None:
+        d = dat_yx  # (in place: A y is not needed again)
+        check(lib.unires_rigid_resid_g(_ptr(dat_x), _ptr(dat_yx), _ptr(weight), i3(dat_x.shape), axis,
+                                       None if slice_w is None else _ptr(slice_w), _ptr(d), _stream()))
+    elif slice_w is None:
         d = dat_yx - dat_x
         d[(dat_x == 0) | (dat_yx == 0)] = 0  # :517-519
     else:
@@ -144,18 +171,19 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
 
 
 @on_device
-def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None):
+def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None, weight=None):
     """Rigid matching term with the reference's return shapes (unires/_update.py:448-538):
     ll, gr (dim, 3) = grid_grad * residual, Hes (dim, 6) = outer(grid_grad) [* CtC].
-    ``slice_w``: the observation's slice weights along ``po.dim_thick`` (``_rigid_terms``); the Hessian's weight is the
-    caller's ``CtC`` (``_ctc`` with the same weights)."""
+    ``slice_w``: the observation's slice weights along ``po.dim_thick`` (``_rigid_terms``); ``weight``: its voxel
+    weights, the shape of ``dat_x``; the Hessian's weight is the caller's ``CtC`` (``_ctc`` with the same weights)."""
+    weighted = slice_w is not None or weight is not None
     ll, gr3, d = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=diff, slice_w=slice_w,
-                              axis=None if slice_w is None else _thick_axis(po))
+                              axis=_thick_axis(po) if weighted else None, weight=weight)
     if not diff:
         return ll, None, None
     Hes = torch.stack([gr3[..., 0] * gr3[..., 0], gr3[..., 1] * gr3[..., 1], gr3[..., 2] * gr3[..., 2],
                        gr3[..., 0] * gr3[..., 1], gr3[..., 0] * gr3[..., 2], gr3[..., 1] * gr3[..., 2]], -1)
-    if sett.method == 'super-resolution' or (slice_w is not None and CtC is not None):
+    if sett.method == 'super-resolution' or (weighted and CtC is not None):
         Hes = Hes * CtC[..., None]
     return ll, gr3 * d[..., None], Hes
 
@@ -167,12 +195,25 @@ def _spread(slice_w, shape, axis):
     return slice_w.reshape(view).expand(tuple(int(v) for v in shape))
 
 
-def _ctc(po, dim, device, slice_w=None, axis=None):
+def _voxel_times(src, weight, slice_w, axis):
+    """g [u[s(v)]] src in place on ``src`` (contiguous float32, ``weight``'s shape): ``unires_voxel_apply`` without a
+    mask - g u is exact in float64, g u src one rounding to float32."""
+    check(_lib.load().unires_voxel_apply(_ptr(src), _ptr(src), _ptr(weight), None,
+                                         None if slice_w is None else _ptr(slice_w), i3(weight.shape), axis, 0, None,
+                                         _stream()))
+    return src
+
+
+def _ctc(po, dim, device, slice_w=None, axis=None, weight=None):
     """conv_transpose(conv(1)) (unires/_update.py:603-607); with slice weights conv_transpose(u . conv(1)): the
-    weights applied in x space between the two halves (times 1 is exact: u = 1 gives the unweighted bits)."""
+    weights applied in x space between the two halves (times 1 is exact: u = 1 gives the unweighted bits).  With voxel
+    weights ``weight`` (contiguous float32, the decimated observation's shape) conv_transpose(W . conv(1)), W = g or
+    g u[s(v)]: one pass and one rounding (``_voxel_times``; g = 1 gives the bits of the form above)."""
     ones = torch.ones(dim, dtype=torch.float32, device=device)
     low = _ops.conv_down(ones, _taps(po), po.ratio)
-    if slice_w is not None:
+    if weight is not None:
+        low = _voxel_times(low.contiguous().reshape(tuple(weight.shape)), weight, slice_w, axis)
+    elif slice_w is not None:
         low = low * _spread(slice_w, low.shape, axis)
     return _ops.conv_up(low, _taps(po), po.ratio).contiguous()
 
@@ -187,7 +228,13 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
     Hessian's weight - conv_transpose(u . conv(1)), or the volume u[s(v)] in the denoising regime - all carry the
     weights, decimated with the observation (``u[::sk[a]][:dim_x[a]]``) and built once per repeat.  A repeat whose
     weights are all zero has a zero Hessian: its ``rigid_q`` and ``po.rigid`` are left as they are and it adds 0 to
-    ``sll``.  A repeat without weights runs exactly what it ran before."""
+    ``sll``.  A repeat without weights runs exactly what it ran before.
+
+    With ``sett.voxel_gn`` a repeat with voxel weights (``xn.weight``) takes its step on 1/2 tau sum_v g(v) u[s(v)]
+    [x != 0] (x - A y)^2 in the same way: the map is decimated as the data are (``g[::sk[0], ::sk[1], ::sk[2]]``, cut
+    to ``dim_x``), the Hessian's weight is conv_transpose(W . conv(1)) with W = g or g u[s(v)] - the volume W in the
+    denoising regime - and a map that is all zero leaves the repeat alone.  Without ``sett.voxel_gn`` the map is
+    ignored, as it was before the update could carry it."""
     lib = _lib.load()
     dev = yc.dat.device
     method = sett.method
@@ -214,11 +261,20 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
         dat_x = xn.dat[::sk[0], ::sk[1], ::sk[2]][:po.dim_x[0], :po.dim_x[1], :po.dim_x[2]].contiguous()
         dat_y = yc.dat
         u = getattr(xn, 'slice_w', None)
+        g = _gn_weight(xn, sett)
         a = _slice_axis(xn)
-        if u is None:
+        if u is not None:
+            u = u[::sk[a]][:po.dim_x[a]].contiguous()
+        if g is not None:
+            # (the map decimated as the data are; the Hessian's weight W = g [u] once per repeat and call)
+            g = g[::sk[0], ::sk[1], ::sk[2]][:po.dim_x[0], :po.dim_x[1], :po.dim_x[2]].contiguous()
+            if method == 'super-resolution':
+                CtC = _ctc(po, dim, dev, u, a, weight=g)
+            else:
+                CtC = g if u is None else _voxel_times(torch.ones_like(g), g, u, a)
+        elif u is None:
             CtC = _ctc(po, dim, dev) if method == 'super-resolution' else None
         else:
-            u = u[::sk[a]][:po.dim_x[a]].contiguous()
             CtC = _ctc(po, dim, dev, u, a) if method == 'super-resolution' else _spread(u, dat_x.shape, a).contiguous()
         empty = False
         ll = torch.zeros((), dtype=_F64, device=dev)
@@ -226,7 +282,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
         for _gn in range(max_niter_gn):
             rigid, d_rigid = _expm(q, basis, grad_X=True)
             D = torch.stack([torch.linalg.solve(po.mat_y, d_rigid[i].mm(mat)) for i in range(num_q)])
-            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a)
+            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a, weight=g)
             d72 = (C.c_float * 72)(*D[:, :3, :].reshape(-1).float().tolist())
             check(lib.unires_rigid_sums(_ptr(gr3), _ptr(dg), _ptr(CtC) if CtC is not None else None,
                                         i3(dim), d72, _ptr(sums), _stream()))
@@ -234,7 +290,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
             Hes = np.zeros((num_q, num_q))
             Hes[iu] = s[num_q:]
             Hes = Hes + np.triu(Hes, 1).T
-            if u is not None and not Hes.any():  # (all weights zero: no data term, no step - nothing to solve)
+            if (u is not None or g is not None) and not Hes.any():  # (all weights zero: no data term, no step - nothing to solve)
                 empty = True
                 break
             Update = torch.from_numpy(np.linalg.solve(Hes, s[:num_q]))
@@ -246,7 +302,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
                 for n_ls in range(num_linesearch):
                     q = old_q - armijo * Update
                     rigid = _expm(q, basis)
-                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a)[0]
+                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a, weight=g)[0]
                     if bool(ll < old_ll):
                         armijo = min(1.25 * armijo, 1.0)
                         if verbose >= 1:

@@ -214,6 +214,20 @@ def _voxel_robust(sett):
     return bool(getattr(sett, 'voxel_robust', False))
 
 
+def _gn_weight(xn, sett):
+    """The voxel weights the scaling and rigid Gauss-Newton updates carry for repeat ``xn``: ``xn.weight`` with
+    ``sett.voxel_gn`` (checked: a contiguous float32 device tensor of the observation's shape, as ``fit()`` leaves
+    it), else None - the switch is off by default, and the updates then ignore the map as they did before."""
+    g = getattr(xn, 'weight', None)
+    if g is None or not getattr(sett, 'voxel_gn', False):
+        return None
+    if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() \
+            or tuple(g.shape) != tuple(xn.dat.shape):
+        raise ValueError('unires_amd: xn.weight must be a contiguous float32 device tensor of the observation\'s '
+                         'shape, as fit() leaves it')
+    return g
+
+
 @on_device
 def _slice_sums(x, y, sett, ays=None):
     """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights: SSE_s = sum_{v in s,
@@ -364,7 +378,12 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
     A repeat with slice weights (``xn.slice_w``, a float32 device tensor as ``fit()`` leaves it) minimises its own data
     term 1/2 tau sum_v u[s(v)] [x != 0] (x - A y)^2: every one of the five sums carries the weight of the voxel's slice
     (``unires_scaling_sums_w``).  A repeat whose weights are all zero has no data term: its ``po.scl`` is left as it
-    is and it adds 0 to ``sll``.  A repeat without weights runs exactly what it ran before."""
+    is and it adds 0 to ``sll``.  A repeat without weights runs exactly what it ran before.
+
+    With ``sett.voxel_gn`` a repeat with voxel weights (``xn.weight``, a contiguous float32 device tensor as ``fit()``
+    leaves it) minimises 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - A y)^2: the five sums carry g, and the slice weights
+    where the repeat has both (``unires_scaling_sums_g``); all weights zero: left alone, as above.  Without
+    ``sett.voxel_gn`` ``xn.weight`` is ignored, as it was before the update could carry it."""
     from ._project import _apply_scaling
     if sett.method != 'super-resolution':
         raise ValueError('_update_scaling needs the super-resolution projection '
@@ -385,9 +404,13 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
             dat_y = plan.proj_apply(n_x, 'A', y[c].dat)  # pull + conv + S(scl)  (:316-322)
             u = getattr(xn, 'slice_w', None)
             u = None if u is None else u.contiguous()
+            g = _gn_weight(xn, sett)
 
             def evaluate(ay):
-                if u is None:
+                if g is not None:
+                    check(lib.unires_scaling_sums_g(_ptr(dat_x), _ptr(ay), i3(dat_x.shape), dim_thick, _ptr(g),
+                                                    None if u is None else _ptr(u), _ptr(sums), _stream()))
+                elif u is None:
                     check(lib.unires_scaling_sums(_ptr(dat_x), _ptr(ay), i3(dat_x.shape), dim_thick,
                                                   _ptr(sums), _stream()))
                 else:
@@ -402,7 +425,7 @@ def _update_scaling(x, y, sett, max_niter_gn=1, num_linesearch=4, verbose=0):
                 ll = 0.5 * tau * s[0]
                 gr = tau * (s[1] - s[2])
                 hes = tau * (s[3] + s[4])
-                if u is not None and hes == 0.0:  # (all weights zero: no data term, no step - not the 0 / 0 below)
+                if (u is not None or g is not None) and hes == 0.0:  # (all weights zero: no data term, no step - not the 0 / 0 below)
                     empty = True
                     break
                 update = float(torch.tensor(gr, dtype=torch.float64) / torch.tensor(hes, dtype=torch.float64))  # IEEE: 0/0 -> nan, like the reference's tensors

@@ -245,9 +245,61 @@ __global__ void __launch_bounds__(kBlock)
     for (int k = 0; k < 5; ++k) part[5 * blockIdx.x + k] = v[k];
 }
 
+// The same five sums of the data term with per-voxel weights, 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - y)^2 (voxel.hip):
+// k_scaling_sums' walk, grid and trees, every term times W(v) = g(v) [u[c]].  g is read at the walk's own index, one
+// float beside x; W is formed in float64, where g u is exact (24 + 24 significant bits).  Without SLICE the summand W t
+// is exact too (48 bits): g = 1 gives k_scaling_sums' bits, g constant per slice k_scaling_sums_w's.  With SLICE W t has
+// up to 72 bits and is rounded to float64 once, by __dmul_rn - no fused multiply-add, whose sum would round differently;
+// g = 1 leaves W = u and the product exact: k_scaling_sums_w's bits.  A sibling again: the two kernels above keep their
+// instructions.
+template <bool SLICE>
+__global__ void __launch_bounds__(kBlock)
+    k_scaling_sums_g(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ gw, Dim3i d,
+                     int dim_thick, const float *__restrict__ u, double *__restrict__ part) {
+  const size_t n = d.numel(), stride = (size_t)gridDim.x * blockDim.x;
+  const size_t plane = (size_t)d.y * d.z;
+  const int sx = (int)(stride / plane), sy = (int)((stride % plane) / d.z), sz = (int)(stride % d.z);
+  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int px = (int)(i0 / plane), py = (int)((i0 % plane) / d.z), pz = (int)(i0 % d.z);
+  double s0 = 0.0, ge = 0.0, go = 0.0, he = 0.0, ho = 0.0;
+  for (size_t i = i0; i < n; i += stride) {
+    const float xv = x[i];
+    if (xv != 0.f) {
+      const float yv = y[i], r = __fsub_rn(xv, yv);
+      const int c = dim_thick == 2 ? pz : (dim_thick == 1 ? py : px);
+      const double W = SLICE ? __dmul_rn((double)gw[i], (double)u[c]) : (double)gw[i];
+      s0 += __dmul_rn(W, (double)__fmul_rn(r, r));
+      const double g = __dmul_rn(W, (double)__fmul_rn(yv, r)), h = __dmul_rn(W, (double)__fmul_rn(yv, yv));
+      if (c & 1)  // index 1::2 along dim_thick
+        ge += g, he += h;
+      else
+        go += g, ho += h;
+    }
+    pz += sz;
+    if (pz >= d.z) pz -= d.z, ++py;
+    py += sy;
+    if (py >= d.y) py -= d.y, ++px;  // (py + carry + sy <= 2 dy - 1: once)
+    px += sx;
+  }
+  const double v[5] = {block_sum(s0), block_sum(ge), block_sum(go), block_sum(he), block_sum(ho)};
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 5; ++k) part[5 * blockIdx.x + k] = v[k];
+}
+
 int scaling_sums_blocks(Dim3i d) {
   size_t b = (d.numel() + kBlock - 1) / kBlock;
   return (int)(b > (size_t)kScalingBlocks ? (size_t)kScalingBlocks : b);
+}
+
+// part as launch_scaling_sums'; g: a volume d of voxel weights; u: d[dim_thick] slice weights on the device, or nullptr
+void launch_scaling_sums_g(const float *x, const float *y, const float *g, Dim3i d, int dim_thick, const float *u,
+                           double *part, double *out, hipStream_t st) {
+  const int nb = scaling_sums_blocks(d);
+  if (u)
+    hipLaunchKernelGGL(k_scaling_sums_g<true>, dim3(nb), dim3(kBlock), 0, st, x, y, g, d, dim_thick, u, part);
+  else
+    hipLaunchKernelGGL(k_scaling_sums_g<false>, dim3(nb), dim3(kBlock), 0, st, x, y, g, d, dim_thick, u, part);
+  launch_sum_cols(part, nb, 5, out, st);
 }
 
 // part: 5 * scaling_sums_blocks(d) doubles of scratch; u: d[dim_thick] slice weights on the device, or nullptr (= 1)

@@ -21,6 +21,10 @@ int scaling_sums_blocks(Dim3i d);
 // slice weights on the device (every term times the weight of its slice), or nullptr (= 1)
 void launch_scaling_sums(const float *x, const float *y, Dim3i d, int dim_thick, const float *u, double *part,
                          double *out, hipStream_t st);
+// The same with per-voxel weights g (a volume d): every term times g(v), or g(v) u[s(v)] where u is given - the weight
+// formed in float64, the sums in launch_scaling_sums' order (g = 1: its bits)
+void launch_scaling_sums_g(const float *x, const float *y, const float *g, Dim3i d, int dim_thick, const float *u,
+                           double *part, double *out, hipStream_t st);
 int rigid_sums_blocks(Dim3i dm);
 // part: 27 * rigid_sums_blocks(dm) doubles of scratch
 void launch_rigid_sums(const float *gr3, const float *diff, const float *ctc, Dim3i dm,

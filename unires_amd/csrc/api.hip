@@ -469,6 +469,19 @@ extern "C" int unires_scaling_sums_w(const float *x, const float *ay, const int3
   return UNIRES_OK;
 }
 
+extern "C" int unires_scaling_sums_g(const float *x, const float *ay, const int32_t dim[3], int32_t dim_thick,
+                                     const float *g_dev, const float *u_dev, double *out_dev, void *stream) {
+  if (!x || !ay || !dim || !g_dev || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (dim_thick < 0 || dim_thick > 2) return fail(UNIRES_ERR_ARG, "bad dim_thick");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  if (int rc = reduce_scratch(st, 5 * (size_t)scaling_sums_blocks(mk(dim)), &part)) return rc;
+  launch_scaling_sums_g(x, ay, g_dev, mk(dim), dim_thick, u_dev, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 extern "C" int unires_rigid_sums(const float *gr3, const float *diff, const float *ctc,
                                  const int32_t dim[3], const float d_rigid[72], double *out_dev,
                                  void *stream) {
@@ -561,6 +574,17 @@ extern "C" int unires_rigid_resid(const float *x, const float *ay, const int32_t
   if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
   if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
   launch_rigid_resid(x, ay, out, u_dev, mk(dim), axis, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_rigid_resid_g(const float *x, const float *ay, const float *g, const int32_t dim[3], int32_t axis,
+                                    const float *u_dev, float *out, void *stream) {
+  if (!x || !ay || !g || !dim || !out) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
+  if (out == g) return fail(UNIRES_ERR_ARG, "out must not be g: the weights are only read");
+  launch_rigid_resid_g(x, ay, g, out, u_dev, mk(dim), axis, (hipStream_t)stream);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

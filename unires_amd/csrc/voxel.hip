@@ -7,6 +7,8 @@
 //   k_voxel_sums_rows / k_voxel_sums_z + k_voxel_finish: sum g (x - A y)^2 and sum g of every slice, the one statement
 //     of a voxel-weighted repeat's data term.  Not on any solve's path.
 //   k_voxel_huber: g = prior . h, h the Huber weight of the residual.  One streaming pass, no reduction.
+//   k_rigid_resid_g: g [u[s(v)]] (A y - x), masked - the residual of the rigid Gauss-Newton step on the same data term
+//     (the five sums of the scaling step on it are k_scaling_sums_g, admm.hip).
 #include <algorithm>
 
 #include "slice.hpp"
@@ -222,7 +224,99 @@ __global__ void __launch_bounds__(kBlock) k_voxel_huber(const float *__restrict_
   for (size_t e = 4 * n4 + tid; e < n; e += step) g_out[e] = huber_term(x[e], ay[e], PRIOR ? prior[e] : 1.f, c);
 }
 
+// one voxel of the rigid step's residual on the voxel-weighted data term: g [u] (ay - x) where both are non-zero
+// (_rigid_terms' mask), else +0; the product rounds as k_voxel_apply's: g u exact in float64, times the float32
+// difference, one rounding to float32 - or one float32 product where there is no u
+template <bool SLICE>
+__device__ __forceinline__ float resid_term_g(float xv, float av, float gv, float uv) {
+  if (!(xv != 0.f && av != 0.f)) return 0.f;
+  const float r = __fsub_rn(av, xv);
+  return SLICE ? (float)(((double)gv * (double)uv) * (double)r) : __fmul_rn(gv, r);
+}
+
+// out = g [u[s(v)]] (ay - x), masked: k_rigid_resid (slice.hip) with the voxel weights read beside x and ay - 16-byte
+// loads of all three and 16-byte stores whatever the row length; with SLICE (i, j, k) of a thread's group of four kept
+// by carry arithmetic and a group that crosses a row end stepped through voxel by voxel, without it no position at all;
+// the voxels from 4 n4 on one by one (n4 = 0 for a buffer off its boundary).  g = 1 gives k_rigid_resid's bits: g u r
+// is then u r, exact in float64 and rounded once, as __fmul_rn(u, r) is.  out may be ay: a thread reads its group
+// before it stores it, and no other thread touches the group.  x and g are only read.
+template <bool SLICE>
+__global__ void __launch_bounds__(kBlock) k_rigid_resid_g(const float *__restrict__ x, const float *ay,
+                                                          const float *__restrict__ g, float *out,
+                                                          const float *__restrict__ u, Dim3i d, int axis, int si, int sj,
+                                                          int sk, size_t n4, size_t n) {
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, step = (size_t)gridDim.x * kBlock;
+  const size_t plane = (size_t)d.y * d.z;
+  const auto weight = [&](int i, int j, int k) { return SLICE ? u[axis == 0 ? i : (axis == 1 ? j : k)] : 1.f; };
+  if (tid < n4) {
+    int i = 0, j = 0, k = 0;
+    if (SLICE) {
+      const size_t e0 = 4 * tid;
+      if (n <= 0xffffffffull) {  // (uniform: the usual case, without 64-bit divisions)
+        const unsigned e = (unsigned)e0, pl = (unsigned)plane, r = e / (unsigned)d.z;
+        i = (int)(e / pl), j = (int)(r - (unsigned)i * (unsigned)d.y), k = (int)(e - r * (unsigned)d.z);
+      } else {
+        i = (int)(e0 / plane), j = (int)((e0 % plane) / d.z), k = (int)(e0 % d.z);
+      }
+    }
+    for (size_t q = tid; q < n4; q += step) {
+      float w[4] = {1.f, 1.f, 1.f, 1.f};
+      if (SLICE) {
+        if (axis != 2 && k + 3 < d.z) {  // (axes 0 and 1: the weight is uniform over a z-row, and the group stays in its row)
+          w[0] = w[1] = w[2] = w[3] = weight(i, j, k);
+        } else {
+          int ie = i, je = j, ke = k;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            w[e] = weight(ie, je, ke);
+            if (++ke == d.z) {
+              ke = 0;
+              if (++je == d.y) je = 0, ++ie;
+            }
+          }
+        }
+      }
+      const float4 xv = *reinterpret_cast<const float4 *>(x + 4 * q);
+      const float4 av = *reinterpret_cast<const float4 *>(ay + 4 * q);
+      const float4 gv = *reinterpret_cast<const float4 *>(g + 4 * q);
+      float4 v;
+      v.x = resid_term_g<SLICE>(xv.x, av.x, gv.x, w[0]), v.y = resid_term_g<SLICE>(xv.y, av.y, gv.y, w[1]);
+      v.z = resid_term_g<SLICE>(xv.z, av.z, gv.z, w[2]), v.w = resid_term_g<SLICE>(xv.w, av.w, gv.w, w[3]);
+      *reinterpret_cast<float4 *>(out + 4 * q) = v;
+      if (SLICE) {
+        k += sk;
+        if (k >= d.z) k -= d.z, ++j;
+        j += sj;
+        if (j >= d.y) j -= d.y, ++i;  // (j + carry + sj <= 2 dy - 1: once)
+        i += si;
+      }
+    }
+  }
+  for (size_t e = 4 * n4 + tid; e < n; e += step)
+    out[e] = resid_term_g<SLICE>(x[e], ay[e], g[e],
+                                 weight((int)(e / plane), (int)((e % plane) / d.z), (int)(e % d.z)));
+}
+
 }  // namespace
+
+void launch_rigid_resid_g(const float *x, const float *ay, const float *g, float *out, const float *u, Dim3i d, int axis,
+                          hipStream_t st) {
+  const size_t n = d.numel();
+  if (!n) return;
+  const bool aligned = (((uintptr_t)x | (uintptr_t)ay | (uintptr_t)g | (uintptr_t)out) & 15) == 0;
+  const size_t n4 = aligned ? n / 4 : 0;
+  // launch_slice_apply's grid and stride decode
+  const size_t work = aligned ? n4 + 3 : n;
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((work + kBlock - 1) / kBlock, 2048));
+  const size_t se = 4 * blocks * kBlock, plane = (size_t)d.y * d.z;
+  const int si = (int)(se / plane), sj = (int)((se % plane) / d.z), sk = (int)(se % d.z);
+  if (u)
+    hipLaunchKernelGGL(k_rigid_resid_g<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, g, out, u, d, axis, si,
+                       sj, sk, n4, n);
+  else
+    hipLaunchKernelGGL(k_rigid_resid_g<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, g, out, u, d, axis, si,
+                       sj, sk, n4, n);
+}
 
 void launch_voxel_apply(const float *src, float *dst, const float *g, const uint8_t *mask, const float *u, Dim3i d,
                         int axis, bool flip, const int *done, hipStream_t st) {

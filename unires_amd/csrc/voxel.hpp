@@ -23,6 +23,12 @@ void launch_voxel_permute(const float *g_u, const Orient &O, Dim3i du, float *g,
 void launch_voxel_sums(const float *x, const float *ay, const float *g, Dim3i d, int axis, double *part, double *out,
                        hipStream_t st);
 
+// The x-space residual of the rigid Gauss-Newton step on the voxel-weighted data term: out[v] = g[v] [u[s(v)]] *
+// (ay[v] - x[v]) where x[v] != 0 and ay[v] != 0, else +0; launch_voxel_apply's rounding.  u == nullptr: no slice weights.
+// g = 1 gives launch_rigid_resid's bits (slice.hpp).  out == ay is allowed; x and g are only read.
+void launch_rigid_resid_g(const float *x, const float *ay, const float *g, float *out, const float *u, Dim3i d, int axis,
+                          hipStream_t st);
+
 // g_out[v] = (prior ? prior[v] : 1) * h(v); h = 1 where x == 0 or |x - ay| <= c, else c / |x - ay|.  g_out may be prior.
 void launch_voxel_huber(const float *x, const float *ay, const float *prior, float c, size_t n, float *g_out,
                         hipStream_t st);

@@ -82,8 +82,8 @@ def _init_voxel_weights(x, sett, dev):
     observation's shape, real, finite, >= 0 - the one read-back) and moved to the device as contiguous float32.  With
     ``sett.voxel_robust`` a private clone of it is kept as the rule's prior (``xn._weight_prior``; None: ones) and
     every observation starts from its prior, or from ones where it has none, so that the plans' kernels do not change
-    mid-fit.  The scaling and rigid Gauss-Newton updates do not carry voxel weights yet: they are refused by name
-    rather than left to minimise another data term."""
+    mid-fit.  The scaling and rigid Gauss-Newton updates carry voxel weights only with ``sett.voxel_gn``: without it
+    they are refused by name rather than left to minimise another data term."""
     robust = bool(getattr(sett, 'voxel_robust', False))
     if robust and not float(getattr(sett, 'voxel_k', 3.0)) > 0:
         raise ValueError('sett.voxel_k must be positive')
@@ -112,11 +112,12 @@ def _init_voxel_weights(x, sett, dev):
                 xn.weight = xn._weight_prior.clone()
             else:
                 xn.weight = g
-    if any_w:
+    if any_w and not getattr(sett, 'voxel_gn', False):
         for name in ('scaling', 'unified_rigid'):
             if getattr(sett, name, False):
                 raise NotImplementedError('sett.%s with voxel weights (_input.weight, sett.voxel_robust): the '
-                                          'Gauss-Newton updates do not carry per-voxel weights' % name)
+                                          'Gauss-Newton updates carry per-voxel weights only where asked to - '
+                                          'set sett.voxel_gn' % name)
 
 
 @on_device
@@ -134,7 +135,12 @@ def fit(x, y, sett):
 
     Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
-    ``_update_rigid``).  Under ``sett.slice_robust`` they see the weights ``_update_admm`` has just re-estimated."""
+    ``_update_rigid``).  Under ``sett.slice_robust`` they see the weights ``_update_admm`` has just re-estimated.
+
+    Voxel weights define it likewise.  With ``sett.voxel_gn`` the two Gauss-Newton updates of a repeat that has voxel
+    weights take them too - beside its slice weights, where it has both - and under ``sett.voxel_robust`` they see the
+    weights ``_update_admm`` has just re-estimated.  Without ``sett.voxel_gn`` (the default) ``sett.scaling`` and
+    ``sett.unified_rigid`` are refused with voxel weights, by name."""
     if len(x) != len(y):
         raise ValueError('one output per channel')
     with torch.no_grad():

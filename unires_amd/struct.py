@@ -29,7 +29,8 @@ class _input:
         # per-voxel weights of the data term, float32 (X, Y, Z) like dat, >= 0: None - every voxel has weight 1.  Set
         # before fit() to distrust known voxels (a defect mask, a confidence map; fit() validates them once and moves
         # them to the device); with sett.voxel_robust they are the prior the Huber weights multiply, so a 0 stays 0.
-        # They enter the y-update and the objective; sett.scaling and sett.unified_rigid are refused with them
+        # They enter the y-update and the objective, and with sett.voxel_gn the scaling and rigid Gauss-Newton updates;
+        # without it sett.scaling and sett.unified_rigid are refused with them
         self.weight = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
@@ -106,6 +107,12 @@ class settings:
         # real data.  Off: every voxel has weight 1 unless the user set _input.weight.
         self.voxel_robust = False
         self.voxel_k = 3.0
+        # the scaling and rigid Gauss-Newton updates (sett.scaling, sett.unified_rigid) carry the voxel weights of every
+        # repeat that has some: both minimise the data term above (_update._update_scaling, _rigid._update_rigid).
+        # Off: fit() refuses those two settings with voxel weights, and the update functions ignore xn.weight, as they
+        # did before the updates could carry them.  A switch only because that refusal is pinned by a test; not a
+        # modelling choice - with voxel weights and either update, turn it on
+        self.voxel_gn = False
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
