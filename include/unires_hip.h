@@ -146,6 +146,59 @@ typedef struct {
  * point inside G adds 65536; a point whose image falls outside F counts as f = 0).  At most 2^31 - 1 sample points per job. */
 int unires_coreg_hist(int32_t n_jobs, const unires_coreg_job_t *jobs, uint64_t *hist, void *stream);
 
+/* Voxel weight maps in the initialisation: the support of a map - g(v) > 0 - decides
+ * which voxels the noise estimator, the coregistration and the first guess read.
+ *
+ * unires_noise_hist under weight maps.  gptrs: a HOST array of n_obs device pointers to float32 maps
+ * of the same sizes; an entry, or the array, may be NULL (that observation is read as by
+ * unires_noise_hist).  Voxels taken: those unires_noise_hist takes whose weight is > 0.  The 16-byte
+ * loads are used where an observation AND its map are 16-byte aligned. */
+int unires_noise_hist_g(int32_t n_obs, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
+                        const float *const *gptrs, uint32_t *counts, float *range, void *stream);
+
+/* unires_coreg_quantise under supports.  masks: a HOST array of n_obs device pointers to uint8
+ * supports of the same sizes (non-zero usable, 0 not); an entry, or the array, may be NULL.  min, max,
+ * the 1024-bin histogram and the robust maximum are those of the finite USABLE voxels; every finite
+ * voxel, usable or not, is converted with them (clamped to 0 .. 255).  Status 1: no finite usable
+ * voxel; 2: all of them equal. */
+int unires_coreg_quantise_m(int32_t n_obs, const float *const *ptrs, const int64_t *sizes,
+                            const uint8_t *const *masks, uint8_t *const *outs, uint32_t *counts,
+                            float *params, void *stream);
+
+/* Cell support of a uint8 support: cell[i0, i1, i2] = 1 iff the eight voxels (i0..i0+1, i1..i1+1,
+ * i2..i2+1) of mask are non-zero, for i_d <= dim_d - 2; the last plane of every axis (no cell
+ * starts there; unires_coreg_hist_m never reads it) is written 0.  cell has mask's shape and is
+ * not mask. */
+int unires_coreg_cellmask(const uint8_t *mask, const int32_t dim[3], uint8_t *cell, void *stream);
+
+/* unires_coreg_job_t, then the cell supports (unires_coreg_cellmask) of G and of F; either may be
+ * NULL. */
+typedef struct {
+  const uint8_t *G;
+  const uint8_t *F;
+  int32_t dim_g[3];
+  int32_t dim_f[3];
+  float M[12];
+  float step[3];
+  const uint8_t *mG;
+  const uint8_t *mF;
+} unires_coreg_job_m_t;
+
+/* unires_coreg_hist under cell supports.  The cell of a point is the one its interpolation reads,
+ * i_d = min(floor(x_d), dim_d - 2).  A sample point inside G whose G cell has mG == 0 adds nothing;
+ * neither does one whose image lies inside F in a cell with mF == 0.  A point whose image falls
+ * outside F counts as f = 0 whatever mF holds.  No voxel outside a support is interpolated into a
+ * counted sample. */
+int unires_coreg_hist_m(int32_t n_jobs, const unires_coreg_job_m_t *jobs, uint64_t *hist, void *stream);
+
+/* Support of unires_pull3d_affine(., sdim, M, ., gdim, fov_tol) under the weight map g (sdim,
+ * float32): dst[gdim] (uint8) = 1 iff the coordinate c = M (i,j,k) is inside the FOV by the pull's
+ * rule and every corner (floor(c_d) | floor(c_d) + 1 per axis) that lies inside the volume has
+ * g > 0; else 0.  Corners outside the volume add 0 to the pull and do not decide.  The coordinate is
+ * computed by the pull's own device code. */
+int unires_pull3d_support(const float *g, const int32_t sdim[3], const float M[12], uint8_t *dst,
+                          const int32_t gdim[3], float fov_tol, void *stream);
+
 /* Step 3: the cost of n histograms in one launch.  cost_fun: 0 'nmi', 1 'mi', 2 'ecc'; fwhm: the
  * histogram smoothing in bins (0 <= fwhm <= 16).  work: n x 2 x 256 x 256 float64 device scratch;
  * cost: (n,) float64 device. */

@@ -22,9 +22,38 @@ from .struct import _input, _output
 MAX_LABELS = 255  # the reference's limit (unires/_core.py:425)
 
 
+def _init_weight(xn, sett):
+    """The weight map ``init()`` honours for an observation: ``xn.weight`` with ``sett.voxel_init``, else None
+    (``xn.weight`` is not touched)."""
+    if sett is None or not getattr(sett, 'voxel_init', False):
+        return None
+    return getattr(xn, 'weight', None)
+
+
+def _check_init_weights(x, sett):
+    """With ``sett.voxel_init``: every ``x[c][n].weight`` becomes a contiguous float32 tensor on its observation's
+    device; a map that is not finite and >= 0 everywhere is a ValueError naming channel and repeat."""
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            g = _init_weight(xn, sett)
+            if g is None:
+                continue
+            g = torch.as_tensor(g)
+            if tuple(g.shape) != tuple(xn.dat.shape):
+                raise ValueError('voxel_init: the weight map of channel %d, repeat %d has shape %s, its observation %s'
+                                 % (c, n, tuple(g.shape), tuple(xn.dat.shape)))
+            g = g.to(device=xn.dat.device, dtype=torch.float32).contiguous()
+            if not bool((torch.isfinite(g) & (g >= 0)).all()):
+                raise ValueError('voxel_init: the weight map of channel %d, repeat %d must be finite and >= 0' % (c, n))
+            xn.weight = g
+    return x
+
+
 def _init_y_dat(x, y, sett=None):
     """y[c].dat = mean over repeats of each input trilinearly resliced into the output
-    space (HIP pull with on-the-fly coordinates), clamped to the input's range."""
+    space (HIP pull with on-the-fly coordinates), clamped to the input's range.  With ``sett.voxel_init`` a repeat
+    with a weight map takes its range over the voxels of weight > 0 and gives a value only where its pull read no
+    other voxel (``_ops.pull_support``); an output voxel no repeat supports is 0."""
     dim_y = tuple(y[0].dim)
     mat_y = torch.as_tensor(y[0].mat).detach().to('cpu', torch.float64)
     for c in range(len(x)):
@@ -33,9 +62,14 @@ def _init_y_dat(x, y, sett=None):
             mat_x = torch.as_tensor(xn.mat).detach().to('cpu', torch.float64)
             mat = torch.linalg.solve(mat_x, mat_y)                 # mat_x \ mat_y
             dat = xn.dat
-            mn, mx = torch.min(dat), torch.max(dat)
+            g = _init_weight(xn, sett)
+            use = dat if g is None else dat[g > 0]
             res = _ops.pull_affine(dat, _m12(mat), dim_y)
-            res = torch.minimum(torch.maximum(res, mn), mx)
+            if use.numel() > 0:
+                mn, mx = torch.min(use), torch.max(use)
+                res = torch.minimum(torch.maximum(res, mn), mx)
+            if g is not None:  # (after the clamp: an unsupported voxel is 0 whatever the range)
+                res = torch.where(_ops.pull_support(g, _m12(mat), dim_y) != 0, res, torch.zeros_like(res))
             dat_y = res if dat_y is None else dat_y + res
             cnt = (res > 0).to(res.dtype)
             sm = cnt if sm is None else sm + cnt
@@ -119,17 +153,19 @@ def _estimate_hyperpar(x, sett):
     ``x[c][n].sd``, ``.tau = 1 / sd**2`` and ``.mu = |mean_fg - mean_bg|`` from a two-class mixture
     fit to the intensity histogram (``stats.estimate_noise``).  A non-CT observation
     keeps its voxels >= 0.  One histogram launch and one fit launch for all observations, one read
-    back.  The values are float32 CPU scalars, with the reference's ``.float()`` arithmetic."""
+    back.  The values are float32 CPU scalars, with the reference's ``.float()`` arithmetic.  With
+    ``sett.voxel_init`` an observation with a weight map is read only where the map is > 0."""
     obs = [(c, n) for c in range(len(x)) for n in range(len(x[c]))]
     if not obs:
         return x
-    counts, rng = stats.noise_hist([x[c][n].dat for c, n in obs], [bool(x[c][n].ct) for c, n in obs])
+    gs = [_init_weight(x[c][n], sett) for c, n in obs]  # (sett.voxel_init: only voxels of weight > 0; DESIGN 8.10)
+    counts, rng = stats.noise_hist([x[c][n].dat for c, n in obs], [bool(x[c][n].ct) for c, n in obs], gs)
     rows = stats.noise_fit(counts, rng).cpu()
-    for (c, n), row in zip(obs, rows):
+    for (c, n), row, g in zip(obs, rows, gs):
         if row[stats.MODEL] < 0:
             raise ValueError('_estimate_hyperpar: channel %d, repeat %d has no usable voxels '
-                             '(finite, non-zero%s) or all of them are equal'
-                             % (c, n, '' if x[c][n].ct else ', >= 0'))
+                             '(finite, non-zero%s%s) or all of them are equal'
+                             % (c, n, '' if x[c][n].ct else ', >= 0', '' if g is None else ', weight > 0'))
         prm_noise, prm_not_noise = stats._noise_params(row)
         sd_bg = prm_noise['sd'].float()
         x[c][n].sd = sd_bg
@@ -160,14 +196,19 @@ def _init_reg(x, sett):
     the observation of flat index ``sett.fix`` (``preproc.affine_align`` with
     ``sett.coreg_params``), ``sett.mat_coreg`` keeps the transforms and
     ``x[c][n].mat = mat_a[i] \\ x[c][n].mat``; every ``x[c][n].rigid_q`` is set to zeros(6).
-    Labels are not touched (they share their image's orientation).  Atlas alignment is not built."""
+    Labels are not touched (they share their image's orientation).  Atlas alignment is not built.
+    With ``sett.voxel_init`` the weight maps go along as cost-function masks (``affine_align(weights=)``)."""
     if sett.do_atlas_align:
         raise NotImplementedError('_init_reg: atlas alignment (do_atlas_align) is not built')
     N = sum(len(xc) for xc in x)
     sett.rigid_basis = affine_basis(group='SE', dtype=torch.float64)
     if sett.do_coreg and N > 1:
         imgs = [[x[c][n].dat, x[c][n].mat] for c in range(len(x)) for n in range(len(x[c]))]
-        mat_a = preproc.affine_align(imgs, **sett.coreg_params, fix=sett.fix, device=sett.device)[1]
+        gs = [_init_weight(x[c][n], sett) for c in range(len(x)) for n in range(len(x[c]))]
+        if any(g is not None for g in gs):  # (sett.voxel_init: cost-function masking; DESIGN 8.10)
+            mat_a = preproc.affine_align(imgs, **sett.coreg_params, fix=sett.fix, device=sett.device, weights=gs)[1]
+        else:
+            mat_a = preproc.affine_align(imgs, **sett.coreg_params, fix=sett.fix, device=sett.device)[1]
         sett.mat_coreg = mat_a
         i = 0
         for c in range(len(x)):

@@ -52,6 +52,15 @@ SIGNATURES = {
     'unires_coreg_hist': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'unires_coreg_cost': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    'unires_noise_hist_g': (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_coreg_quantise_m': (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    'unires_coreg_cellmask': (C.c_int, [C.c_void_p, c_i32x3, C.c_void_p, C.c_void_p]),
+    'unires_coreg_hist_m': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_pull3d_support': (C.c_int, [C.c_void_p, c_i32x3, c_f32x12, C.c_void_p, c_i32x3,
+                                        C.c_float, C.c_void_p]),
     'unires_pull_grad3d_affine': (C.c_int, [C.c_void_p, c_i32x3, c_f32x12, C.c_void_p, c_i32x3,
                                             C.c_float, C.c_void_p]),
     'unires_push3d_affine': (C.c_int, [C.c_void_p, c_i32x3, c_f32x12, C.c_void_p, c_i32x3,

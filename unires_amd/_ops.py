@@ -103,6 +103,18 @@ def pull_nearest(src, M, gdim, fov_tol=FOV_TOL):
 
 
 @on_device
+def pull_support(g, M, gdim, fov_tol=FOV_TOL):
+    """Support of ``pull_affine(., M, gdim)`` under the weight map ``g`` (float32, the source's shape):
+    a uint8 volume, 1 where the sample is inside the FOV and every corner of it inside the volume has
+    g > 0 - there the pull reads no voxel outside the map's support."""
+    s, lead = _vol(g, 'g')
+    out = torch.empty(tuple(gdim), dtype=torch.uint8, device=s.device)
+    check(_lib.load().unires_pull3d_support(_ptr(s), i3(s.shape), f12(M), _ptr(out), i3(gdim),
+                                            fov_tol, _stream()))
+    return out.reshape(lead + tuple(gdim))
+
+
+@on_device
 def warp_label(label, M, gdim, fov_tol=FOV_TOL):
     """The reference's label vote in one pass: per output voxel, the value u of ``label`` whose
     indicator (label == u) has the highest linear pull; ties go to the smallest value, a best of 0

@@ -6,6 +6,7 @@
 // hipStream_t.
 #include <float.h>
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <map>
@@ -162,6 +163,42 @@ extern "C" int unires_noise_hist(int32_t n_obs, const float *const *ptrs, const 
   return UNIRES_OK;
 }
 
+extern "C" int unires_pull3d_support(const float *g, const int32_t sdim[3], const float M[12], uint8_t *dst,
+                                     const int32_t gdim[3], float fov_tol, void *stream) {
+  if (!g || !dst || !sdim || !gdim || !M) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(sdim) || !dims_ok(gdim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  Affine A;
+  memcpy(A.m, M, sizeof(A.m));
+  launch_pull_support(g, mk(sdim), A, dst, mk(gdim), fov_tol, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_noise_hist_g(int32_t n_obs, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
+                                   const float *const *gptrs, uint32_t *counts, float *range, void *stream) {
+  if (!ptrs || !sizes || !ct || !counts || !range) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
+  size_t blocks = 0;
+  for (int32_t o = 0; o < n_obs; ++o) {
+    if (!ptrs[o]) return fail(UNIRES_ERR_NULL, "null observation pointer");
+    if (sizes[o] < 1 || sizes[o] > (int64_t)UINT32_MAX) return fail(UNIRES_ERR_DIM, "observation size out of range");
+    blocks += (size_t)noise_hist_blocks(sizes[o]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;  // one (min, max) float pair per workgroup
+  if (int rc = reduce_scratch(st, blocks, &part)) return rc;
+  HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_obs * kNoiseBins * sizeof(uint32_t), st));
+  for (int32_t o = 0; o < n_obs; o += kNoiseMaxObs) {
+    const int n = std::min<int32_t>(kNoiseMaxObs, n_obs - o);
+    size_t off = 0;
+    for (int32_t q = 0; q < o; ++q) off += (size_t)noise_hist_blocks(sizes[q]);
+    launch_noise_hist_g(n, ptrs + o, sizes + o, ct + o, gptrs ? gptrs + o : nullptr, reinterpret_cast<float *>(part + off),
+                        counts + (size_t)o * kNoiseBins, range + 2 * (size_t)o, noise_hist_form(), st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
 extern "C" int unires_noise_fit(int32_t n_obs, const uint32_t *counts, const float *range,
                                 int32_t max_iter, double *out, void *stream) {
   if (!counts || !range || !out) return fail(UNIRES_ERR_NULL, "null argument");
@@ -210,6 +247,61 @@ extern "C" int unires_coreg_hist(int32_t n_jobs, const unires_coreg_job_t *jobs,
   for (int32_t o = 0; o < n_jobs; o += kCoregMaxJobs) {
     const int n = std::min<int32_t>(kCoregMaxJobs, n_jobs - o);
     launch_coreg_hist(n, J + o, hist + (size_t)o * kCoregBins * kCoregBins, st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_quantise_m(int32_t n_obs, const float *const *ptrs, const int64_t *sizes,
+                                       const uint8_t *const *masks, uint8_t *const *outs, uint32_t *counts,
+                                       float *params, void *stream) {
+  if (!ptrs || !sizes || !outs || !counts || !params) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_obs < 1) return fail(UNIRES_ERR_ARG, "n_obs must be >= 1");
+  for (int32_t o = 0; o < n_obs; ++o) {
+    if (!ptrs[o] || !outs[o]) return fail(UNIRES_ERR_NULL, "null observation pointer");
+    if (sizes[o] < 1 || sizes[o] > (int64_t)UINT32_MAX) return fail(UNIRES_ERR_DIM, "observation size out of range");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int32_t o = 0; o < n_obs; o += kCoregMaxObs) {
+    const int n = std::min<int32_t>(kCoregMaxObs, n_obs - o);
+    launch_coreg_quantise_m(n, ptrs + o, sizes + o, masks ? masks + o : nullptr, outs + o,
+                            counts + (size_t)o * kCoregQBins, params + (size_t)o * kCoregQOut, st);
+    CHECK_LAUNCH();
+  }
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_cellmask(const uint8_t *mask, const int32_t dim[3], uint8_t *cell, void *stream) {
+  if (!mask || !dim || !cell) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+  if (mask == cell) return fail(UNIRES_ERR_ARG, "cellmask cannot run in place");
+  launch_coreg_cellmask(mask, dim, cell, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_coreg_hist_m(int32_t n_jobs, const unires_coreg_job_m_t *jobs, uint64_t *hist, void *stream) {
+  static_assert(sizeof(unires_coreg_job_m_t) == sizeof(CoregJobMHost), "job layout");
+  static_assert(offsetof(unires_coreg_job_m_t, mG) == offsetof(CoregJobMHost, mG), "job layout");
+  if (!jobs || !hist) return fail(UNIRES_ERR_NULL, "null argument");
+  if (n_jobs < 1) return fail(UNIRES_ERR_ARG, "n_jobs must be >= 1");
+  const CoregJobMHost *J = reinterpret_cast<const CoregJobMHost *>(jobs);
+  for (int32_t o = 0; o < n_jobs; ++o) {
+    const CoregJobHost &j = J[o].job;
+    if (!j.G || !j.F) return fail(UNIRES_ERR_NULL, "null volume pointer");
+    for (int d = 0; d < 3; ++d) {
+      if (j.dim_g[d] < 2 || j.dim_f[d] < 2) return fail(UNIRES_ERR_DIM, "every dimension must be >= 2");
+      if (!(j.step[d] > 0.f) || !(j.step[d] <= 3.0e38f)) return fail(UNIRES_ERR_ARG, "step must be finite and > 0");
+    }
+    if (!dims_ok(j.dim_g) || !dims_ok(j.dim_f)) return fail(UNIRES_ERR_DIM, "bad dimensions");
+    int32_t ng[3];
+    if (coreg_grid(j, ng) > (int64_t)INT32_MAX) return fail(UNIRES_ERR_DIM, "more than 2^31 - 1 sample points");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)n_jobs * kCoregBins * kCoregBins * sizeof(uint64_t), st));
+  for (int32_t o = 0; o < n_jobs; o += kCoregMaxJobs) {
+    const int n = std::min<int32_t>(kCoregMaxJobs, n_jobs - o);
+    launch_coreg_hist_m(n, J + o, hist + (size_t)o * kCoregBins * kCoregBins, st);
     CHECK_LAUNCH();
   }
   return UNIRES_OK;

@@ -12,6 +12,11 @@
 //                  halves interpolate G; only the owner of g gathers F, and a point outside F counts
 //                  as f = 0 (every point inside G is counted).  The background bin pair
 //                  (g = 0, f in {0, 1}) is counted in per-lane registers.
+//   k_coreg_qrange_m / k_coreg_qhist_m / k_coreg_cellmask / k_coreg_hist_m
+//                  the same under supports: range, histogram and robust maximum over the
+//                  usable voxels; a joint histogram that drops every sample point whose interpolation
+//                  cell in G, or in F when its image is inside F, holds an unusable voxel - one byte
+//                  per image per point, from cell supports built once per level.
 //   k_coreg_cost   one workgroup per histogram: float64 smoothing, normalisation, marginals and
 //                  entropies with a fixed reduction order, one cost per histogram.
 #include <float.h>
@@ -215,6 +220,106 @@ __global__ void __launch_bounds__(kCoregQBlock) k_coreg_quant(QBatch B, const fl
   }
 }
 
+// ---- quantisation under supports ---------------------------------------------------
+// The range and the robust-maximum histogram read the finite voxels whose support byte is non-zero;
+// k_coreg_qinit, k_coreg_qparam and k_coreg_quant run as above (every finite voxel is converted).
+struct QBatchM {
+  QBatch B;
+  const uint8_t *m[kCoregMaxObs];  // null: every voxel is usable
+};
+
+__global__ void __launch_bounds__(kCoregQBlock) k_coreg_qrange_m(QBatchM Q, float *__restrict__ params) {
+  __shared__ float s_lo[kCoregQBlock / kWave], s_hi[kCoregQBlock / kWave];
+  const QBatch &B = Q.B;
+  const int o = qobs_of(B, blockIdx.x);
+  const int blk = blockIdx.x - B.blk0[o], nb = B.blk0[o + 1] - B.blk0[o];
+  float lo = INFINITY, hi = -INFINITY;
+  const float *p = B.p[o];
+  const uint8_t *m = Q.m[o];
+  for (int64_t i = (int64_t)blk * kCoregQBlock + threadIdx.x; i < B.n[o]; i += (int64_t)nb * kCoregQBlock) {
+    const float v = p[i];
+    if (finite(v) && (!m || m[i])) {
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+    }
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, off, kWave));
+    hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
+  }
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (lane == 0) {
+    s_lo[wave] = lo;
+    s_hi[wave] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kCoregQBlock / kWave; ++w) {
+      lo = fminf(lo, s_lo[w]);
+      hi = fmaxf(hi, s_hi[w]);
+    }
+    if (lo <= hi) {  // this workgroup saw a finite usable voxel
+      uint32_t *k = qkeys(params, o);
+      atomicMin(k, fkey(lo));
+      atomicMax(k + 1, fkey(hi));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kCoregQBlock)
+    k_coreg_qhist_m(QBatchM Q, const float *__restrict__ params, uint32_t *__restrict__ counts) {
+  __shared__ uint32_t h[kCoregQBins];
+  const QBatch &B = Q.B;
+  const int o = qobs_of(B, blockIdx.x);
+  const int blk = blockIdx.x - B.blk0[o], nb = B.blk0[o + 1] - B.blk0[o];
+  const uint32_t *k = reinterpret_cast<const uint32_t *>(params + (size_t)o * kCoregQOut + kCqKeyLo);
+  const uint32_t klo = k[0], khi = k[1];
+  if (klo == 0xffffffffu) return;  // no finite usable voxel
+  const float lo = funkey(klo), hi = funkey(khi);
+  if (!(hi > lo)) return;
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const double mn = lo, width = (double)hi - (double)lo;
+  const float *p = B.p[o];
+  const uint8_t *m = Q.m[o];
+  for (int64_t i = (int64_t)blk * kCoregQBlock + threadIdx.x; i < B.n[o]; i += (int64_t)nb * kCoregQBlock) {
+    const float v = p[i];
+    const bool ok = finite(v) && (!m || m[i]);
+    int bin = 0;
+    if (ok) bin = min((int)((((double)v - mn) * (double)kCoregQBins) / width), kCoregQBins - 1);
+    if (ok) {  // lanes that share the first active lane's bin add once (background pile-ups)
+      const int b0 = __builtin_amdgcn_readfirstlane(bin);
+      const uint64_t same = __ballot(bin == b0);
+      if (bin == b0) {
+        if ((int)__lane_id() == __ffsll((unsigned long long)same) - 1) atomicAdd(h + b0, (uint32_t)__popcll(same));
+      } else {
+        atomicAdd(h + bin, 1u);
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t c = h[threadIdx.x];
+  if (c) atomicAdd(counts + (size_t)o * kCoregQBins + threadIdx.x, c);
+}
+
+// cell[i0, i1, i2] = 1 iff the eight voxels (i0..i0+1, i1..i1+1, i2..i2+1) of mask are all non-zero, for
+// i_d <= dim_d - 2; the last plane of every axis has no cell and is written 0.  One thread per voxel.
+__global__ void __launch_bounds__(256)
+    k_coreg_cellmask(const uint8_t *__restrict__ mask, int32_t d0, int32_t d1, int32_t d2, uint8_t *__restrict__ cell) {
+  const size_t n = (size_t)d0 * d1 * d2;
+  const size_t s1 = (size_t)d2, s0 = (size_t)d1 * d2;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int32_t i2 = (int32_t)(i % s1), i1 = (int32_t)((i / s1) % (size_t)d1), i0 = (int32_t)(i / s0);
+    uint8_t c = 0;
+    if (i0 + 1 < d0 && i1 + 1 < d1 && i2 + 1 < d2) {
+      const uint8_t *p = mask + i;
+      c = (p[0] && p[1] && p[s1] && p[s1 + 1] && p[s0] && p[s0 + 1] && p[s0 + s1] && p[s0 + s1 + 1]) ? 1 : 0;
+    }
+    cell[i] = c;
+  }
+}
+
 // ---- joint histograms --------------------------------------------------------------------------
 struct HJob {
   const uint8_t *G;
@@ -285,6 +390,89 @@ __global__ void __launch_bounds__(kCoregBlock) k_coreg_hist(HBatch B, uint64_t *
     const bool in_f = inside(y0, J.df[0]) && inside(y1, J.df[1]) && inside(y2, J.df[2]);
     const int g = min((int)rintf(tri_u8(J.G, J.dg, x0, x1, x2)), kCoregBins - 1);
     if (g < g_lo || g >= g_lo + kHalf) continue;
+    const float f = in_f ? fminf(tri_u8(J.F, J.df, y0, y1, y2), 255.f) : 0.f;
+    const int fl = (int)floorf(f);
+    const uint32_t whi = (uint32_t)rintf((f - (float)fl) * 65536.f), wlo = 65536u - whi;
+    if (g == 0 && fl == 0) {
+      r00 += wlo;
+      r01 += whi;
+      continue;
+    }
+    uint32_t *row = h + (g - g_lo) * kCoregBins;
+    if (wlo) atomicAdd(row + fl, wlo);
+    if (fl < kCoregBins - 1 && whi) atomicAdd(row + fl + 1, whi);
+  }
+  if (half == 0) {  // at most kCoregChunk points x 65536 < 2^32 per workgroup
+    r00 = wave_sum_u32(r00);
+    r01 = wave_sum_u32(r01);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      if (r00) atomicAdd(h, r00);
+      if (r01) atomicAdd(h + 1, r01);
+    }
+  }
+  __syncthreads();
+  unsigned long long *out = reinterpret_cast<unsigned long long *>(hist) + (size_t)o * kCoregBins * kCoregBins +
+                            (size_t)g_lo * kCoregBins;
+  for (int i = threadIdx.x; i < kHalf * kCoregBins; i += kCoregBlock) {
+    const uint32_t c = h[i];
+    if (c) atomicAdd(out + i, (unsigned long long)c);
+  }
+}
+
+// ---- joint histograms under cell supports -------------------------------------------
+struct HJobM {
+  HJob j;
+  const uint8_t *mG;  // cell supports (k_coreg_cellmask) of G's / F's shape; null: every cell is usable
+  const uint8_t *mF;
+};
+
+struct HBatchM {
+  HJobM j[kCoregMaxJobs];
+  int32_t blk0[kCoregMaxJobs + 1];
+  int32_t njobs;
+};
+
+// the support byte of the cell tri_u8 reads at x: i_d = min(floor(x_d), dim_d - 2)
+__device__ __forceinline__ bool cell_ok(const uint8_t *__restrict__ m, const int32_t *d, float x0, float x1, float x2) {
+  const int i0 = min((int)floorf(x0), d[0] - 2), i1 = min((int)floorf(x1), d[1] - 2), i2 = min((int)floorf(x2), d[2] - 2);
+  return m[((int64_t)i0 * d[1] + i1) * d[2] + i2] != 0;
+}
+
+// k_coreg_hist with the drop rule: a sample point whose G cell is not supported adds nothing (decided
+// before the ownership test, so both halves drop the same points); neither does a point whose image
+// lies inside F in an unsupported F cell.  A point whose image is outside F counts with f = 0.
+__global__ void __launch_bounds__(kCoregBlock) k_coreg_hist_m(HBatchM B, uint64_t *__restrict__ hist) {
+  __shared__ uint32_t h[kHalf * kCoregBins];
+  __shared__ float s_jit[kCoregJitter];
+  int o = 0;
+  while (o + 1 < B.njobs && (int)blockIdx.x >= B.blk0[o + 1]) ++o;
+  const HJob &J = B.j[o].j;
+  const uint8_t *mG = B.j[o].mG, *mF = B.j[o].mF;
+  const int local = blockIdx.x - B.blk0[o], half = local & 1, chunk = local >> 1;
+  const int g_lo = half * kHalf;
+  for (int i = threadIdx.x; i < kHalf * kCoregBins; i += kCoregBlock) h[i] = 0;
+  if (threadIdx.x < kCoregJitter) s_jit[threadIdx.x] = kJitter.t[threadIdx.x];
+  __syncthreads();
+  const int p0 = chunk * kCoregChunk, p1 = min(J.npts, p0 + kCoregChunk);
+  const uint32_t ng1 = J.ng[1], ng2 = J.ng[2];
+  uint32_t r00 = 0, r01 = 0;  // background pair (g = 0, f = 0 | 1), half 0 only
+  for (int64_t p = p0 + (int64_t)threadIdx.x; p < p1; p += kCoregBlock) {
+    const uint32_t up = (uint32_t)p;
+    const uint32_t i2 = up % ng2, t = up / ng2, i1 = t % ng1, i0 = t / ng1;
+    const int k0 = (int)((3u * (up % (uint32_t)kCoregJitter)) % (uint32_t)kCoregJitter);
+    const int k1 = k0 + 1 == kCoregJitter ? 0 : k0 + 1, k2 = k1 + 1 == kCoregJitter ? 0 : k1 + 1;
+    const float x0 = ((float)i0 + s_jit[k0]) * J.s[0];
+    const float x1 = ((float)i1 + s_jit[k1]) * J.s[1];
+    const float x2 = ((float)i2 + s_jit[k2]) * J.s[2];
+    if (!(inside(x0, J.dg[0]) && inside(x1, J.dg[1]) && inside(x2, J.dg[2]))) continue;
+    if (mG && !cell_ok(mG, J.dg, x0, x1, x2)) continue;
+    const float y0 = ((J.M[0] * x0 + J.M[1] * x1) + J.M[2] * x2) + J.M[3];
+    const float y1 = ((J.M[4] * x0 + J.M[5] * x1) + J.M[6] * x2) + J.M[7];
+    const float y2 = ((J.M[8] * x0 + J.M[9] * x1) + J.M[10] * x2) + J.M[11];
+    const bool in_f = inside(y0, J.df[0]) && inside(y1, J.df[1]) && inside(y2, J.df[2]);
+    const int g = min((int)rintf(tri_u8(J.G, J.dg, x0, x1, x2)), kCoregBins - 1);
+    if (g < g_lo || g >= g_lo + kHalf) continue;
+    if (in_f && mF && !cell_ok(mF, J.df, y0, y1, y2)) continue;
     const float f = in_f ? fminf(tri_u8(J.F, J.df, y0, y1, y2), 255.f) : 0.f;
     const int fl = (int)floorf(f);
     const uint32_t whi = (uint32_t)rintf((f - (float)fl) * 65536.f), wlo = 65536u - whi;
@@ -474,6 +662,59 @@ void launch_coreg_hist(int n, const CoregJobHost *jobs, uint64_t *hist, hipStrea
   }
   B.blk0[n] = nb;
   hipLaunchKernelGGL(k_coreg_hist, dim3(nb), dim3(kCoregBlock), 0, st, B, hist);
+}
+
+void launch_coreg_quantise_m(int n, const float *const *ptrs, const int64_t *sizes, const uint8_t *const *masks,
+                             uint8_t *const *outs, uint32_t *counts, float *params, hipStream_t st) {
+  QBatchM Q{};
+  QBatch &B = Q.B;
+  B.nobs = n;
+  int nb = 0;
+  for (int o = 0; o < n; ++o) {
+    B.p[o] = ptrs[o];
+    B.u[o] = outs[o];
+    Q.m[o] = masks ? masks[o] : nullptr;
+    B.n[o] = sizes[o];
+    B.blk0[o] = nb;
+    nb += coreg_quant_blocks(sizes[o]);
+  }
+  B.blk0[n] = nb;
+  hipLaunchKernelGGL(k_coreg_qinit, dim3(n), dim3(kCoregQBlock), 0, st, counts, params);
+  hipLaunchKernelGGL(k_coreg_qrange_m, dim3(nb), dim3(kCoregQBlock), 0, st, Q, params);
+  hipLaunchKernelGGL(k_coreg_qhist_m, dim3(nb), dim3(kCoregQBlock), 0, st, Q, (const float *)params, counts);
+  hipLaunchKernelGGL(k_coreg_qparam, dim3(n), dim3(kCoregQBins), 0, st, (const uint32_t *)counts, params);
+  hipLaunchKernelGGL(k_coreg_quant, dim3(nb), dim3(kCoregQBlock), 0, st, B, (const float *)params);
+}
+
+void launch_coreg_cellmask(const uint8_t *mask, const int32_t dim[3], uint8_t *cell, hipStream_t st) {
+  const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+  const int nb = (int)std::min<size_t>((n + 255) / 256, 65536);
+  hipLaunchKernelGGL(k_coreg_cellmask, dim3(nb), dim3(256), 0, st, mask, dim[0], dim[1], dim[2], cell);
+}
+
+void launch_coreg_hist_m(int n, const CoregJobMHost *jobs, uint64_t *hist, hipStream_t st) {
+  HBatchM B{};
+  B.njobs = n;
+  int nb = 0;
+  for (int o = 0; o < n; ++o) {
+    const CoregJobHost &s = jobs[o].job;
+    HJob &j = B.j[o].j;
+    j.G = s.G;
+    j.F = s.F;
+    for (int d = 0; d < 3; ++d) {
+      j.dg[d] = s.dim_g[d];
+      j.df[d] = s.dim_f[d];
+      j.s[d] = s.step[d];
+    }
+    for (int e = 0; e < 12; ++e) j.M[e] = s.M[e];
+    j.npts = (int32_t)coreg_grid(s, j.ng);  // <= INT32_MAX: checked by the caller
+    B.j[o].mG = jobs[o].mG;
+    B.j[o].mF = jobs[o].mF;
+    B.blk0[o] = nb;
+    nb += 2 * (int)((j.npts + kCoregChunk - 1) / kCoregChunk);
+  }
+  B.blk0[n] = nb;
+  hipLaunchKernelGGL(k_coreg_hist_m, dim3(nb), dim3(kCoregBlock), 0, st, B, hist);
 }
 
 void launch_coreg_cost(int n, const uint64_t *hist, int cost_fun, const double *taps, int radius, double *work,

@@ -37,6 +37,12 @@ struct CoregJobHost {  // mirrors unires_coreg_job_t
   float step[3];
 };
 
+struct CoregJobMHost {  // mirrors unires_coreg_job_m_t
+  CoregJobHost job;
+  const uint8_t *mG;  // cell supports of G's / F's shape, or null
+  const uint8_t *mF;
+};
+
 // Blocks one observation of n voxels gets in the quantisation launches.
 int coreg_quant_blocks(int64_t n);
 // Sample-grid size of a job along each axis: floor((dim_g - 1) / step) + 1 (float64), and points.
@@ -48,6 +54,14 @@ void launch_coreg_quantise(int n, const float *const *ptrs, const int64_t *sizes
                            uint32_t *counts, float *params, hipStream_t st);
 // One chained group of at most kCoregMaxJobs jobs; hist (n x 256 x 256 uint64) zeroed by the caller.
 void launch_coreg_hist(int n, const CoregJobHost *jobs, uint64_t *hist, hipStream_t st);
+// The two above under supports.  masks[o] (or masks itself) may be null: uint8, non-zero = usable;
+// range, histogram and robust maximum read the finite usable voxels, every finite voxel is converted.
+void launch_coreg_quantise_m(int n, const float *const *ptrs, const int64_t *sizes, const uint8_t *const *masks,
+                             uint8_t *const *outs, uint32_t *counts, float *params, hipStream_t st);
+// cell[i] = 1 iff the eight voxels of the cell at i are all usable (0 in the last plane of every axis)
+void launch_coreg_cellmask(const uint8_t *mask, const int32_t dim[3], uint8_t *cell, hipStream_t st);
+// a sample point in an unsupported G cell, or imaged into an unsupported F cell, adds nothing
+void launch_coreg_hist_m(int n, const CoregJobMHost *jobs, uint64_t *hist, hipStream_t st);
 // n histograms -> n float64 costs; work: n x 256 x 256 doubles of scratch.
 void launch_coreg_cost(int n, const uint64_t *hist, int cost_fun, const double *taps, int radius, double *work,
                        double *cost, hipStream_t st);

@@ -9,6 +9,9 @@
 //   k_noise_fit    one workgroup per observation: a float64 EM fit of a two-class Rice (all values
 //                  >= 0) or Gaussian (CT) mixture to the histogram, 4 bins per lane in registers, one
 //                  block reduction of 7 sums per iteration, the convergence test in the kernel.
+//   k_noise_range_g / k_noise_hist_g
+//                  the first two under per-voxel weight maps: a voxel whose weight is not > 0 is not
+//                  read into either.
 //
 // Selected voxels: finite, non-zero, and >= 0 unless the observation is CT.
 #include <float.h>
@@ -167,6 +170,105 @@ __global__ void __launch_bounds__(kNoiseHistBlock)
                   if (ok) bin = min((int)((((double)v - mn) * (double)kNoiseBins) / width), kNoiseBins - 1);
                   hist_add<kAgg>(h, ok, bin);
                 });
+  __syncthreads();
+  const uint32_t c = h[threadIdx.x];
+  if (c) atomicAdd(counts + (size_t)o * kNoiseBins + threadIdx.x, c);
+}
+
+// ---- the same two passes under per-voxel weight maps ---------------------------------
+// A voxel is taken when selected(v, ct) and its weight g(v) > 0: the support of the map, not its size
+// (counts stay integers).  An observation without a map (g[o] == nullptr) walks as above.
+struct NoiseBatchG {
+  NoiseBatch B;
+  const float *g[kNoiseMaxObs];
+};
+
+// f(v, w) for every element tid, tid + nthr, ... of (p, g)[0, n): 16-byte loads of both, two pairs
+// in flight per lane, when p AND g are 16-byte aligned; voxel by voxel otherwise.
+template <class F>
+__device__ __forceinline__ void for_each_pair(const float *__restrict__ p, const float *__restrict__ g, int64_t n,
+                                              int64_t tid, int64_t nthr, F f) {
+  int64_t done = 0;
+  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g)) & 15) == 0) {
+    const float4 *p4 = reinterpret_cast<const float4 *>(p);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    const int64_t n4 = n >> 2;
+    int64_t i = tid;
+    for (; i + nthr < n4; i += 2 * nthr) {
+      const float4 a = p4[i], wa = g4[i];
+      const float4 b = p4[i + nthr], wb = g4[i + nthr];
+      f(a.x, wa.x); f(a.y, wa.y); f(a.z, wa.z); f(a.w, wa.w);
+      f(b.x, wb.x); f(b.y, wb.y); f(b.z, wb.z); f(b.w, wb.w);
+    }
+    if (i < n4) {
+      const float4 a = p4[i], wa = g4[i];
+      f(a.x, wa.x); f(a.y, wa.y); f(a.z, wa.z); f(a.w, wa.w);
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + tid; i < n; i += nthr) f(p[i], g[i]);
+}
+
+// f(v, w) over observation o of the batch; w = 1 where the observation has no map
+template <class F>
+__device__ __forceinline__ void for_each_weighted(const NoiseBatchG &G, int o, int64_t tid, int64_t nthr, F f) {
+  if (G.g[o])
+    for_each_pair(G.B.p[o], G.g[o], G.B.n[o], tid, nthr, f);
+  else
+    for_each_elem(G.B.p[o], G.B.n[o], tid, nthr, [&](float v) { f(v, 1.f); });
+}
+
+__global__ void __launch_bounds__(kNoiseHistBlock) k_noise_range_g(NoiseBatchG G, float *__restrict__ part) {
+  __shared__ float s_lo[kHistWaves], s_hi[kHistWaves];
+  const NoiseBatch &B = G.B;
+  const int o = obs_of(B, blockIdx.x);
+  const int blk = blockIdx.x - B.blk0[o], nb = B.blk0[o + 1] - B.blk0[o];
+  const int ct = B.ct[o];
+  float lo = INFINITY, hi = -INFINITY;
+  for_each_weighted(G, o, (int64_t)blk * kNoiseHistBlock + threadIdx.x, (int64_t)nb * kNoiseHistBlock,
+                    [&](float v, float w) {
+                      if (selected(v, ct) && w > 0.f) {
+                        lo = fminf(lo, v);
+                        hi = fmaxf(hi, v);
+                      }
+                    });
+  block_minmax(lo, hi, s_lo, s_hi);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = lo;
+    part[2 * blockIdx.x + 1] = hi;
+  }
+}
+
+template <int kAgg>
+__global__ void __launch_bounds__(kNoiseHistBlock)
+    k_noise_hist_g(NoiseBatchG G, const float *__restrict__ part, uint32_t *__restrict__ counts, float *__restrict__ range) {
+  __shared__ uint32_t h[kNoiseBins];
+  __shared__ float s_lo[kHistWaves], s_hi[kHistWaves];
+  const NoiseBatch &B = G.B;
+  const int o = obs_of(B, blockIdx.x);
+  const int b0 = B.blk0[o], blk = blockIdx.x - b0, nb = B.blk0[o + 1] - b0;
+  const int ct = B.ct[o];
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = threadIdx.x; i < nb; i += kNoiseHistBlock) {
+    lo = fminf(lo, part[2 * (b0 + i)]);
+    hi = fmaxf(hi, part[2 * (b0 + i) + 1]);
+  }
+  block_minmax(lo, hi, s_lo, s_hi);
+  h[threadIdx.x] = 0;
+  if (blk == 0 && threadIdx.x == 0) {
+    range[2 * o] = lo;
+    range[2 * o + 1] = hi;
+  }
+  if (!(hi > lo)) return;  // nothing usable, or one value: the fit reports it
+  __syncthreads();
+  const double mn = lo, width = (double)hi - (double)lo;
+  for_each_weighted(G, o, (int64_t)blk * kNoiseHistBlock + threadIdx.x, (int64_t)nb * kNoiseHistBlock,
+                    [&](float v, float w) {
+                      const bool ok = selected(v, ct) && w > 0.f;
+                      int bin = 0;
+                      if (ok) bin = min((int)((((double)v - mn) * (double)kNoiseBins) / width), kNoiseBins - 1);
+                      hist_add<kAgg>(h, ok, bin);
+                    });
   __syncthreads();
   const uint32_t c = h[threadIdx.x];
   if (c) atomicAdd(counts + (size_t)o * kNoiseBins + threadIdx.x, c);
@@ -394,6 +496,29 @@ void launch_noise_hist(int n, const float *const *ptrs, const int64_t *sizes, co
     hipLaunchKernelGGL(k_noise_hist<1>, dim3(nb), dim3(kNoiseHistBlock), 0, st, B, (const float *)part, counts, range);
   else
     hipLaunchKernelGGL(k_noise_hist<0>, dim3(nb), dim3(kNoiseHistBlock), 0, st, B, (const float *)part, counts, range);
+}
+
+void launch_noise_hist_g(int n, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
+                         const float *const *gptrs, float *part, uint32_t *counts, float *range, int hist_form,
+                         hipStream_t st) {
+  NoiseBatchG G{};
+  NoiseBatch &B = G.B;
+  B.nobs = n;
+  int nb = 0;
+  for (int o = 0; o < n; ++o) {
+    B.p[o] = ptrs[o];
+    G.g[o] = gptrs ? gptrs[o] : nullptr;
+    B.n[o] = sizes[o];
+    B.ct[o] = ct ? ct[o] : 0;
+    B.blk0[o] = nb;
+    nb += noise_hist_blocks(sizes[o]);
+  }
+  B.blk0[n] = nb;
+  hipLaunchKernelGGL(k_noise_range_g, dim3(nb), dim3(kNoiseHistBlock), 0, st, G, part);
+  if (hist_form)
+    hipLaunchKernelGGL(k_noise_hist_g<1>, dim3(nb), dim3(kNoiseHistBlock), 0, st, G, (const float *)part, counts, range);
+  else
+    hipLaunchKernelGGL(k_noise_hist_g<0>, dim3(nb), dim3(kNoiseHistBlock), 0, st, G, (const float *)part, counts, range);
 }
 
 void launch_noise_fit(int n, const uint32_t *counts, const float *range, int max_iter, double *out,

@@ -33,6 +33,11 @@ int noise_hist_blocks(int64_t n);
 // hist_form: 0 plain LDS atomics, 1 wave pre-aggregation of lanes that share the first lane's bin.
 void launch_noise_hist(int n, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
                        float *part, uint32_t *counts, float *range, int hist_form, hipStream_t st);
+// The same under per-voxel weight maps: gptrs[o] (or gptrs itself) may be null; a voxel of an
+// observation with a map is taken only where its weight is > 0.
+void launch_noise_hist_g(int n, const float *const *ptrs, const int64_t *sizes, const int32_t *ct,
+                         const float *const *gptrs, float *part, uint32_t *counts, float *range, int hist_form,
+                         hipStream_t st);
 void launch_noise_fit(int n, const uint32_t *counts, const float *range, int max_iter, double *out,
                       hipStream_t st);
 

@@ -1,5 +1,6 @@
 // pull.hip - the affine pulls: trilinear (k_pull), label vote (k_warp_label), nearest neighbour (k_pull_nearest) and
-// the spatial gradient of the trilinear sample (k_pull_grad).
+// the spatial gradient of the trilinear sample (k_pull_grad), and the support of the trilinear pull under a weight
+// map (k_pull_support).
 //
 // Layout: float32 volumes, (X,Y,Z) C-contiguous, Z fastest.  Every kernel puts
 // the 64 lanes of a wave along Z so that HBM/L2 requests are coalesced.
@@ -180,6 +181,58 @@ __global__ void __launch_bounds__(kBlock) k_pull_grad(const float *__restrict__ 
 }
 
 // --------------------------------------------------------------------------
+// support of a pull under a weight map g: dst[v] = 1 iff k_pull's sample at v is inside
+// the FOV and every corner (floor(c_d), floor(c_d) + 1) of it that lies inside the volume has g > 0.
+// A corner outside the volume adds 0 to a zero-bound pull and does not decide; a corner inside it
+// decides even at weight 0 (0 x NaN is not 0).  Coordinates and loads are k_pull's own (affine_row /
+// affine_along, pull_issue on the map): the floors below are of the same floats.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ bool support_of(const PullLoads &L, const Dim3i &sd, float gx, float gy, float gz,
+                                           float tol) {
+  if (!in_fov(gx, gy, gz, sd, tol)) return false;
+  const int ix = (int)floorf(gx), iy = (int)floorf(gy), iz = (int)floorf(gz);
+  const bool x0 = ix >= 0 && ix < sd.x, x1 = ix + 1 >= 0 && ix + 1 < sd.x;
+  const bool y0 = iy >= 0 && iy < sd.y, y1 = iy + 1 >= 0 && iy + 1 < sd.y;
+  const bool z0 = iz >= 0 && iz < sd.z, z1 = iz + 1 >= 0 && iz + 1 < sd.z;
+  // pull_issue's z pair (b, b + 1): which of its two loads hold the corners iz and iz + 1
+  const int b = min(max(iz, 0), max(sd.z - 2, 0));
+  const bool px = iz == b ? z0 : (iz == b - 1 ? z1 : false);  // pair.x is a corner inside the volume
+  const bool py = iz == b ? z1 : (iz == b + 1 ? z0 : false);  // pair.y likewise
+  bool ok = true;
+  ok = ok && (!(x0 && y0 && px) || L.v00.x > 0.f) && (!(x0 && y0 && py) || L.v00.y > 0.f);
+  ok = ok && (!(x0 && y1 && px) || L.v01.x > 0.f) && (!(x0 && y1 && py) || L.v01.y > 0.f);
+  ok = ok && (!(x1 && y0 && px) || L.v10.x > 0.f) && (!(x1 && y0 && py) || L.v10.y > 0.f);
+  ok = ok && (!(x1 && y1 && px) || L.v11.x > 0.f) && (!(x1 && y1 && py) || L.v11.y > 0.f);
+  return ok;
+}
+
+// Launch shape and coordinates as k_pull.
+template <int kChunks>
+__global__ void __launch_bounds__(kBlock) k_pull_support(const float *__restrict__ g, Dim3i sd, Affine A,
+                                                         uint8_t *__restrict__ dst, Dim3i gd, float tol) {
+  const int lane = threadIdx.x;
+  const int j = blockIdx.y * 4 + threadIdx.y;
+  const int i = blockIdx.z;
+  const int kbase = blockIdx.x * (kWave * kChunks);
+  if (j >= gd.y) return;
+  const RowBase rb = affine_row(A, (float)i, (float)j);
+  uint8_t *row = dst + ((size_t)i * gd.y + j) * gd.z;
+  PullLoads L[kChunks];
+  float c[kChunks][3];
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int k = min(kbase + u * kWave + lane, gd.z - 1);
+    affine_along(A, rb, (float)k, c[u][0], c[u][1], c[u][2]);
+    pull_issue(g, sd, c[u][0], c[u][1], c[u][2], tol, L[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int k = kbase + u * kWave + lane;
+    if (k < gd.z) row[k] = support_of(L[u], sd, c[u][0], c[u][1], c[u][2], tol) ? 1 : 0;
+  }
+}
+
+// --------------------------------------------------------------------------
 // host launchers
 // --------------------------------------------------------------------------
 // fewest idle lanes: chunks per thread = the count (<= 4) that wastes least of the row's tail
@@ -220,6 +273,21 @@ void launch_warp_label(const float *label, Dim3i sd, const Affine &A, float *dst
     hipLaunchKernelGGL(k_warp_label<2>, grid, vol_block(), 0, st, label, sd, A, dst, gd, tol);
   else
     hipLaunchKernelGGL(k_warp_label<1>, grid, vol_block(), 0, st, label, sd, A, dst, gd, tol);
+}
+
+void launch_pull_support(const float *g, Dim3i sd, const Affine &A, uint8_t *dst, Dim3i gd, float tol,
+                         hipStream_t st) {
+  const int best = pull_chunks(gd.z);
+  const int zspan = kWave * best;
+  const dim3 grid((gd.z + zspan - 1) / zspan, (gd.y + 3) / 4, gd.x);
+  if (best == 4)
+    hipLaunchKernelGGL(k_pull_support<4>, grid, vol_block(), 0, st, g, sd, A, dst, gd, tol);
+  else if (best == 3)
+    hipLaunchKernelGGL(k_pull_support<3>, grid, vol_block(), 0, st, g, sd, A, dst, gd, tol);
+  else if (best == 2)
+    hipLaunchKernelGGL(k_pull_support<2>, grid, vol_block(), 0, st, g, sd, A, dst, gd, tol);
+  else
+    hipLaunchKernelGGL(k_pull_support<1>, grid, vol_block(), 0, st, g, sd, A, dst, gd, tol);
 }
 
 void launch_pull_nearest(const float *src, Dim3i sd, const Affine &A, float *dst, Dim3i gd,

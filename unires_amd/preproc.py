@@ -54,12 +54,25 @@ def _vol(dat, name='dat'):
     return dat.contiguous()
 
 
+class JobM(C.Structure):
+    """``unires_coreg_job_m_t``."""
+    _fields_ = Job._fields_ + [('mG', C.c_void_p), ('mF', C.c_void_p)]
+
+
+def _u8vol(v):
+    return (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.uint8 and v.dim() == 3
+            and v.is_contiguous())
+
+
 @on_device
-def coreg_quantise(dats):
+def coreg_quantise(dats, masks=None):
     """uint8 copies of float32 volumes, one launch for all (DESIGN 8.2 rule 1).  Returns
     ``(vols, counts, params)``: the uint8 volumes, the (N, 1024) int32 histograms of the finite
     voxels over [min, max] and the (N, 8) float32 rows (min, max, robust max, scale, status, ...),
-    all on the device.  Raises ValueError for a volume with no finite voxel or a constant one."""
+    all on the device.  Raises ValueError for a volume with no finite voxel or a constant one.
+    ``masks``: one uint8 device support (non-zero usable) or None per volume; range, histogram and
+    robust maximum are then those of the finite usable voxels, and every finite voxel is converted
+    with them."""
     vols = [_vol(d) for d in dats]
     if any(v.dtype != torch.float32 for v in vols):
         raise TypeError('unires_amd: coreg_quantise takes float32 volumes')
@@ -71,24 +84,50 @@ def coreg_quantise(dats):
     ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vols])
     sizes = (C.c_int64 * n)(*[v.numel() for v in vols])
     optrs = (C.c_void_p * n)(*[u.data_ptr() for u in outs])
-    check(_lib.load().unires_coreg_quantise(n, ptrs, sizes, optrs, C.c_void_p(counts.data_ptr()),
-                                            C.c_void_p(params.data_ptr()), _stream()))
+    masked = masks is not None and any(m is not None for m in masks)
+    if masked:
+        if len(masks) != n or any(m is not None and not (_u8vol(m) and m.shape == v.shape) for m, v in zip(masks, vols)):
+            raise ValueError('unires_amd: coreg_quantise takes one contiguous uint8 device support of its '
+                             "volume's shape (or None) per volume")
+        mptrs = (C.c_void_p * n)(*[None if m is None else m.data_ptr() for m in masks])
+        check(_lib.load().unires_coreg_quantise_m(n, ptrs, sizes, mptrs, optrs, C.c_void_p(counts.data_ptr()),
+                                                  C.c_void_p(params.data_ptr()), _stream()))
+    else:
+        check(_lib.load().unires_coreg_quantise(n, ptrs, sizes, optrs, C.c_void_p(counts.data_ptr()),
+                                                C.c_void_p(params.data_ptr()), _stream()))
     status = params[:, STATUS].cpu()
     for i, s in enumerate(status.tolist()):
+        usable = ' usable' if masked and masks[i] is not None else ''
         if s == 1:
-            raise ValueError('coreg: observation %d has no finite voxel' % i)
+            raise ValueError('coreg: observation %d has no finite%s voxel' % (i, usable))
         if s == 2:
-            raise ValueError('coreg: observation %d is constant' % i)
+            raise ValueError('coreg: observation %d is constant%s' % (i, ' over its usable voxels' if usable else ''))
     return outs, counts, params
 
 
-def _job(G, F, M, step):
-    j = Job()
+@on_device
+def coreg_cellmask(mask):
+    """Cell support of a uint8 device support (X, Y, Z): 1 where the eight voxels of the interpolation
+    cell that starts at the voxel are all usable, 0 elsewhere and in the last plane of every axis
+    (DESIGN 8.10)."""
+    if not _u8vol(mask):
+        raise ValueError('unires_amd: coreg_cellmask takes a contiguous (X, Y, Z) uint8 device volume')
+    cell = torch.empty_like(mask)
+    check(_lib.load().unires_coreg_cellmask(C.c_void_p(mask.data_ptr()), _lib.i3(mask.shape),
+                                            C.c_void_p(cell.data_ptr()), _stream()))
+    return cell
+
+
+def _job(G, F, M, step, mG=None, mF=None, cls=Job):
+    j = cls()
     j.G, j.F = G.data_ptr(), F.data_ptr()
     j.dim_g = _lib.c_i32x3(*G.shape)
     j.dim_f = _lib.c_i32x3(*F.shape)
     j.M = _lib.c_f32x12(*[float(v) for v in np.asarray(M, dtype=np.float32).reshape(-1)])
     j.step = _lib.c_f32x3(*[float(v) for v in np.asarray(step, dtype=np.float32)])
+    if cls is JobM:
+        j.mG = None if mG is None else mG.data_ptr()
+        j.mF = None if mF is None else mF.data_ptr()
     return j
 
 
@@ -96,16 +135,27 @@ def _job(G, F, M, step):
 def coreg_hist(jobs):
     """Joint histograms of ``jobs``, a list of ``(G, F, M, step)``: uint8 device volumes, the
     float32 3x4 (12,) map from G voxels to F voxels and the sampling step in G voxels.  One launch
-    -> (N, 256, 256) int64 device counts in Q16 units (DESIGN 8.2 rule 2)."""
+    -> (N, 256, 256) int64 device counts in Q16 units (DESIGN 8.2 rule 2).  A job may be
+    ``(G, F, M, step, mG, mF)``: the cell supports (``coreg_cellmask``) of G and F, each or both None;
+    a sample point in an unsupported cell of G, or imaged into an unsupported cell of F, is dropped
+    (DESIGN 8.10)."""
     n = len(jobs)
-    for G, F, _, _ in jobs:
-        for v in (G, F):
-            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.uint8 and v.dim() == 3
-                    and v.is_contiguous()):
+    for job in jobs:
+        if len(job) not in (4, 6):
+            raise ValueError('unires_amd: a coreg_hist job is (G, F, M, step) or (G, F, M, step, mG, mF)')
+        for v in job[:2]:
+            if not _u8vol(v):
                 raise ValueError('unires_amd: coreg_hist takes contiguous (X, Y, Z) uint8 device volumes')
+        for m, v in zip(job[4:], job[:2]):
+            if m is not None and not (_u8vol(m) and m.shape == v.shape):
+                raise ValueError("unires_amd: a cell support is a contiguous uint8 device volume of its image's shape")
     dev = jobs[0][0].device
-    arr = (Job * n)(*[_job(*j) for j in jobs])
     hist = torch.empty((n, BINS, BINS), dtype=torch.int64, device=dev)
+    if any(len(job) == 6 and (job[4] is not None or job[5] is not None) for job in jobs):
+        arr = (JobM * n)(*[_job(*j, cls=JobM) for j in jobs])
+        check(_lib.load().unires_coreg_hist_m(n, arr, C.c_void_p(hist.data_ptr()), _stream()))
+        return hist
+    arr = (Job * n)(*[_job(*j[:4]) for j in jobs])
     check(_lib.load().unires_coreg_hist(n, arr, C.c_void_p(hist.data_ptr()), _stream()))
     return hist
 
@@ -318,10 +368,39 @@ def _smooth_taps(fwhm):
     return (k / k.sum()).astype(np.float32)
 
 
+def _level_taps(vx, samp):
+    return [_smooth_taps(math.sqrt(max(samp ** 2 - float(v) ** 2, 0.0)) / float(v)) for v in vx]
+
+
+def erode_support(sup, radius):
+    """Erode a boolean support (X, Y, Z) along each axis d by ``radius[d]`` voxels: a voxel stays
+    usable only if no voxel within +-radius[d] along that axis is unusable.  Voxels beyond the
+    volume's end count as usable (the smoothing pads with zeros there with or without a support).
+    Exact integer arithmetic (a running count of unusable voxels per line), one axis after the other."""
+    bad = ~sup
+    for ax, r in enumerate(radius):
+        if r <= 0:
+            continue
+        n = bad.shape[ax]
+        c = torch.cumsum(bad.to(torch.int32), dim=ax)
+        c = torch.cat([torch.zeros_like(c.narrow(ax, 0, 1)), c], dim=ax)  # c[k] = unusable among [0, k)
+        idx = torch.arange(n, device=bad.device)
+        hi, lo = torch.clamp(idx + r + 1, max=n), torch.clamp(idx - r, min=0)
+        bad = (c.index_select(ax, hi) - c.index_select(ax, lo)) > 0
+    return ~bad
+
+
+def _level_support(weight, vx, samp):
+    """uint8 support of a level volume: the support of the map (> 0), eroded by the tap radius along
+    every axis ``_level_volume`` smooths."""
+    R = [(t.size - 1) // 2 for t in _level_taps(vx, samp)]
+    return erode_support(weight > 0, R).to(torch.uint8).contiguous()
+
+
 def _level_volume(dat, vx, samp):
     """The float volume sampled at ``samp`` mm: smoothed along every axis whose voxel is smaller
     than ``samp`` by a Gaussian of FWHM sqrt(samp^2 - vx^2) mm (zero padding, same size)."""
-    taps = [_smooth_taps(math.sqrt(max(samp ** 2 - float(v) ** 2, 0.0)) / float(v)) for v in vx]
+    taps = _level_taps(vx, samp)
     if all(t.size == 1 for t in taps):
         return dat
     full = _ops.conv_up(dat, taps, (1, 1, 1))
@@ -340,12 +419,15 @@ def voxel_map(q, basis, mat_moving, mat_fix):
     return np.linalg.solve(mat_moving, R @ mat_fix)
 
 
-def affine_align(imgs, cost_fun='nmi', group='SE', samp=1, fwhm=7, mean_space=False, fix=0, device=None):
+def affine_align(imgs, cost_fun='nmi', group='SE', samp=1, fwhm=7, mean_space=False, fix=0, device=None,
+                 weights=None):
     """Align every observation of ``imgs`` (``[[dat, mat], ...]``) rigidly to ``imgs[fix]``.
     Returns ``(q, mat_a)``: the (N, 6) float64 parameters (``_rigid.affine_basis('SE')``) and
     the (N, 4, 4) float64 transforms ``mat_a[i] = expm(q_i)``, ``mat_a[fix] = I``; observation
     i's aligned orientation is ``mat_a[i]^-1 mat_i``.  ``samp``: sampling distance in mm, or a
-    tuple of them run coarse to fine.  DESIGN 8.2 states the estimator."""
+    tuple of them run coarse to fine.  DESIGN 8.2 states the estimator.  ``weights``: one map of its
+    image's shape (or None) per image - cost-function masking: voxels where a map is not > 0 enter
+    neither the quantisation parameters nor any counted sample of the histograms."""
     if group != 'SE':
         raise NotImplementedError("affine_align: only group='SE' (rigid) is built")
     if mean_space:
@@ -369,14 +451,29 @@ def affine_align(imgs, cost_fun='nmi', group='SE', samp=1, fwhm=7, mean_space=Fa
                 d = d.to(dev)
             dats.append(d.to(torch.float32).contiguous())
         vxs = [voxel_size(m).numpy() for m in mats]
+        maps = None
+        if weights is not None and any(w is not None for w in weights):
+            if len(weights) != N:
+                raise ValueError('affine_align: weights must have one entry (a map or None) per image')
+            maps = [None if w is None else torch.as_tensor(w).to(d.device) for w, d in zip(weights, dats)]
+            if any(g is not None and g.shape != d.shape for g, d in zip(maps, dats)):
+                raise ValueError("affine_align: a weight map must have its image's shape")
         for s in levels:
             vols = [_level_volume(d, vx, s) for d, vx in zip(dats, vxs)]
-            u8, _, _ = coreg_quantise(vols)
             step = (s / vxs[fix]).astype(np.float32)
+            if maps is None:
+                u8, _, _ = coreg_quantise(vols)
+                cell = [None] * N
+            else:  # supports of the level volumes, then their cell supports: once per level
+                sup = [None if g is None else _level_support(g, vx, s) for g, vx in zip(maps, vxs)]
+                u8, _, _ = coreg_quantise(vols, sup)
+                cell = [None if m is None else coreg_cellmask(m) for m in sup]
 
-            def evaluate(reqs, u8=u8, step=step):
+            def evaluate(reqs, u8=u8, step=step, cell=cell):
                 jobs = [(u8[fix], u8[pairs[k]], _m12(voxel_map(x, basis, mats[pairs[k]], mats[fix])), step)
                         for k, x in reqs]
+                if maps is not None:
+                    jobs = [j + (cell[fix], cell[pairs[k]]) for j, (k, _) in zip(jobs, reqs)]
                 return coreg_cost(coreg_hist(jobs), cost_fun, fwhm).cpu().tolist()
 
             res, _ = lockstep([powell(q[i]) for i in pairs], evaluate)

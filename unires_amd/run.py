@@ -8,7 +8,7 @@ paths or arrays to the structs fit() takes, and from its result to clamped image
 import torch
 
 from . import _lib
-from ._core import (_estimate_hyperpar, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
+from ._core import (_check_init_weights, _estimate_hyperpar, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
                     _not_built, _proj_info_add, _read_data, _read_weights, _resample_inplane, _write_data)
 from ._host import wait_blocking
 from ._lib import check, i3
@@ -212,7 +212,9 @@ def init(data, sett=None):
     ``data``: paths (``['T1.nii', 'T2.nii']``; with repeats ``[['T1_1.nii', 'T1_2.nii'], ['T2.nii']]``),
     ``[dat, mat]`` pairs in the same nestings, an (X, Y, Z, C) array with ``sett.mat``, or the path
     of a 4-D NIfTI.  ``sett``: a ``settings()``; the defaults when None.  Returns ``(x, y, sett)``,
-    what ``fit`` takes."""
+    what ``fit`` takes.  With ``sett.voxel_init`` the weight maps of ``sett.weight`` are validated here (finite, >= 0;
+    ValueError naming channel and repeat) and a voxel of weight 0 is read by neither the hyper-parameter estimate, nor
+    the coregistration, nor the first guess of ``y``; without it the three ignore the maps."""
     sett = settings() if sett is None else sett
     _not_built(sett, ('crop', 'common_output', 'do_atlas_align', 'write_jtv'))
     for name in ('plot_conv', 'show_hyperpar', 'show_jtv'):
@@ -222,6 +224,8 @@ def init(data, sett=None):
         x = _read_data(data, sett)
         del data
         x = _read_weights(x, sett)
+        if getattr(sett, 'voxel_init', False):
+            x = _check_init_weights(x, sett)
         if sett.max_iter > 0:
             x = _estimate_hyperpar(x, sett)
         x = _fix_affine(x, sett)

@@ -29,10 +29,12 @@ def _flat(dat, name='dat'):
 
 
 @on_device
-def noise_hist(dats, cts):
+def noise_hist(dats, cts, weights=None):
     """Masked range and 1024-bin histogram of every volume of ``dats`` in one pass.  Returns
     ``(counts, rng)``: (N, 1024) int32 device (the kernel's uint32 counts; < 2^31 per bin here since
-    a volume has < 2^31 voxels) and (N, 2) float32 device (min, max of the voxels taken)."""
+    a volume has < 2^31 voxels) and (N, 2) float32 device (min, max of the voxels taken).
+    ``weights``: one float32 device map (of its volume's size) or None per volume; a voxel of a volume
+    with a map is taken only where the map is > 0."""
     flats = [_flat(d) for d in dats]
     if any(f.numel() >= 2 ** 31 for f in flats):
         raise ValueError('unires_amd: noise_hist takes volumes of fewer than 2^31 voxels')
@@ -43,6 +45,16 @@ def noise_hist(dats, cts):
     ptrs = (C.c_void_p * n)(*[f.data_ptr() for f in flats])
     sizes = (C.c_int64 * n)(*[f.numel() for f in flats])
     ct = (C.c_int32 * n)(*[1 if c else 0 for c in cts])
+    if weights is not None and any(w is not None for w in weights):
+        if len(weights) != n:
+            raise ValueError('unires_amd: noise_hist takes one weight map (or None) per volume')
+        gs = [None if w is None else _flat(w, 'weight') for w in weights]
+        if any(g is not None and g.numel() != f.numel() for g, f in zip(gs, flats)):
+            raise ValueError('unires_amd: a weight map must have the size of its volume')
+        gptrs = (C.c_void_p * n)(*[None if g is None else g.data_ptr() for g in gs])
+        check(_lib.load().unires_noise_hist_g(n, ptrs, sizes, ct, gptrs, C.c_void_p(counts.data_ptr()),
+                                              C.c_void_p(rng.data_ptr()), _stream()))
+        return counts, rng
     check(_lib.load().unires_noise_hist(n, ptrs, sizes, ct, C.c_void_p(counts.data_ptr()),
                                         C.c_void_p(rng.data_ptr()), _stream()))
     return counts, rng
@@ -71,16 +83,17 @@ def _noise_params(row):
             {'sd': f64(row[SIG + fg]), 'mean': f64(row[MEAN + fg])})
 
 
-def estimate_noise(dat, num_class=2, bins=1024, max_iter=10000):
+def estimate_noise(dat, num_class=2, bins=1024, max_iter=10000, weight=None):
     """Noise and not-noise statistics of the finite, non-zero voxels of ``dat`` (a float32 device
     tensor of any shape), nitorch's call shape: returns ``(prm_noise, prm_not_noise)``, dicts with
     ``'sd'`` and ``'mean'`` (float64 CPU scalars) of the class with the smaller and the larger mean.
-    Negative values select the Gaussian mixture.  Only two classes and 1024 bins are built."""
+    Negative values select the Gaussian mixture.  Only two classes and 1024 bins are built.
+    ``weight``: a float32 device map of ``dat``'s size; only voxels where it is > 0 are read."""
     if num_class != 2:
         raise NotImplementedError('estimate_noise: only num_class=2 is implemented')
     if bins != BINS:
         raise NotImplementedError('estimate_noise: only bins=%d is implemented' % BINS)
-    counts, rng = noise_hist([dat], [True])
+    counts, rng = noise_hist([dat], [True], None if weight is None else [weight])
     row = noise_fit(counts, rng, max_iter)[0].cpu()
     if row[MODEL] < 0:
         raise ValueError('estimate_noise: no finite non-zero voxels, or all of them equal')

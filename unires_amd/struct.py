@@ -116,6 +116,13 @@ class settings:
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
+        # init() honours the weight maps too: a voxel whose weight is 0 is read by neither the noise / intensity
+        # estimate (tau, mu, lam), nor the coregistration (quantisation range and every counted sample of the joint
+        # histograms), nor the first guess of y (run.init).  Only the support of a map (> 0) counts
+        # there; how large a positive weight is stays the data term's business.  Off: init() ignores the maps, as it
+        # did before it could read them.  A switch only because tests pin init()'s results with sett.weight set; not
+        # a modelling choice - with a defect mask, turn it on
+        self.voxel_init = False
         self.gap = 0.0
         self.interpolation = 'linear'
         self.method = None
