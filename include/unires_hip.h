@@ -554,6 +554,46 @@ int unires_voxel_apply(const float *src, float *dst, const float *g, const uint8
 int unires_voxel_huber(const float *x, const float *ay, const float *prior, float c, int64_t n, float *g_out,
                        void *stream);
 
+/* ------------------------------------------------------------------------
+ * Exact medians on the device (no counterpart in the reference): a radix select on the bit patterns of |t(v)|, three
+ * histogram passes of 11 + 11 + 10 bits with a one-workgroup scan after each.
+ *
+ * Both entry points give the LOWER median (the ceil(N/2)-th smallest of N, torch.median's convention) of |t(v)| over
+ * the eligible voxels.  out_dev: 2 float64 on the device:
+ *   [0] the median (a float32 value that occurs in the stream, widened; 0 when N = 0)
+ *   [1] N.
+ * work: UNIRES_MEDIAN_WORK_BYTES of device scratch, 4-byte aligned; the caller need not clear it, and may reuse it for
+ * the next call on the same stream.  No read-back, no host synchronisation, the same bits every run (integer counts).
+ * Status of the two median entry points: n < 0, n or a cell count above 2^32 - 1, an axis outside 0..2 and a null x, ay,
+ * dim, work or out_dev are UNIRES_ERR_ARG; a `dim` with an entry < 1 (or beyond what every volume entry point takes) is
+ * UNIRES_ERR_DIM.
+ * ------------------------------------------------------------------------ */
+#define UNIRES_MEDIAN_WORK_BYTES 24592
+
+/* t = fl32(x - ay) over n voxels;
+ * eligible: x != 0, t finite, and (prior == NULL or prior > 0): the missing-data and prior conventions of the Huber
+ * rule above.  16-byte loads where x, ay and prior are on a 16-byte boundary, voxel by voxel otherwise. */
+int unires_median_absres(const float *x, const float *ay, const float *prior, int64_t n, void *work, double *out_dev,
+                         void *stream);
+
+/* Haar diagonal detail in the plane orthogonal to `axis`, at every 2x2 in-plane cell (undecimated) of the volume `dim`:
+ *   t = ((a - b) - c) + d,  in float32, in this order,
+ *   where a = x[p,q], b = x[p+1,q], c = x[p,q+1], d = x[p+1,q+1];
+ *   p, q run along the two other axes in ascending axis order.
+ * Eligible: all four voxels finite, != 0 (ct == 0: > 0), and (w == NULL or all four w > 0); w: a volume `dim`.
+ * Of i.i.d. noise of variance s^2, t has variance 4 s^2. */
+int unires_median_hh(const float *x, const int32_t dim[3], int32_t axis, int32_t ct, const float *w, void *work,
+                     double *out_dev, void *stream);
+
+/* The Huber weights above with the threshold taken from the device:
+ *   c = fl32(mult * (float)scale_dev[0]),  mult > 0.
+ * c > 0: the bits the Huber entry point gives for that c.
+ * c == 0 (nothing eligible, or a zero median): g_out = prior (ones where prior == NULL).
+ * g_out may be prior.  Status, as the Huber entry point above: a null x, ay, scale_dev or g_out is UNIRES_ERR_NULL,
+ * n < 0 UNIRES_ERR_DIM, a mult that is not > 0 UNIRES_ERR_ARG. */
+int unires_voxel_huber_dev(const float *x, const float *ay, const float *prior, const double *scale_dev, float mult,
+                           int64_t n, float *g_out, void *stream);
+
 /* Gradient and Hessian sums of one rigid Gauss-Newton step (_update_rigid_channel,
  * _update.py:622-650) in one pass over the grid: gr3 (dim,3) = grid_grad of the pulled image,
  * diff (dim) = residual (conv_transposed, _update.py:524), ctc (dim) = conv_transpose(conv(1))

@@ -147,6 +147,55 @@ def _resample_inplane(x, sett):
     return x
 
 
+NOISE_EST = ('mixture', 'mad')
+
+
+def _noise_est(sett):
+    """sett.noise_est ('mixture' where the settings object has none); any other name than NOISE_EST's is a ValueError."""
+    name = getattr(sett, 'noise_est', 'mixture')
+    if name not in NOISE_EST:
+        raise ValueError("sett.noise_est must be 'mixture' or 'mad', not %r" % (name,))
+    return name
+
+
+def _thick_axis(mat):
+    """The first of the largest voxel sizes of an observation's affine: the axis its slices are stacked along, as
+    ``_proj_info`` picks ``dim_thick`` once the output space exists."""
+    vx = [float(v) for v in voxel_size(torch.as_tensor(mat).detach().to('cpu', torch.float64)).tolist()]
+    return vx.index(max(vx))
+
+
+def _estimate_hyperpar_mad(x, obs, gs):
+    """``_estimate_hyperpar`` with ``sett.noise_est = 'mad'``: ``sd`` from the exact median of the
+    magnitude of the in-plane Haar diagonal detail (``stats.median_hh``, ``stats.mad_sd``), ``tau = 1 / sd**2`` in the
+    same float32 arithmetic as the mixture's, and ``mu`` = |mean of the voxels read| - what |mean_fg - mean_bg| is
+    without a background.  One scratch buffer for all observations, one read-back."""
+    dev = x[obs[0][0]][obs[0][1]].dat.device
+    work = stats.median_work(dev)
+    res = torch.zeros((len(obs), 4), dtype=torch.float64, device=dev)  # median, cells, sum and count of the voxels read
+    for r, ((c, n), g) in enumerate(zip(obs, gs)):
+        xn = x[c][n]
+        dat = xn.dat.contiguous()
+        stats.median_hh(dat, _thick_axis(xn.mat), bool(xn.ct), g, work=work, out=res[r, :2])
+        use = torch.isfinite(dat) & ((dat != 0) if xn.ct else (dat > 0))
+        if g is not None:
+            use = use & (g > 0)
+        res[r, 2] = torch.where(use, dat, torch.zeros_like(dat)).sum(dtype=torch.float64)
+        res[r, 3] = use.sum()
+    res = res.cpu()
+    for ((c, n), g), (med, cells, tot, cnt) in zip(zip(obs, gs), res.tolist()):
+        if cells == 0 or med == 0:
+            raise ValueError('_estimate_hyperpar: channel %d, repeat %d: noise_est=\'mad\' found %s'
+                             % (c, n, 'no 2 x 2 in-plane cell of usable voxels (finite, non-zero%s%s)'
+                                % ('' if x[c][n].ct else ', > 0', '' if g is None else ', weight > 0') if cells == 0
+                                else 'a zero median detail: the image carries no noise to estimate'))
+        sd = stats.mad_sd(torch.tensor(med, dtype=torch.float64))
+        x[c][n].sd = sd
+        x[c][n].tau = 1 / sd ** 2
+        x[c][n].mu = torch.abs(torch.tensor(tot / cnt, dtype=torch.float64).float())
+    return x
+
+
 @_ops.on_device
 def _estimate_hyperpar(x, sett):
     """Noise precision and mean foreground intensity of every observation (unires/_core.py:96-142):
@@ -154,11 +203,14 @@ def _estimate_hyperpar(x, sett):
     fit to the intensity histogram (``stats.estimate_noise``).  A non-CT observation
     keeps its voxels >= 0.  One histogram launch and one fit launch for all observations, one read
     back.  The values are float32 CPU scalars, with the reference's ``.float()`` arithmetic.  With
-    ``sett.voxel_init`` an observation with a weight map is read only where the map is > 0."""
+    ``sett.voxel_init`` an observation with a weight map is read only where the map is > 0.  ``sett.noise_est = 'mad'``
+    replaces the mixture by ``_estimate_hyperpar_mad`` - for inputs without an air background."""
     obs = [(c, n) for c in range(len(x)) for n in range(len(x[c]))]
     if not obs:
         return x
     gs = [_init_weight(x[c][n], sett) for c, n in obs]  # (sett.voxel_init: only voxels of weight > 0; DESIGN 8.10)
+    if _noise_est(sett) == 'mad':
+        return _estimate_hyperpar_mad(x, obs, gs)
     counts, rng = stats.noise_hist([x[c][n].dat for c, n in obs], [bool(x[c][n].ct) for c, n in obs], gs)
     rows = stats.noise_fit(counts, rng).cpu()
     for (c, n), row, g in zip(obs, rows, gs):

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('UNIRES_LIB') or os.path.join(_HERE, 'libunires_hip.so')
 
 UNIRES_MAX_TAPS = 32
+UNIRES_MEDIAN_WORK_BYTES = 24592  # device scratch of unires_median_absres / unires_median_hh
 OP = {'A': 0, 'At': 1, 'AtA': 2}
 REGIME_IDENTITY, REGIME_DENOISE, REGIME_SUPERRES = 0, 1, 2
 # nitorch cg(stop=...): 'e' = residual norm; anything else = the objective 0.5 sum x (A(x) - 2b) (UniRes passes 'max_gain').
@@ -141,6 +142,11 @@ SIGNATURES = {
     'unires_voxel_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'unires_voxel_huber':(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),
+    'unires_median_absres': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_median_hh': (C.c_int, [C.c_void_p, c_i32x3, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    'unires_voxel_huber_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
+                                         C.c_void_p]),
     'unires_mark_create': (C.c_int, [C.POINTER(C.c_void_p)]),
     'unires_mark_destroy': (C.c_int, [C.c_void_p]),
     'unires_mark_signal': (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -11,6 +11,7 @@ from ._host import Pacer
 from ._plan import cg_many
 from ._project import _channel_plan, _proj, _slice_axis
 from .spatial import voxel_size
+from .stats import MAD_TO_SD, median_absres, median_work
 
 
 _PACERS = {}
@@ -228,6 +229,18 @@ def _gn_weight(xn, sett):
     return g
 
 
+VOXEL_SCALE = ('noise', 'mad')
+
+
+def _voxel_scale(sett):
+    """sett.voxel_scale ('noise' where the settings object has none): what the Huber rule's threshold is a multiple of.
+    Any other name than VOXEL_SCALE's is a ValueError."""
+    name = getattr(sett, 'voxel_scale', 'noise')
+    if name not in VOXEL_SCALE:
+        raise ValueError("sett.voxel_scale must be 'noise' or 'mad', not %r" % (name,))
+    return name
+
+
 @on_device
 def _slice_sums(x, y, sett, ays=None):
     """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights: SSE_s = sum_{v in s,
@@ -267,9 +280,23 @@ def _update_voxel_weights(x, y, sett, ays=None):
     where missing).  ``prior`` is the private clone ``fit()`` keeps of a user's ``_input.weight`` (None: ones), so a
     weight of 0 stays 0.  The weight tensors are written in place and their version counters bumped: they tell the
     plans (``sync_voxel_weights``, at the next y-update's plan fetch) and the cached sum tau At (g . x).  One
-    streaming pass per repeat, no read-back."""
+    streaming pass per repeat, no read-back.
+
+    With ``sett.voxel_scale = 'mad'`` the threshold is voxel_k robust standard deviations of the residuals themselves:
+    c = fl32(fl32(voxel_k) 1.4826) median|x - A y|, the exact median over the voxels the rule judges (x != 0, a finite
+    residual, prior > 0) taken on the device (``unires_median_absres``) and read by the rule's kernel from there
+    (``unires_voxel_huber_dev``): three more passes over x and A y, still no read-back.  No floor at the noise sd, and
+    tau is not re-estimated.  ``xn._voxel_scale`` keeps (median, N) of the last estimate on the device."""
     lib = _lib.load()
     k = float(getattr(sett, 'voxel_k', 3.0))
+    mad = _voxel_scale(sett) == 'mad'
+    mult = float(torch.tensor(k, dtype=torch.float32) * torch.tensor(MAD_TO_SD, dtype=torch.float32))
+    work = None
+    if mad:  # one scratch for every repeat (they share the stream): fit()'s, or one made here for a direct call
+        first = next((xn for xc in x for xn in xc if getattr(xn, 'weight', None) is not None), None)
+        work = getattr(first, '_median_work', None)
+        if work is None and first is not None:
+            work = median_work(first.dat.device)
     for c in range(len(x)):
         for n, xn in enumerate(x[c]):
             g = getattr(xn, 'weight', None)
@@ -283,8 +310,15 @@ def _update_voxel_weights(x, y, sett, ays=None):
                 Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = xn.dat.contiguous()
             prior = getattr(xn, '_weight_prior', None)
-            check(lib.unires_voxel_huber(_ptr(xd), _ptr(Ay), None if prior is None else _ptr(prior),
-                                         k / float(xn.tau) ** 0.5, xd.numel(), _ptr(g), _stream()))
+            if mad:
+                if getattr(xn, '_voxel_scale', None) is None:
+                    xn._voxel_scale = torch.zeros(2, dtype=torch.float64, device=xd.device)
+                median_absres(xd, Ay, prior, work=work, out=xn._voxel_scale)
+                check(lib.unires_voxel_huber_dev(_ptr(xd), _ptr(Ay), None if prior is None else _ptr(prior),
+                                                 _ptr(xn._voxel_scale), mult, xd.numel(), _ptr(g), _stream()))
+            else:
+                check(lib.unires_voxel_huber(_ptr(xd), _ptr(Ay), None if prior is None else _ptr(prior),
+                                             k / float(xn.tau) ** 0.5, xd.numel(), _ptr(g), _stream()))
             torch.autograd.graph.increment_version(g)
     return x
 

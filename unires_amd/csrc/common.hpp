@@ -72,6 +72,25 @@ __device__ __forceinline__ double block_sum(double v) {
   return tot;
 }
 
+// One count into a workgroup's LDS histogram (noise.hip, median.hip).  kAgg: the lanes whose bin equals the first
+// active lane's add once, through that lane - a one-bin pile-up (air / background; residuals of one binary exponent)
+// costs one LDS atomic per wave, not 64 serialised ones.  Counts are integers: the sum does not depend on the order.
+template <int kAgg>
+__device__ __forceinline__ void hist_add(uint32_t *h, bool ok, int bin) {
+  if (!ok) return;
+  if (kAgg) {
+    const int b0 = __builtin_amdgcn_readfirstlane(bin);
+    const uint64_t same = __ballot(bin == b0);
+    if (bin == b0) {
+      if ((int)__lane_id() == __ffsll((unsigned long long)same) - 1) atomicAdd(h + b0, (uint32_t)__popcll(same));
+    } else {
+      atomicAdd(h + bin, 1u);
+    }
+  } else {
+    atomicAdd(h + bin, 1u);
+  }
+}
+
 // Affine coordinate of grid voxel (i,j,k).  The reference builds the dense grid
 // in float32 as lin @ ijk + off (unires/_project.py:159 -> nitorch affine_grid).
 __device__ __forceinline__ void affine_point(const Affine &A, float i, float j, float k, float &gx,

@@ -121,24 +121,7 @@ __global__ void __launch_bounds__(kNoiseHistBlock) k_noise_range(NoiseBatch B, f
   }
 }
 
-// One count into the LDS histogram.  kAgg: the lanes whose bin equals the first active lane's add
-// once, through that lane (the one-bin pile-ups of air / background cost one atomic, not 64).
-template <int kAgg>
-__device__ __forceinline__ void hist_add(uint32_t *h, bool ok, int bin) {
-  if (!ok) return;
-  if (kAgg) {
-    const int b0 = __builtin_amdgcn_readfirstlane(bin);
-    const uint64_t same = __ballot(bin == b0);
-    if (bin == b0) {
-      if ((int)__lane_id() == __ffsll((unsigned long long)same) - 1) atomicAdd(h + b0, (uint32_t)__popcll(same));
-    } else {
-      atomicAdd(h + bin, 1u);
-    }
-  } else {
-    atomicAdd(h + bin, 1u);
-  }
-}
-
+// (one count into the LDS histogram: hist_add, common.hpp)
 template <int kAgg>
 __global__ void __launch_bounds__(kNoiseHistBlock)
     k_noise_hist(NoiseBatch B, const float *__restrict__ part, uint32_t *__restrict__ counts, float *__restrict__ range) {

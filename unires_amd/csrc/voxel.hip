@@ -7,6 +7,7 @@
 //   k_voxel_sums_rows / k_voxel_sums_z + k_voxel_finish: sum g (x - A y)^2 and sum g of every slice, the one statement
 //     of a voxel-weighted repeat's data term.  Not on any solve's path.
 //   k_voxel_huber: g = prior . h, h the Huber weight of the residual.  One streaming pass, no reduction.
+//   k_voxel_huber_dev: the same with the threshold a multiple of a scale the device holds (median.hip).
 //   k_rigid_resid_g: g [u[s(v)]] (A y - x), masked - the residual of the rigid Gauss-Newton step on the same data term
 //     (the five sums of the scaling step on it are k_scaling_sums_g, admm.hip).
 #include <algorithm>
@@ -224,6 +225,29 @@ __global__ void __launch_bounds__(kBlock) k_voxel_huber(const float *__restrict_
   for (size_t e = 4 * n4 + tid; e < n; e += step) g_out[e] = huber_term(x[e], ay[e], PRIOR ? prior[e] : 1.f, c);
 }
 
+// k_voxel_huber with the threshold taken from the device: c = fl32(mult scale[0]), scale a median of median.hip that
+// was never read back.  The same walk and the same huber_term, so c > 0 gives k_voxel_huber's bits; a threshold that
+// is not > 0 (nothing eligible, a zero median) switches the rule off: g_out = prior.
+template <bool PRIOR>
+__global__ void __launch_bounds__(kBlock) k_voxel_huber_dev(const float *__restrict__ x, const float *__restrict__ ay,
+                                                            const float *prior, const double *__restrict__ scale,
+                                                            float mult, size_t n4, size_t n, float *g_out) {
+  const float c = __fmul_rn(mult, (float)scale[0]);
+  const bool off = !(c > 0.f);
+  const auto term = [&](float xv, float av, float pv) { return off ? pv : huber_term(xv, av, pv, c); };
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, step = (size_t)gridDim.x * kBlock;
+  for (size_t q = tid; q < n4; q += step) {
+    const float4 xv = *reinterpret_cast<const float4 *>(x + 4 * q);
+    const float4 av = *reinterpret_cast<const float4 *>(ay + 4 * q);
+    const float4 pv = PRIOR ? *reinterpret_cast<const float4 *>(prior + 4 * q) : make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 v;
+    v.x = term(xv.x, av.x, pv.x), v.y = term(xv.y, av.y, pv.y);
+    v.z = term(xv.z, av.z, pv.z), v.w = term(xv.w, av.w, pv.w);
+    *reinterpret_cast<float4 *>(g_out + 4 * q) = v;
+  }
+  for (size_t e = 4 * n4 + tid; e < n; e += step) g_out[e] = term(x[e], ay[e], PRIOR ? prior[e] : 1.f);
+}
+
 // one voxel of the rigid step's residual on the voxel-weighted data term: g [u] (ay - x) where both are non-zero
 // (_rigid_terms' mask), else +0; the product rounds as k_voxel_apply's: g u exact in float64, times the float32
 // difference, one rounding to float32 - or one float32 product where there is no u
@@ -375,6 +399,22 @@ void launch_voxel_huber(const float *x, const float *ay, const float *prior, flo
     hipLaunchKernelGGL(k_voxel_huber<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, prior, c, n4, n, g_out);
   else
     hipLaunchKernelGGL(k_voxel_huber<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, prior, c, n4, n, g_out);
+}
+
+// launch_voxel_huber's grid and alignment rule
+void launch_voxel_huber_dev(const float *x, const float *ay, const float *prior, const double *scale_dev, float mult,
+                            size_t n, float *g_out, hipStream_t st) {
+  if (!n) return;
+  const bool aligned = (((uintptr_t)x | (uintptr_t)ay | (uintptr_t)prior | (uintptr_t)g_out) & 15) == 0;
+  const size_t n4 = aligned ? n / 4 : 0;
+  const size_t work = aligned ? n4 + 3 : n;
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((work + kBlock - 1) / kBlock, 2048));
+  if (prior)
+    hipLaunchKernelGGL(k_voxel_huber_dev<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, prior, scale_dev, mult,
+                       n4, n, g_out);
+  else
+    hipLaunchKernelGGL(k_voxel_huber_dev<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ay, prior, scale_dev, mult,
+                       n4, n, g_out);
 }
 
 }  // namespace unires

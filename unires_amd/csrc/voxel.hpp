@@ -32,5 +32,8 @@ void launch_rigid_resid_g(const float *x, const float *ay, const float *g, float
 // g_out[v] = (prior ? prior[v] : 1) * h(v); h = 1 where x == 0 or |x - ay| <= c, else c / |x - ay|.  g_out may be prior.
 void launch_voxel_huber(const float *x, const float *ay, const float *prior, float c, size_t n, float *g_out,
                         hipStream_t st);
+// The same with c = fl32(mult * (float)scale_dev[0]) read on the device; c not > 0: g_out = prior (ones without one).
+void launch_voxel_huber_dev(const float *x, const float *ay, const float *prior, const double *scale_dev, float mult,
+                            size_t n, float *g_out, hipStream_t st);
 
 }  // namespace unires

@@ -8,13 +8,14 @@ paths or arrays to the structs fit() takes, and from its result to clamped image
 import torch
 
 from . import _lib
-from ._core import (_check_init_weights, _estimate_hyperpar, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
+from ._core import (_check_init_weights, _estimate_hyperpar, _noise_est, _fix_affine, _format_y, _init_reg, _init_y_dat, _init_y_label,
                     _not_built, _proj_info_add, _read_data, _read_weights, _resample_inplane, _write_data)
 from ._host import wait_blocking
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
 from ._rigid import _update_rigid
-from ._update import _admm_aux, _step_size, _update_admm, _update_scaling
+from ._update import _admm_aux, _step_size, _update_admm, _update_scaling, _voxel_scale
+from .stats import MAD_TO_SD, median_work
 from .optim import get_gain
 from .spatial import _m12
 from .struct import settings
@@ -87,10 +88,15 @@ def _init_voxel_weights(x, sett, dev):
     robust = bool(getattr(sett, 'voxel_robust', False))
     if robust and not float(getattr(sett, 'voxel_k', 3.0)) > 0:
         raise ValueError('sett.voxel_k must be positive')
+    mad = _voxel_scale(sett) == 'mad' and robust
+    work = median_work(dev) if mad else None  # (one scratch for the medians of every repeat: they share the stream)
     any_w = robust
     for c, xc in enumerate(x):
         for n, xn in enumerate(xc):
             xn._weight_prior = None
+            # sett.voxel_scale = 'mad': (median |r|, N) of the repeat's last re-estimate, on the device, and the scratch
+            xn._voxel_scale = torch.zeros(2, dtype=torch.float64, device=dev) if mad else None
+            xn._median_work = work
             g = getattr(xn, 'weight', None)
             if g is None:
                 if robust:
@@ -131,7 +137,9 @@ def fit(x, y, sett):
     ``obj`` (n_iter, 3), the iteration count, the regularisation schedule and ``slice_w``: per channel a list with
     each repeat's final slice weights (a CPU float32 tensor, one per slice along ``po.dim_thick``) or None for a
     repeat without weights, and ``voxel_w``: likewise each repeat's final voxel weights (``_input.weight``,
-    ``sett.voxel_robust``) as the DEVICE float32 tensor the iterations used, or None.
+    ``sett.voxel_robust``) as the DEVICE float32 tensor the iterations used, or None, and ``voxel_scale``: likewise each
+    repeat's last robust residual scale 1.4826 median|x - A y| (a float32 CPU scalar) under ``sett.voxel_robust`` with
+    ``sett.voxel_scale = 'mad'``, else None.
 
     Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
@@ -199,8 +207,13 @@ def fit(x, y, sett):
         dat_y = torch.stack([yc.dat for yc in y], dim=-1)
         slice_w = [[None if getattr(xn, 'slice_w', None) is None else xn.slice_w.detach().cpu() for xn in xc] for xc in x]
         voxel_w = [[getattr(xn, 'weight', None) for xn in xc] for xc in x]
+        # sett.voxel_scale = 'mad': the scale of every repeat's last re-estimate, read once, here
+        meds = [xn._voxel_scale for xc in x for xn in xc if xn._voxel_scale is not None and n_done > 0]
+        meds = iter(torch.stack(meds)[:, 0].cpu().float() if meds else ())
+        voxel_scale = [[None if xn._voxel_scale is None or n_done == 0
+                        else torch.tensor(MAD_TO_SD, dtype=torch.float32) * next(meds) for xn in xc] for xc in x]
         info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w,
-                    voxel_w=voxel_w)
+                    voxel_w=voxel_w, voxel_scale=voxel_scale)
         return dat_y, y[0].mat, R, info
 
 
@@ -217,6 +230,7 @@ def init(data, sett=None):
     the coregistration, nor the first guess of ``y``; without it the three ignore the maps."""
     sett = settings() if sett is None else sett
     _not_built(sett, ('crop', 'common_output', 'do_atlas_align', 'write_jtv'))
+    _noise_est(sett)  # (a name that is not built: ValueError before anything is read)
     for name in ('plot_conv', 'show_hyperpar', 'show_jtv'):
         if getattr(sett, name, False):
             raise NotImplementedError('sett.%s: plotting is not built' % name)

@@ -2,7 +2,11 @@
 reference calls it (unires/_core.py:123-125), on the estimator DESIGN 8.1 states: a 1024-bin
 histogram of the finite, non-zero voxels, then a float64 EM fit of a two-class Rice mixture (all
 values >= 0) or Gaussian mixture (any value < 0).  Both steps are HIP kernels (``noise.hip``): one
-launch bins any number of observations, one launch fits all their histograms."""
+launch bins any number of observations, one launch fits all their histograms.
+
+Exact medians of masked float32 magnitudes, on the device and without a read-back (``median.hip``):
+``median_absres`` - the robust scale of the Huber rule's residuals - and ``median_hh`` / ``estimate_noise_mad`` - a noise
+sd for volumes without an air background, which the mixture cannot give."""
 import ctypes as C
 
 import torch
@@ -72,6 +76,89 @@ def noise_fit(counts, rng, max_iter=MAX_ITER):
     check(_lib.load().unires_noise_fit(n, C.c_void_p(counts.data_ptr()), C.c_void_p(rng.data_ptr()),
                                        int(max_iter), C.c_void_p(out.data_ptr()), _stream()))
     return out
+
+
+MAD_TO_SD = 1.4826  # 1 / Phi^-1(3/4): the median of |t| of a centred Gaussian t, times this, is its sd
+
+
+def median_work(device):
+    """The device scratch of one median call (``UNIRES_MEDIAN_WORK_BYTES``); the entry points clear it themselves, so
+    one buffer serves any number of calls on a stream."""
+    return torch.empty(_lib.UNIRES_MEDIAN_WORK_BYTES // 4, dtype=torch.int32, device=device)
+
+
+def _out(out, device):
+    """The (2,) float64 device result of a median call: a new tensor, or the caller's, checked."""
+    if out is None:
+        return torch.empty(2, dtype=torch.float64, device=device)
+    if not isinstance(out, torch.Tensor) or out.device != device or out.dtype != torch.float64 or out.numel() != 2 \
+            or not out.is_contiguous():
+        raise ValueError('unires_amd: out must be a contiguous float64 tensor of 2 elements on the data\'s device')
+    return out
+
+
+def _work(work, device):
+    if work is None:
+        return median_work(device)
+    if not isinstance(work, torch.Tensor) or not work.is_cuda or work.device != device or not work.is_contiguous() \
+            or work.numel() * work.element_size() < _lib.UNIRES_MEDIAN_WORK_BYTES:
+        raise ValueError('unires_amd: work must be a contiguous device buffer of UNIRES_MEDIAN_WORK_BYTES on the data\'s device')
+    return work
+
+
+@on_device
+def median_absres(x, ay, prior=None, work=None, out=None):
+    """Exact lower median of |fl32(x - ay)| over the voxels with x != 0, a finite difference and (``prior`` given)
+    prior > 0 - the Huber rule's conventions - by a radix select on the device (``unires_median_absres``).
+    Returns the (2,) float64 DEVICE tensor (median, N); nothing is read back.  ``work`` (``median_work``) and ``out``
+    may be handed in to be reused."""
+    fx, fa = _flat(x, 'x'), _flat(ay, 'ay')
+    fp = None if prior is None else _flat(prior, 'prior')
+    if fa.numel() != fx.numel() or (fp is not None and fp.numel() != fx.numel()):
+        raise ValueError('unires_amd: x, ay and prior must have one size')
+    out = _out(out, fx.device)
+    work = _work(work, fx.device)
+    check(_lib.load().unires_median_absres(C.c_void_p(fx.data_ptr()), C.c_void_p(fa.data_ptr()),
+                                           None if fp is None else C.c_void_p(fp.data_ptr()), fx.numel(),
+                                           C.c_void_p(work.data_ptr()), C.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+@on_device
+def median_hh(dat, axis, ct=False, weight=None, work=None, out=None):
+    """Exact lower median of the magnitude of the Haar diagonal detail ((a - b) - c) + d of every 2 x 2 cell of the
+    planes orthogonal to ``axis`` of the (X, Y, Z) float32 device volume ``dat``, over the cells whose four voxels are
+    finite, non-zero (``ct`` False: > 0) and (``weight`` given) of weight > 0 (``unires_median_hh``).
+    Returns the (2,) float64 DEVICE tensor (median, N); nothing is read back."""
+    if not isinstance(dat, torch.Tensor) or dat.dim() != 3:
+        raise ValueError('unires_amd: dat must be an (X, Y, Z) tensor')
+    if axis not in (0, 1, 2):
+        raise ValueError('unires_amd: axis must be 0, 1 or 2')
+    fd = _flat(dat)
+    fw = None if weight is None else _flat(weight, 'weight')
+    if fw is not None and tuple(weight.shape) != tuple(dat.shape):
+        raise ValueError('unires_amd: a weight map must have the shape of its volume')
+    out = _out(out, fd.device)
+    work = _work(work, fd.device)
+    check(_lib.load().unires_median_hh(C.c_void_p(fd.data_ptr()), _lib.i3(dat.shape), int(axis), 1 if ct else 0,
+                                       None if fw is None else C.c_void_p(fw.data_ptr()), C.c_void_p(work.data_ptr()),
+                                       C.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def mad_sd(med):
+    """sd of the noise from the median of the Haar detail's magnitude, in float32: fl32(fl32(1.4826 med) 0.5) - the
+    detail of i.i.d. noise of variance s^2 has variance 4 s^2.  ``med``: a CPU scalar tensor; returns a float32 one."""
+    med = torch.as_tensor(med).detach().cpu().to(torch.float32)
+    return (torch.tensor(MAD_TO_SD, dtype=torch.float32) * med) * torch.tensor(0.5, dtype=torch.float32)
+
+
+def estimate_noise_mad(dat, axis, ct=False, weight=None):
+    """Noise sd of ``dat`` without a background class: ``(sd, N)`` with sd = ``mad_sd`` of ``median_hh``'s median (a
+    float32 CPU scalar) and N the number of cells ranked.  For background-free inputs (skull-stripped, masked, cropped);
+    with an air background the Rayleigh region pulls the estimate down, towards 0.655 sd."""
+    r = median_hh(dat, axis, ct, weight).cpu()
+    return mad_sd(r[0]), int(r[1])
 
 
 def _noise_params(row):

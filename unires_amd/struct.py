@@ -107,6 +107,13 @@ class settings:
         # real data.  Off: every voxel has weight 1 unless the user set _input.weight.
         self.voxel_robust = False
         self.voxel_k = 3.0
+        # what the Huber threshold is a multiple of.  'noise': the image-noise sd 1 / sqrt(tau), as above.  'mad': the
+        # robust sd of the residuals the rule judges, c = voxel_k 1.4826 median|x - A y| over the voxels with x != 0 and
+        # prior > 0, re-taken for every repeat at every re-estimate - an exact median on the device, no read-back
+        # (DESIGN 8.11).  Residuals carry model error too (slice profile, interpolation, partial volume), and tau may be
+        # wrong; 'mad' follows both.  No floor at the noise sd, tau is not re-estimated.  fit() reports the last scale
+        # of every repeat in info['voxel_scale'].  Any other name: ValueError in fit()
+        self.voxel_scale = 'noise'
         # the scaling and rigid Gauss-Newton updates (sett.scaling, sett.unified_rigid) carry the voxel weights of every
         # repeat that has some: both minimise the data term above (_update._update_scaling, _rigid._update_rigid).
         # Off: fit() refuses those two settings with voxel weights, and the update functions ignore xn.weight, as they
@@ -123,6 +130,12 @@ class settings:
         # did before it could read them.  A switch only because tests pin init()'s results with sett.weight set; not
         # a modelling choice - with a defect mask, turn it on
         self.voxel_init = False
+        # how init() estimates the noise sd (and so tau) of an observation.  'mixture': the reference's rule, the noise
+        # class of a two-class mixture fitted to the intensity histogram - it needs an air background.  'mad': 1.4826 / 2
+        # times the exact median magnitude of the in-plane Haar diagonal detail over the cells of usable voxels, and
+        # mu = |mean of the usable voxels| - for background-free inputs (skull-stripped, masked, cropped);
+        # WITH an air background it reads low, towards 0.655 sd.  Any other name: ValueError in init()
+        self.noise_est = 'mixture'
         self.gap = 0.0
         self.interpolation = 'linear'
         self.method = None
