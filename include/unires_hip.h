@@ -345,6 +345,27 @@ int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const float *x, void
  * the canonical axis behind `axis` and its direction follow the new orientation).  Errors: a bad n or axis
  * UNIRES_ERR_ARG; UNIRES_REGIME_IDENTITY UNIRES_ERR_UNSUPPORTED, as for the mask. */
 int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int32_t axis, const float *u_dev, void *stream);
+/* Per-slice intensity gains of repeat n's data term (no counterpart in the reference, whose even / odd scaling is one
+ * special case): e_dev = dim_x[axis] float32 ON THE DEVICE, one per slice along the caller's voxel axis `axis`, in the
+ * caller's slice order.  The data term becomes 1/2 tau_n sum_v W(v) (x(v) - e[s(v)] (A y)(v))^2 with W = g . u . m (the
+ * voxel weights, the slice weights and the mask, each 1 where the repeat has none): diag(e) sits in observation space
+ * after S(scl), beside diag(u) and diag(m), and commutes with them.  The plan applies A_n^T diag(W . e^2) A_n wherever
+ * it applied A_n^T diag(W) A_n - the matvec of unires_ata_matvec and of the CG solves, the Jacobi diagonal, the mean
+ * diagonal of the FFT preconditioner's symbol - and unires_rhs_assemble / unires_atx_assemble accumulate
+ * tau_n A_n^T (W . e . x_n).  unires_proj_apply keeps the reference's A, A^T and A^T A, without gains.
+ * The plan keeps the gains and two composed per-slice tables at fixed addresses,
+ *   w_mat[s] = fl32(fl64(fl64(u e) e)),  w_rhs[s] = fl32(fl64(u e))      (u = 1 without slice weights; u e is exact in
+ * float64), written by a one-workgroup kernel on `stream` whenever gains OR slice weights are set on a gained repeat; the
+ * passes of a weighted repeat take w_mat or w_rhs where they took u, so e = 1 gives the bits of the plan without gains.
+ * A gained repeat runs forward -> pass -> push and declines what a weighted repeat declines.  Call semantics as for
+ * unires_plan_set_slice_weights: a first set, a clear (e_dev == NULL) or a new axis rebuilds the repeat's tables where
+ * its kernel family changes, waits for the plan's earlier launches and drops the captured CG graphs; new VALUES rebuild
+ * nothing, wait for nothing and keep a captured solve, which reads the new tables when it is replayed.  Every set drops
+ * the built preconditioner.  unires_plan_set_repeat keeps the gains (the new descriptor must have the same dim_x).
+ * The values are not checked: e > 0 is the caller's contract.  Errors: a bad n or axis, or an axis that differs from
+ * the one the repeat's slice weights run along (and likewise slice weights set along another axis than the gains'),
+ * UNIRES_ERR_ARG; UNIRES_REGIME_IDENTITY UNIRES_ERR_UNSUPPORTED, as for the mask. */
+int unires_plan_set_slice_gains(unires_plan_t *plan, int32_t n, int32_t axis, const float *e_dev, void *stream);
 /* Per-voxel weights of repeat n's data term (no counterpart in the reference): g_dev = dim_x float32 ON THE DEVICE, one
  * per x-space voxel in the caller's layout (the observation's).  The data term becomes
  * 1/2 tau_n sum_v g(v) u[s(v)] m(v) (x - A y)^2(v) and the plan applies A_n^T diag(g . u . m) A_n wherever it applied
@@ -370,7 +391,7 @@ int64_t unires_plan_workspace_bytes(const unires_plan_t *plan);
  * j is reversed, info[4] = 1 if the LDS-window pull serves it, info[5] = 0 if the schedule-driven
  * splat does not serve it, else 2 + its conv_up axis (1: grid-space source, 2..4: along x / y / z, 5: all), info[6] bit 0 = the translation-only one-kernel
  * matvec serves it, bit 1 = the single-pass AtA kernel of the denoising regime does (ata1.hip), bit 2 = the repeat is masked (unires_plan_set_missing:
- * bits 0 and 1 are then clear), bit 3 = the repeat is weighted (unires_plan_set_slice_weights: bits 0 and 1 are then clear), bit 4 = the repeat is voxel-weighted (unires_plan_set_voxel_weights: bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
+ * bits 0 and 1 are then clear), bit 3 = the repeat is weighted (unires_plan_set_slice_weights: bits 0 and 1 are then clear), bit 4 = the repeat is voxel-weighted (unires_plan_set_voxel_weights: bits 0 and 1 are then clear), bit 5 = the repeat has slice gains (unires_plan_set_slice_gains: bits 0 and 1 are then clear), info[7] = 1 if the convolutions run as separable passes. */
 int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int32_t info[8]);
 /* The relabelling a plan applies to an operator with grid -> output affine M (host arithmetic only, no device
  * call): perm[j] = caller's voxel axis behind canonical axis j, flip[j] = 1 where it is reversed, chosen so that
@@ -536,6 +557,26 @@ int unires_slice_sums(const float *x, const float *ay, const int32_t dim[3], int
  * statement of a voxel-weighted repeat's data term: 1/2 tau sum_s u_s out_dev[s].  out_dev: 2 S doubles on the device. */
 int unires_voxel_sums(const float *x, const float *ay, const float *g, const int32_t dim[3], int32_t dim_thick,
                       double *out_dev, void *stream);
+
+/* The sums per slice that per-slice intensity gains are estimated from (no counterpart in the reference): with
+ * W(v) = g(v) u[s(v)] - g an x-space volume `dim` of weights or NULL (1), u dim[dim_thick] slice weights or NULL (1),
+ * all on the device - over the voxels of slice s with x != 0, S = dim[dim_thick]:
+ *   out_dev[s]       = sum W fl32(x ay)      (tau times this is P_s of the rule e_s = (P_s + kappa) / (Q_s + kappa))
+ *   out_dev[S + s]   = sum W fl32(ay ay)     (Q_s / tau)
+ *   out_dev[2 S + s] = sum W                 the slice's effective count
+ * ay is A y WITHOUT gains.  float32 terms; W is formed in float64, where g u is exact; the summand fl64(W t) is exact
+ * with one factor and rounded once with both (unires_scaling_sums_g's conventions); float64 sums added in a fixed order
+ * (no atomics: the same bits every run); every one of the 3 S entries is written.  out_dev: 3 S doubles on the device.
+ * tau is the caller's.  Errors as for unires_slice_sums. */
+int unires_gain_sums(const float *x, const float *ay, const float *g, const float *u, const int32_t dim[3],
+                     int32_t dim_thick, double *out_dev, void *stream);
+
+/* dst[v] = fl32(u[s(v)] src[v]) over a z-fastest volume `dim`, s(v) = v's index along `axis`, u dim[axis] floats on the
+ * device: the pass of a slice-weighted repeat on its own, without mask and without a `done` word (no counterpart in the
+ * reference).  dst == src: in place; dst != src: src is only read.  With the gains of a repeat as u it makes e . (A y),
+ * the prediction every residual sum and rule of a gained repeat is taken on.  Buffers off a 16-byte boundary are served
+ * voxel by voxel. */
+int unires_slice_apply(const float *src, float *dst, const float *u, const int32_t dim[3], int32_t axis, void *stream);
 
 /* The pass a voxel-weighted repeat runs between the forward half of A^T A and its push, on its own (no counterpart in
  * the reference): over a z-fastest volume `dim`

@@ -87,6 +87,7 @@ SIGNATURES = {
     'unires_plan_set_missing': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_plan_set_slice_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_plan_set_voxel_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_plan_set_slice_gains': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_plan_workspace_bytes': (C.c_int64, [C.c_void_p]),
     'unires_orient_of': (C.c_int, [c_f32x12, c_i32x3, c_i32x3]),
     'unires_plan_repeat_info': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32 * 8]),
@@ -139,6 +140,9 @@ SIGNATURES = {
     'unires_masked_sse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'unires_slice_sums': (C.c_int, [C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_voxel_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p]),
+    'unires_gain_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    'unires_slice_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p]),
     'unires_voxel_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'unires_voxel_huber':(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -82,6 +82,7 @@ class ChannelPlan:
         self._slice_w = [None] * len(repeats)  # per repeat: (weak reference, version, axis) of the weight tensor the plan holds, or None
         self.weights = False  # whether the plan was last fetched with the observations' slice weights (_channel_plan)
         self._voxel_w = [None] * len(repeats)  # per repeat: (weak reference, version) of the voxel-weight tensor the plan holds, or None
+        self._slice_e = [None] * len(repeats)  # per repeat: (weak reference, version, axis) of the gain tensor the plan holds, or None
         check(self.lib.unires_plan_create(C.byref(self._h), i3(self.dim_y), f3(vx_y), self.regime,
                                           len(repeats), arr, fov_tol))
         self.dims_x = [self.dim_y if self.regime == REGIME_IDENTITY else tuple(po.dim_x)
@@ -116,15 +117,15 @@ class ChannelPlan:
         voxel_weighted);
         ``fused``: the single-pass AtA kernel (denoising regime, ata1.hip) serves the CG matvec; ``masked``: the
         repeat has a validity mask (:meth:`set_missing`), ``weighted``: per-slice weights
-        (:meth:`set_slice_weights`), ``voxel_weighted``: per-voxel weights (:meth:`set_voxel_weights`) - ``shift`` and
-        ``fused`` are then False."""
+        (:meth:`set_slice_weights`), ``voxel_weighted``: per-voxel weights (:meth:`set_voxel_weights`), ``gained``:
+        per-slice gains (:meth:`set_slice_gains`) - ``shift`` and ``fused`` are then False."""
         info = (C.c_int32 * 8)()
         check(self.lib.unires_plan_repeat_info(self._h, int(n), info))
         v = list(info)
         return dict(perm=tuple(v[:3]), flip=tuple((v[3] >> j) & 1 for j in range(3)), pull2=bool(v[4]),
                     splat2_axis=None if v[5] == 0 else v[5] - 2, shift=bool(v[6] & 1), separable=bool(v[7]),
                     fused=bool(v[6] & 2), masked=bool(v[6] & 4), weighted=bool(v[6] & 8),
-                    voxel_weighted=bool(v[6] & 16))
+                    voxel_weighted=bool(v[6] & 16), gained=bool(v[6] & 32))
 
     @on_device
     def time_matvecs(self, on=True):
@@ -238,10 +239,55 @@ class ChannelPlan:
             self.set_slice_weights(n, axis, t)
 
     def _slice_key(self):
-        """The weights' part of :meth:`rhs_cached`'s key: (object, version) per repeat, slice weights then voxel
-        weights."""
+        """The weights' part of :meth:`rhs_cached`'s key: (object, version) per repeat, slice weights, then voxel
+        weights, then slice gains."""
         return (tuple(None if k is None else (id(k[0]()), k[1]) for k in self._slice_w),
-                tuple(None if k is None else (id(k[0]()), k[1]) for k in self._voxel_w))
+                tuple(None if k is None else (id(k[0]()), k[1]) for k in self._voxel_w),
+                tuple(None if k is None else (id(k[0]()), k[1]) for k in self._slice_e))
+
+    @on_device
+    def set_slice_gains(self, n, axis, e):
+        """Per-slice intensity gains of repeat n's data term (``unires_plan_set_slice_gains``): ``e`` a float32 device
+        tensor with one gain > 0 per slice along the caller's voxel axis ``axis`` (not checked here: ``fit`` validates
+        the user's once).  The observation is modelled as e . (A_n y): the plan's AtA_n becomes A_n^T diag(W e^2) A_n
+        and its right-hand side term A_n^T (W e . x_n), W the repeat's weights and mask; A and At of
+        :meth:`proj_apply` stay without gains.  ``e=None`` clears.  The plan keeps a copy: call again when the values
+        change (that rebuilds nothing, a captured solve reads the new values; a first set or a clear changes the
+        repeat's kernels).  The axis is the one the repeat's slice weights run along, where it has some."""
+        import weakref
+        n, axis = int(n), int(axis)
+        if not 0 <= n < self.n_repeats:
+            raise ValueError('unires_amd: repeat index out of range')
+        if axis not in (0, 1, 2):
+            raise ValueError('unires_amd: slice axis must be 0, 1 or 2')
+        if e is not None and (not e.is_cuda or e.dtype != torch.float32
+                              or tuple(e.shape) != (int(self.dims_x[n][axis]),)):
+            raise ValueError('unires_amd: slice gains must be a float32 device tensor of shape (%d,)'
+                             % int(self.dims_x[n][axis]))
+        self._slice_e[n] = None
+        self._atx = None  # (sum tau At (w e . x) follows the gains)
+        if e is None:
+            check(self.lib.unires_plan_set_slice_gains(self._h, n, axis, None, _stream()))
+            return
+        ec = e.contiguous()
+        check(self.lib.unires_plan_set_slice_gains(self._h, n, axis, _ptr(ec), _stream()))
+        self._slice_e[n] = (weakref.ref(e), e._version, axis)
+
+    def sync_slice_gains(self, es):
+        """:meth:`set_slice_gains` for every repeat whose gains are not the tensor, at the version and axis, the plan
+        holds (``es``: per repeat ``(axis, tensor)`` or None for a repeat without gains; ``es=None``: clear all).  Free
+        when nothing changed.  Runs on the current stream, like :meth:`sync_slice_weights`."""
+        for n in range(self.n_repeats):
+            want = None if es is None else es[n]
+            key = self._slice_e[n]
+            if want is None:
+                if key is not None:
+                    self.set_slice_gains(n, key[2], None)
+                continue
+            axis, t = want
+            if key is not None and key[0]() is t and key[1] == t._version and key[2] == int(axis):
+                continue
+            self.set_slice_gains(n, axis, t)
 
     @on_device
     def set_voxel_weights(self, n, g):

@@ -216,6 +216,13 @@ def _voxel_weights(x):
     return gs if any(g is not None for g in gs) else None
 
 
+def _slice_gains(x):
+    """Per repeat ``(axis, gains)`` or None, as ``ChannelPlan.sync_slice_gains`` takes them; None when no repeat of the
+    channel has gains."""
+    es = [None if getattr(xn, 'slice_gain', None) is None else (_slice_axis(xn), xn.slice_gain) for xn in x]
+    return es if any(e is not None for e in es) else None
+
+
 def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weights=None):
     """Fused per-channel plan, cached on the output struct and rebuilt when any
     operator parameter (rigid, scl, tau, dims) changed.  ``diff``: the difference of the plan's D
@@ -226,7 +233,8 @@ def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weigh
     ``weights``: True - the plan's A^T A and right-hand side carry the per-slice weights ``xn.slice_w`` of the repeats
     that have some (``ChannelPlan.set_slice_weights``; they follow the weight tensors and their versions); False -
     the unweighted operator; None leaves the plan as it is.  The per-voxel weights ``xn.weight``
-    (``ChannelPlan.set_voxel_weights``) go with them."""
+    (``ChannelPlan.set_voxel_weights``) and the per-slice gains ``xn.slice_gain`` (``ChannelPlan.set_slice_gains``) go
+    with them."""
     cached = getattr(y, '_plan', None)
     if mask_zeros is None:
         mask_zeros = cached[1].mask_zeros if cached is not None else False
@@ -234,13 +242,16 @@ def _channel_plan(x, y, method, do, vx_y=None, diff=None, mask_zeros=None, weigh
         weights = cached[1].weights if cached is not None else False
     ws = _slice_weights(x) if weights else None
     gs = _voxel_weights(x) if weights else None
+    es = _slice_gains(x) if weights else None
     # (regime A = I has no x-space intermediate for any of the passes: the denoising regime with the identity affine)
-    plan = _channel_plan_any(x, y, method, do, vx_y, bool(mask_zeros) or ws is not None or gs is not None)
+    plan = _channel_plan_any(x, y, method, do, vx_y,
+                             bool(mask_zeros) or ws is not None or gs is not None or es is not None)
     if diff is not None:
         plan.set_diff(diff)
     plan.sync_missing([xn.dat for xn in x] if mask_zeros else None)
     plan.sync_slice_weights(ws)
     plan.sync_voxel_weights(gs)
+    plan.sync_slice_gains(es)
     plan.mask_zeros, plan.weights = bool(mask_zeros), bool(weights)
     return plan
 

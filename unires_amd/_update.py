@@ -241,23 +241,50 @@ def _voxel_scale(sett):
     return name
 
 
+def _slice_gain(sett):
+    """sett.slice_gain (False where the settings object has none): per-slice intensity gains of every non-CT observation
+    are re-estimated after each ADMM iteration (``_update_slice_gains``)."""
+    return bool(getattr(sett, 'slice_gain', False))
+
+
+def _gained(Ay, xn, out=None):
+    """e . (A y): the prediction of a repeat with gains ``xn.slice_gain`` along ``po.dim_thick`` (``unires_slice_apply``,
+    one float32 product per voxel; out of place unless ``out`` is ``Ay``).  ``Ay`` itself where the repeat has none."""
+    e = getattr(xn, 'slice_gain', None)
+    if e is None:
+        return Ay
+    if not torch.is_tensor(e) or not e.is_cuda or e.dtype != torch.float32 or not e.is_contiguous() \
+            or e.numel() != int(Ay.shape[_slice_axis(xn)]):
+        raise ValueError('unires_amd: xn.slice_gain must be a contiguous float32 device tensor with one gain per slice, '
+                         'as fit() leaves it')
+    out = torch.empty_like(Ay) if out is None else out
+    check(_lib.load().unires_slice_apply(_ptr(Ay), _ptr(out), _ptr(e), i3(Ay.shape), _slice_axis(xn), _stream()))
+    return out
+
+
 @on_device
-def _slice_sums(x, y, sett, ays=None):
-    """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights: SSE_s = sum_{v in s,
-    x != 0} (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick`` (``unires_slice_sums``; float32
-    terms, float64 sums in a fixed order); for a repeat with voxel weights ``xn.weight`` both sums carry g(v)
-    (``unires_voxel_sums``: sum g (x - A y)^2 and the effective count sum g).  A y is computed once per repeat; the
-    result serves the objective (``_compute_nll``) and the rules (``_update_slice_weights``; ``_update_voxel_weights``
-    takes the A y itself from ``ays``, a dict filled here with (c, n): A y of the voxel-weighted repeats).  Nothing is
-    read back."""
+def _slice_sums(x, y, sett, ays=None, raw=None):
+    """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights or gains: SSE_s =
+    sum_{v in s, x != 0} (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick``
+    (``unires_slice_sums``; float32 terms, float64 sums in a fixed order); for a repeat with voxel weights
+    ``xn.weight`` both sums carry g(v) (``unires_voxel_sums``: sum g (x - A y)^2 and the effective count sum g).  A y
+    is computed once per repeat; the result serves the objective (``_compute_nll``) and the rules
+    (``_update_slice_weights``; ``_update_voxel_weights`` takes the A y itself from ``ays``, a dict filled here with
+    (c, n): A y of the voxel-weighted repeats).  For a repeat with gains ``xn.slice_gain`` the prediction is
+    e . (A y) throughout (``_gained``), and ``raw``, a dict, receives (c, n): its A y WITHOUT gains, which
+    ``_update_slice_gains`` estimates from.  Nothing is read back."""
     lib = _lib.load()
     out = {}
     for c in range(len(x)):
         for n, xn in enumerate(x[c]):
             g = getattr(xn, 'weight', None)
-            if getattr(xn, 'slice_w', None) is None and g is None:
+            if getattr(xn, 'slice_w', None) is None and g is None and getattr(xn, 'slice_gain', None) is None:
                 continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            if getattr(xn, 'slice_gain', None) is not None:
+                if raw is not None:
+                    raw[(c, n)] = Ay
+                Ay = _gained(Ay, xn)
             xd = xn.dat.contiguous()
             a = _slice_axis(xn)
             sums = torch.empty(2 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
@@ -308,6 +335,7 @@ def _update_voxel_weights(x, y, sett, ays=None):
             Ay = None if ays is None else ays.get((c, n))
             if Ay is None:
                 Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+                Ay = _gained(Ay, xn, out=Ay)  # (a repeat with gains: the residual is x - e . A y)
             xd = xn.dat.contiguous()
             prior = getattr(xn, '_weight_prior', None)
             if mad:
@@ -359,6 +387,69 @@ def _update_slice_weights(x, y, sett, sums=None):
     return x
 
 
+def gain_rule(sums, tau, kappa, gain_max):
+    """The gains of one observation from its ``unires_gain_sums`` ((3 S,) float64: sum W x a, sum W a^2, sum W per
+    slice, a = A y without gains): with P_s = tau sums[s] and Q_s = tau sums[S + s],
+    e_s = clamp((P_s + kappa) / (Q_s + kappa), 1 / gain_max, gain_max) - the exact minimiser over that interval of
+    1/2 tau sum_{v in s} W (x - e_s a)^2 + 1/2 kappa (e_s - 1)^2, a convex parabola in e_s.  A slice with
+    Q_s + kappa = 0 (no data, no prior) keeps e_s = 1.  ``kappa``: a float or a 0-d float64 tensor on the device of
+    ``sums``.  float64 tensor ops on that device, no read-back.  Returns (S,) float64."""
+    S = sums.numel() // 3
+    kappa = torch.as_tensor(kappa, dtype=torch.float64, device=sums.device)
+    P, Q = float(tau) * sums[:S] + kappa, float(tau) * sums[S:2 * S] + kappa
+    one = torch.ones_like(P)
+    e = torch.where(Q > 0, P / torch.where(Q > 0, Q, one), one)
+    return e.clamp(min=1.0 / float(gain_max), max=float(gain_max))
+
+
+@on_device
+def _gain_sums(xn, Ay):
+    """``unires_gain_sums`` of one repeat: (3 S,) float64 on the device, W = xn.weight . xn.slice_w (1 where None),
+    ``Ay`` its A y WITHOUT gains."""
+    xd = xn.dat.contiguous()
+    a = _slice_axis(xn)
+    g, u = getattr(xn, 'weight', None), getattr(xn, 'slice_w', None)
+    sums = torch.empty(3 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
+    check(_lib.load().unires_gain_sums(_ptr(xd), _ptr(Ay.contiguous()), None if g is None else _ptr(g.contiguous()),
+                                       None if u is None else _ptr(u.contiguous()), i3(xd.shape), a, _ptr(sums),
+                                       _stream()))
+    return sums
+
+
+def gain_kappa(xn, gain_reg):
+    """The precision of the gains' prior for one observation: kappa = gain_reg tau (sum_{x != 0} x^2) / K, K the number
+    of slices along ``po.dim_thick`` that hold a non-zero voxel - gain_reg times the Q_s a typical slice has at
+    e = 1.  A float64 sum on the device; returns a 0-d float64 device tensor (0 for an all-zero observation), not
+    read back."""
+    xd = xn.dat.double()
+    a = _slice_axis(xn)
+    K = (xn.dat != 0).sum(dim=[d for d in range(3) if d != a]).ne(0).sum()
+    return float(gain_reg) * float(xn.tau) * (xd * xd).sum() / K.clamp(min=1).double()
+
+
+@on_device
+def _update_slice_gains(x, y, sett, raw=None):
+    """Re-estimates the gains of every non-CT observation that has some by ``gain_rule``, from the current y and the
+    repeat's current weights (``raw``: what ``_slice_sums`` kept of A y WITHOUT gains for this y, computed here where
+    missing).  kappa is ``xn._gain_kappa``, which ``fit()`` fixes before the first iteration (computed here for a
+    direct call).  The gain tensors are updated in place: their version counters tell the plans
+    (``sync_slice_gains``, at the next y-update's plan fetch) and the cached sum tau At (w e . x).  No read-back."""
+    reg, gmax = float(getattr(sett, 'gain_reg', 0.1)), float(getattr(sett, 'gain_max', 2.0))
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            e = getattr(xn, 'slice_gain', None)
+            if e is None or getattr(xn, 'ct', False):
+                continue
+            Ay = None if raw is None else raw.get((c, n))
+            if Ay is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            if getattr(xn, '_gain_kappa', None) is None:
+                xn._gain_kappa = gain_kappa(xn, reg)
+            xn._gain_sums = _gain_sums(xn, Ay)  # (kept: what the last estimate was taken from)
+            e.copy_(gain_rule(xn._gain_sums, xn.tau, xn._gain_kappa, gmax))
+    return x
+
+
 def _slice_ll(tau, w, sums):
     """1/2 tau sum_s u_s SSE_s of one weighted repeat: ``w`` its (S,) weights, ``sums`` its ``unires_slice_sums``
     ((2 S,) float64: SSE_s, then N_s).  A float64 dot product on the device, no read-back.  The one statement of a
@@ -375,7 +466,8 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
     """Negative model log-likelihood (unires/_update.py:396-427); returns 0-d float64
     device tensors (nll_yx, nll_xy, nll_y) without synchronising.  A repeat with slice or voxel weights contributes
     1/2 tau sum_s u_s SSE_s (``slice_sums``: ``_slice_sums``' result for this y, computed here when None; SSE_s
-    carries g for a voxel-weighted repeat)."""
+    carries g for a voxel-weighted repeat, and is taken on e . A y for a repeat with gains).  Under ``sett.slice_gain``
+    the gains' prior 1/2 kappa sum_s (e_s - 1)^2 of every estimated repeat is part of the data term's value."""
     dev = y[0].dat.device
     if slice_sums is None:
         slice_sums = _slice_sums(x, y, sett)
@@ -387,6 +479,11 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
         for n in range(len(x[c])):
             if (c, n) in slice_sums:
                 nll_xy = nll_xy + _slice_ll(x[c][n].tau, getattr(x[c][n], 'slice_w', None), slice_sums[(c, n)])
+                e = getattr(x[c][n], 'slice_gain', None)
+                if e is not None and _slice_gain(sett) and not getattr(x[c][n], 'ct', False):
+                    if getattr(x[c][n], '_gain_kappa', None) is None:
+                        x[c][n]._gain_kappa = gain_kappa(x[c][n], getattr(sett, 'gain_reg', 0.1))
+                    nll_xy = nll_xy + 0.5 * x[c][n]._gain_kappa * ((e.double() - 1.0) ** 2).sum()
                 continue
             Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = x[c][n].dat.contiguous()
@@ -494,10 +591,13 @@ def _update_admm(x, y, z, w, rho, tmp, obj, n_iter, sett, info=None):
     # (the per-slice residual sums of the weighted repeats: once, for the objective and for the rules; A y of the
     # voxel-weighted repeats is kept for the Huber rule)
     ays = {} if _voxel_robust(sett) else None
-    sums = _slice_sums(x, y, sett, ays) if want_obj or _slice_robust(sett) else None
+    raw = {} if _slice_gain(sett) else None  # (A y without gains of the gained repeats, for the gain rule)
+    sums = _slice_sums(x, y, sett, ays, raw) if want_obj or _slice_robust(sett) or _slice_gain(sett) else None
     if want_obj:
         obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums)
     z, w, tmp = _update_zw(y, z, w, rho, tmp, sett)
+    if _slice_gain(sett):  # (before the rules below write their weights: it reads the W this iteration's y-update used;
+        _update_slice_gains(x, y, sett, raw)  # sums and ays keep the prediction e . A y of that y-update's gains)
     if _slice_robust(sett):  # (after the objective: each iteration's is taken with the weights its y-update used)
         _update_slice_weights(x, y, sett, sums)
     if _voxel_robust(sett):  # (likewise; A y is computed there where the sums above were not wanted)

@@ -640,6 +640,30 @@ extern "C" int unires_voxel_sums(const float *x, const float *ay, const float *g
   return UNIRES_OK;
 }
 
+extern "C" int unires_gain_sums(const float *x, const float *ay, const float *g, const float *u, const int32_t dim[3],
+                                int32_t dim_thick, double *out_dev, void *stream) {
+  if (!x || !ay || !dim || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (dim_thick < 0 || dim_thick > 2) return fail(UNIRES_ERR_ARG, "bad dim_thick");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  const size_t cols = 3 * (size_t)dim[dim_thick];
+  if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), dim_thick), &part)) return rc;
+  launch_gain_sums(x, ay, g, u, mk(dim), dim_thick, part, out_dev, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_slice_apply(const float *src, float *dst, const float *u, const int32_t dim[3], int32_t axis,
+                                  void *stream) {
+  if (!src || !dst || !u || !dim) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "slice axis: 0, 1 or 2");
+  launch_slice_apply(src, dst, nullptr, u, mk(dim), axis, false, nullptr, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 extern "C" int unires_voxel_apply(const float *src, float *dst, const float *g, const uint8_t *mask, const float *u,
                                   const int32_t dim[3], int32_t axis, int32_t flip, const int32_t *done, void *stream) {
   if (!src || !dst || !g || !dim) return fail(UNIRES_ERR_NULL, "null argument");

@@ -18,6 +18,7 @@
 #include "cg.hpp"
 #include "fftpre.hpp"
 #include "fused.hpp"
+#include "gain.hpp"
 #include "mask.hpp"
 #include "orient.hpp"
 #include "pull2.hpp"
@@ -175,19 +176,40 @@ struct RepeatVoxel {
   size_t g_cap = 0;  // entries of either allocation
 };
 
-struct Repeat : RepeatDesc, RepeatTables, RepeatMask, RepeatWeights, RepeatVoxel {
+// Per-slice intensity gains (unires_plan_set_slice_gains): e, one float per slice along the caller's axis e_axis, in the
+// caller's slice order, and the two tables composed from it and the slice weights u (1 where the repeat has none;
+// gain.hip: k_gain_compose): w_mat = u e^2, what the pass between the halves of A^T A multiplies by, and w_rhs = u e,
+// what the right-hand side's observation is multiplied by.  ONE allocation of three tables, as for the weights: the
+// passes are given the canonical axis and its direction, and no address changes while the repeat is gained - a
+// captured solve reads the values the tables hold when it runs.  Freed with the plan.
+struct RepeatGains {
+  bool gained = false;
+  float *e_dev = nullptr, *wm_dev = nullptr, *wr_dev = nullptr;
+  int e_axis = 0;
+  size_t e_cap = 0;  // entries of each table
+};
+
+struct Repeat : RepeatDesc, RepeatTables, RepeatMask, RepeatWeights, RepeatVoxel, RepeatGains {
   // the voxel weights in the layout the x-space intermediate of A^T A has
   const float *vox() const { return oriented ? g_c : g_u; }
   // the mask in the layout the x-space intermediate of A^T A has
   const uint8_t *mask() const { return oriented ? mask_c : mask_u; }
-  // a pass runs on the x-space intermediate of A^T A (mask, slice weights, voxel weights or any of them together): the
-  // intermediate has to exist, so the one-kernel matvecs, the single-pass AtA kernel and the hybrid forms are declined
-  bool mid() const { return masked || weighted || voxw; }
-  // the canonical axis the slices of w_axis run along, and whether the plan reversed it
+  // a pass runs on the x-space intermediate of A^T A (mask, slice weights, voxel weights, gains or any of them
+  // together): the intermediate has to exist, so the one-kernel matvecs, the single-pass AtA kernel and the hybrid
+  // forms are declined
+  bool mid() const { return masked || weighted || voxw || gained; }
+  // the per-slice factor of the pass between the halves of A^T A and of the right-hand side's observation: the slice
+  // weights, or a gained repeat's composed tables; nullptr: none
+  const float *w_mat() const { return gained ? wm_dev : (weighted ? w_dev : nullptr); }
+  const float *w_rhs() const { return gained ? wr_dev : (weighted ? w_dev : nullptr); }
+  // the caller's axis the slices of that factor are counted along (weights and gains of one repeat share it)
+  int s_axis() const { return gained && !weighted ? e_axis : w_axis; }
+  // the canonical axis the slices of s_axis() run along, and whether the plan reversed it
   int w_caxis() const {
+    const int a = s_axis();
     for (int j = 0; j < 3; ++j)
-      if (orient.perm[j] == w_axis) return j;
-    return w_axis;
+      if (orient.perm[j] == a) return j;
+    return a;
   }
   bool w_flip() const { return orient.flip[w_caxis()] != 0; }
 };

@@ -63,13 +63,14 @@ static void forward(unires_plan *pl, const Repeat &R, const float *in, const Sca
 // The pass on the x-space intermediate of a masked and / or weighted repeat's A^T A: A^T diag(u . m) A, mask and
 // weights in ONE pass (slice.hip); the mask alone stays k_mask_apply's.  diag(u) is diagonal in observation space like
 // diag(m) and commutes with it and with S.  `weights` false: the repeat's unweighted operator (unires_proj_apply's
-// UNIRES_OP_ATA, which stays the reference's).
+// UNIRES_OP_ATA, which stays the reference's).  A gained repeat (unires_plan_set_slice_gains) runs the same passes with
+// its table u e^2 where the others have u: A^T diag(g . u . e^2 . m) A.
 static void mid_pass(const Repeat &R, float *buf, bool weights, const int *done, hipStream_t st) {
+  const float *wm = R.w_mat();
   if (R.voxw && weights)  // (voxel weights: slice weights and mask in the same pass, voxel.hip)
-    launch_voxel_apply(buf, buf, R.vox(), R.masked ? R.mask() : nullptr, R.weighted ? R.w_dev : nullptr, R.dim_x,
-                       R.w_caxis(), R.w_flip(), done, st);
-  else if (R.weighted && weights)
-    launch_slice_apply(buf, buf, R.masked ? R.mask() : nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), done, st);
+    launch_voxel_apply(buf, buf, R.vox(), R.masked ? R.mask() : nullptr, wm, R.dim_x, R.w_caxis(), R.w_flip(), done, st);
+  else if (wm && weights)
+    launch_slice_apply(buf, buf, R.masked ? R.mask() : nullptr, wm, R.dim_x, R.w_caxis(), R.w_flip(), done, st);
   else if (R.masked)
     launch_mask_apply(buf, R.mask(), R.dim_x.numel(), done, st);
 }
@@ -221,20 +222,20 @@ static void at_accumulate(unires_plan *pl, const Repeat &R, const float *x, floa
     launch_axpy(alpha, x, out, pl->dy.numel(), st);  // caller initialised out
     return;
   }
-  const bool w = weights && R.weighted;
+  const float *wr = weights ? R.w_rhs() : nullptr;  // (a gained repeat: its table u e - the term is At_n(u . e . x))
+  const bool w = wr != nullptr;
   const bool v = weights && R.voxw;  // (g . u . x of a voxel-weighted repeat: one pass for both kinds of weight)
   if (R.oriented) {  // the caller's voxel layout -> the plan's
     launch_to_canonical(R.orient, x, R.dim_xu, pl->xperm, st);
     if (v)
-      launch_voxel_apply(pl->xperm, pl->xperm, R.g_c, nullptr, w ? R.w_dev : nullptr, R.dim_x, R.w_caxis(), R.w_flip(),
-                         nullptr, st);
-    else if (w) launch_slice_apply(pl->xperm, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
+      launch_voxel_apply(pl->xperm, pl->xperm, R.g_c, nullptr, wr, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
+    else if (w) launch_slice_apply(pl->xperm, pl->xperm, nullptr, wr, R.dim_x, R.w_caxis(), R.w_flip(), nullptr, st);
     x = pl->xperm;
   } else if (v) {
-    launch_voxel_apply(x, pl->xperm, R.g_u, nullptr, w ? R.w_dev : nullptr, R.dim_x, R.w_axis, false, nullptr, st);
+    launch_voxel_apply(x, pl->xperm, R.g_u, nullptr, wr, R.dim_x, R.s_axis(), false, nullptr, st);
     x = pl->xperm;
   } else if (w) {
-    launch_slice_apply(x, pl->xperm, nullptr, R.w_dev, R.dim_x, R.w_axis, false, nullptr, st);
+    launch_slice_apply(x, pl->xperm, nullptr, wr, R.dim_x, R.s_axis(), false, nullptr, st);
     x = pl->xperm;
   }
   PushEpilogue ep;

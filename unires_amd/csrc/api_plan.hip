@@ -407,6 +407,15 @@ static void free_weights(RepeatWeights &R) {
   R.w_cap = 0, R.weighted = false;
 }
 
+// the observation's length along the caller's axis `axis`: the number of slices a per-slice table has
+static int du_of(const Repeat &R, int axis) { return axis == 0 ? R.dim_xu.x : (axis == 1 ? R.dim_xu.y : R.dim_xu.z); }
+
+static void free_gains(RepeatGains &R) {
+  if (R.e_dev) (void)hipFree(R.e_dev);  // (one allocation: e, u e^2, u e)
+  R.e_dev = R.wm_dev = R.wr_dev = nullptr;
+  R.e_cap = 0, R.gained = false;
+}
+
 static void free_voxel(RepeatVoxel &R) {
   if (R.g_u) (void)hipFree(R.g_u);
   if (R.g_c) (void)hipFree(R.g_c);
@@ -525,7 +534,7 @@ extern "C" int unires_plan_destroy(unires_plan_t *plan) {
   if (plan->last_use) (void)hipEventDestroy(plan->last_use);
   drop_timing(plan);
   fftpre_destroy(plan->fft);
-  for (Repeat &R : plan->reps) free_tables(R), free_mask(R), free_weights(R), free_voxel(R);
+  for (Repeat &R : plan->reps) free_tables(R), free_mask(R), free_weights(R), free_voxel(R), free_gains(R);
   delete plan;
   return UNIRES_OK;
 }
@@ -608,6 +617,9 @@ extern "C" int unires_plan_set_repeat(unires_plan_t *plan, int32_t n,
     return fail(UNIRES_ERR_DIM, "a weighted repeat keeps its observation's dims (clear the weights first)");
   if (plan->reps[n].voxw && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
     return fail(UNIRES_ERR_DIM, "a voxel-weighted repeat keeps its observation's dims (clear the weights first)");
+  // (and the gains, with the tables composed from them: per slice in the caller's order, like the slice weights)
+  if (plan->reps[n].gained && memcmp(&tmp.dim_xu, &plan->reps[n].dim_xu, sizeof(Dim3i)))
+    return fail(UNIRES_ERR_DIM, "a gained repeat keeps its observation's dims (clear the gains first)");
   if (plan->regime != UNIRES_REGIME_IDENTITY &&
       (tmp.dim_g.numel() > plan->cap_g || tmp.dim_x.numel() > plan->cap_x))
     return fail(UNIRES_ERR_DIM, "new repeat exceeds the plan's workspace");
@@ -736,6 +748,8 @@ extern "C" int unires_plan_set_missing(unires_plan_t *plan, int32_t n, const flo
 //     iteration under sett.slice_robust, which changes the values every iteration.)  The preconditioner is dropped:
 //     the Jacobi diagonal and the FFT symbol's mean follow u; it is rebuilt into the same allocations.
 // The values are not looked at (they are on the device): u >= 0 is the caller's contract.
+// On a gained repeat (unires_plan_set_slice_gains) every call also composes the tables u e^2 and u e again, on the same
+// stream behind the copy, and an axis other than the gains' is refused.
 extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int32_t axis, const float *u_dev,
                                              void *stream) {
   if (!plan) return fail(UNIRES_ERR_NULL, "null plan");
@@ -747,6 +761,8 @@ extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int
                 "identity affine");
   Repeat &R = plan->reps[n];
   if (!u_dev && !R.weighted) return UNIRES_OK;
+  if (u_dev && R.gained && axis != R.e_axis)
+    return fail(UNIRES_ERR_ARG, "slice weights and slice gains of a repeat run along the same axis");
   hipStream_t st = (hipStream_t)stream;
   const bool was = R.weighted, was_mid = R.mid();
   const int was_axis = R.w_axis;
@@ -774,6 +790,10 @@ extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int
   } else {
     R.weighted = false;
   }
+  if (R.gained) {  // (its tables u e^2 and u e follow the weights, on the same stream behind the copy)
+    mark_use(plan, st);
+    launch_gain_compose(R.weighted ? R.w_dev : nullptr, R.e_dev, du_of(R, R.e_axis), R.wm_dev, R.wr_dev, st);
+  }
   if (was_mid != R.mid()) {  // (a masked repeat has the two-kernel family already)
     if (int rc = refamily(plan, R)) {
       // the tables of the new family could not be built: back to the state before the call
@@ -782,6 +802,68 @@ extern "C" int unires_plan_set_slice_weights(unires_plan_t *plan, int32_t n, int
       return rc;
     }
   }
+  return UNIRES_OK;
+}
+
+// Per-slice intensity gains of repeat n's data term: e_dev holds one float per slice along the caller's axis `axis`, on
+// the device.  The data term becomes 1/2 tau sum_v W (x - e[s(v)] (A y)(v))^2, W = g . u . m: the plan's A^T A becomes
+// A^T diag(W . e^2) A and its right-hand side term A^T (W . e . x).  The plan copies the gains into a buffer of its own
+// and composes two tables beside it, u e^2 and u e (u = 1 without slice weights; gain.hip), which the passes of a
+// weighted repeat take where they took u (api_operator.hip: mid_pass, at_accumulate).  Call semantics as for the slice
+// weights: a first set, a clear or a new axis changes the repeat's forms - the plan's earlier launches are waited for,
+// the captured solves go, the tables are rebuilt where the family differs; new values rebuild nothing and wait for
+// nothing - copy and compose are enqueued on `stream`, and a captured solve, which has the tables' addresses baked in,
+// is KEPT and reads the new values when it is replayed.  Every set drops the built preconditioner.  The values are not
+// looked at: e > 0 is the caller's contract.
+extern "C" int unires_plan_set_slice_gains(unires_plan_t *plan, int32_t n, int32_t axis, const float *e_dev,
+                                           void *stream) {
+  if (!plan) return fail(UNIRES_ERR_NULL, "null plan");
+  if (n < 0 || n >= (int)plan->reps.size()) return fail(UNIRES_ERR_ARG, "repeat index");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "slice axis: 0, 1 or 2");
+  if (plan->regime == UNIRES_REGIME_IDENTITY)
+    return fail(UNIRES_ERR_UNSUPPORTED,
+                "regime A = I has no x-space intermediate to scale: build the plan in the denoising regime with the "
+                "identity affine");
+  Repeat &R = plan->reps[n];
+  if (!e_dev && !R.gained) return UNIRES_OK;
+  if (e_dev && R.weighted && axis != R.w_axis)
+    return fail(UNIRES_ERR_ARG, "slice gains run along the axis of the repeat's slice weights");
+  hipStream_t st = (hipStream_t)stream;
+  const bool was = R.gained, was_mid = R.mid();
+  const int was_axis = R.e_axis;
+  const bool values_only = e_dev && was && axis == R.e_axis;
+  plan->prec_ready = false;
+  if (!values_only) {
+    await_use(plan);
+    drop_cg_graph(plan);
+  }
+  if (e_dev) {
+    const size_t cap = (size_t)std::max(R.dim_xu.x, std::max(R.dim_xu.y, R.dim_xu.z));
+    if (R.e_cap < cap) {  // (never while the repeat is gained: its dims are kept, and the tables were sized for them)
+      free_gains(R);
+      if (was_mid != R.mid()) (void)refamily(plan, R);  // (the old gains are gone with their allocation)
+      if (hipMalloc((void **)&R.e_dev, 3 * cap * sizeof(float)) != hipSuccess) {
+        R.e_dev = nullptr;
+        return fail(UNIRES_ERR_ALLOC, "hipMalloc slice gains");
+      }
+      R.wm_dev = R.e_dev + cap, R.wr_dev = R.e_dev + 2 * cap, R.e_cap = cap;
+    }
+    mark_use(plan, st);
+    HIP_TRY(hipMemcpyAsync(R.e_dev, e_dev, (size_t)du_of(R, axis) * sizeof(float), hipMemcpyDeviceToDevice, st));
+    launch_gain_compose(R.weighted ? R.w_dev : nullptr, R.e_dev, du_of(R, axis), R.wm_dev, R.wr_dev, st);
+    R.gained = true, R.e_axis = axis;
+  } else {
+    R.gained = false;
+  }
+  if (was_mid != R.mid()) {  // (a masked or weighted repeat has the two-kernel family already)
+    if (int rc = refamily(plan, R)) {
+      // the tables of the new family could not be built: back to the state before the call
+      R.gained = was, R.e_axis = was_axis;
+      (void)refamily(plan, R);
+      return rc;
+    }
+  }
+  CHECK_LAUNCH();
   return UNIRES_OK;
 }
 
@@ -919,7 +1001,7 @@ extern "C" int unires_plan_repeat_info(const unires_plan_t *plan, int32_t n, int
   info[5] = R.sched.valid ? 2 + R.sched.axis : 0;
   // (the forms the matvec takes: a masked or weighted repeat skips the one-kernel matvec and the single-pass AtA kernel)
   info[6] = (R.shift.valid && !R.mid() ? 1 : 0) | (R.f1.valid && !R.mid() ? 2 : 0) | (R.masked ? 4 : 0) |
-            (R.weighted ? 8 : 0) | (R.voxw ? 16 : 0);
+            (R.weighted ? 8 : 0) | (R.voxw ? 16 : 0) | (R.gained ? 32 : 0);
   info[7] = R.sep ? 1 : 0;
   return UNIRES_OK;
 }

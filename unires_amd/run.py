@@ -78,6 +78,56 @@ def _init_slice_weights(x, sett, dev):
             xn.slice_w = w.clone() if w is xn.slice_w else w
 
 
+def _init_slice_gains(x, sett, dev):
+    """The observations' slice gains as the iterations take them: a user's ``_input.slice_gain`` validated (one gain
+    per slice along ``po.dim_thick``, real, finite, > 0 - the one read-back) and moved to the device as float32; with
+    ``sett.slice_gain`` every non-CT repeat starts from its own, or from ones where it has none, so that the plans'
+    kernels do not change mid-fit, and the precision kappa of its gains' prior is fixed here (``gain_kappa``), so that
+    the objective is one function for the whole fit.  The even / odd scaling is a special case of the gains and the
+    rigid update's residual does not carry them: both settings are refused by name."""
+    from ._project import _slice_axis
+    from ._update import gain_kappa
+    on = bool(getattr(sett, 'slice_gain', False))
+    if not on and all(getattr(xn, 'slice_gain', None) is None for xc in x for xn in xc):
+        for xc in x:
+            for xn in xc:
+                xn._gain_kappa = None
+        return
+    if getattr(sett, 'scaling', False):
+        raise ValueError('sett.scaling with slice gains (_input.slice_gain, sett.slice_gain): the even / odd slice '
+                         'scaling is a special case of the per-slice gains - use one of the two')
+    if getattr(sett, 'unified_rigid', False):
+        raise NotImplementedError('sett.unified_rigid with slice gains (_input.slice_gain, sett.slice_gain): the '
+                                  'rigid Gauss-Newton update\'s residual does not carry per-slice gains yet')
+    if on and not float(getattr(sett, 'gain_reg', 0.1)) >= 0:
+        raise ValueError('sett.gain_reg must be >= 0')
+    if on and not float(getattr(sett, 'gain_max', 2.0)) > 1:
+        raise ValueError('sett.gain_max must be > 1')
+    for c, xc in enumerate(x):
+        for n, xn in enumerate(xc):
+            xn._gain_kappa = None
+            est = on and not getattr(xn, 'ct', False)
+            e = getattr(xn, 'slice_gain', None)
+            S = int(xn.dat.shape[_slice_axis(xn)])
+            if e is None:
+                if est:
+                    xn.slice_gain = torch.ones(S, dtype=torch.float32, device=dev)
+            else:
+                e = given = torch.as_tensor(e)
+                if tuple(e.shape) != (S,):
+                    raise ValueError('x[%d][%d].slice_gain has shape %s, expected (%d,): one gain per slice along axis %d'
+                                     % (c, n, tuple(e.shape), S, _slice_axis(xn)))
+                if e.is_complex() or e.dtype == torch.bool:
+                    raise ValueError('x[%d][%d].slice_gain must be real numbers' % (c, n))
+                e = e.detach().to(device=dev, dtype=torch.float32).contiguous()
+                if not bool((torch.isfinite(e) & (e > 0)).all()):
+                    raise ValueError('x[%d][%d].slice_gain must be finite and > 0' % (c, n))
+                # (estimated gains are written in place: never into the user's memory)
+                xn.slice_gain = e.clone() if est and e.data_ptr() == given.data_ptr() else e
+            if est:
+                xn._gain_kappa = gain_kappa(xn, getattr(sett, 'gain_reg', 0.1))
+
+
 def _init_voxel_weights(x, sett, dev):
     """The observations' voxel weights as the iterations take them: a user's ``_input.weight`` validated (the
     observation's shape, real, finite, >= 0 - the one read-back) and moved to the device as contiguous float32.  With
@@ -139,7 +189,13 @@ def fit(x, y, sett):
     repeat without weights, and ``voxel_w``: likewise each repeat's final voxel weights (``_input.weight``,
     ``sett.voxel_robust``) as the DEVICE float32 tensor the iterations used, or None, and ``voxel_scale``: likewise each
     repeat's last robust residual scale 1.4826 median|x - A y| (a float32 CPU scalar) under ``sett.voxel_robust`` with
-    ``sett.voxel_scale = 'mad'``, else None.
+    ``sett.voxel_scale = 'mad'``, else None, and ``slice_gain``: likewise each repeat's final per-slice intensity gains
+    (``_input.slice_gain``, ``sett.slice_gain``; a CPU float32 tensor, one per slice along ``po.dim_thick``) or None.
+
+    Slice gains model an observation as e[s(v)] (A y)(v) (banding).  Under ``sett.slice_gain`` they are re-estimated
+    after every ADMM iteration's z / w update, before the slice and voxel rules write their weights, against a ridge
+    towards 1 whose precision is fixed here for the whole fit; the objective carries that ridge.  ``sett.scaling``
+    (ValueError) and ``sett.unified_rigid`` (NotImplementedError) are refused with gains, by name.
 
     Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
@@ -155,6 +211,7 @@ def fit(x, y, sett):
         dev = y[0].dat.device
         _init_slice_weights(x, sett, dev)
         _init_voxel_weights(x, sett, dev)
+        _init_slice_gains(x, sett, dev)
         N = sum(len(xc) for xc in x)
         sett = _get_sched(N, sett)
         cnt_scl = 0
@@ -212,8 +269,10 @@ def fit(x, y, sett):
         meds = iter(torch.stack(meds)[:, 0].cpu().float() if meds else ())
         voxel_scale = [[None if xn._voxel_scale is None or n_done == 0
                         else torch.tensor(MAD_TO_SD, dtype=torch.float32) * next(meds) for xn in xc] for xc in x]
+        slice_gain = [[None if getattr(xn, 'slice_gain', None) is None else xn.slice_gain.detach().cpu() for xn in xc]
+                      for xc in x]
         info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w,
-                    voxel_w=voxel_w, voxel_scale=voxel_scale)
+                    voxel_w=voxel_w, voxel_scale=voxel_scale, slice_gain=slice_gain)
         return dat_y, y[0].mat, R, info
 
 

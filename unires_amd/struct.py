@@ -32,6 +32,13 @@ class _input:
         # They enter the y-update and the objective, and with sett.voxel_gn the scaling and rigid Gauss-Newton updates;
         # without it sett.scaling and sett.unified_rigid are refused with them
         self.weight = None
+        # per-slice intensity gains of the data term, float32 (dim[po.dim_thick],), > 0: None - every slice has gain 1.
+        # The observation is modelled as e[s(v)] (A y)(v): a slice that came out a few per cent brighter or darker than
+        # its neighbours (banding) keeps its information.  Set before fit() where the gains are known (used as given
+        # with sett.slice_gain off; fit() validates them once and moves them to the device); with sett.slice_gain
+        # fit() starts from them, or from ones where None, and re-estimates them every ADMM iteration.  They enter the
+        # y-update and the objective; sett.scaling and sett.unified_rigid are refused with them
+        self.slice_gain = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
         self.fname = None
@@ -120,6 +127,18 @@ class settings:
         # did before the updates could carry them.  A switch only because that refusal is pinned by a test; not a
         # modelling choice - with voxel weights and either update, turn it on
         self.voxel_gn = False
+        # build-side knobs: banding correction.  slice_gain: every non-CT observation gets one intensity gain per slice
+        # along po.dim_thick, re-estimated after every ADMM iteration (_update._update_slice_gains): the exact minimiser
+        # of 1/2 tau sum_v W (x - e_s A y)^2 + 1/2 kappa (e_s - 1)^2 over [1 / gain_max, gain_max], W the repeat's
+        # weights and mask.  kappa = gain_reg tau (sum_{x != 0} x^2) / (slices with data), fixed for a whole fit().  The
+        # reference's sett.scaling (one exp(+-s) for even / odd slices) is a special case and is refused with it, and so
+        # is sett.unified_rigid, whose residual does not carry gains.  A factor common to all gains of a repeat trades
+        # against y; the ridge towards 1 bounds it and does not remove it.  gain_reg = 0.1 and
+        # gain_max = 2 are UNTUNED modelling defaults: nobody has chosen them on real data.  Off: every slice has gain 1
+        # unless the user set _input.slice_gain
+        self.slice_gain = False
+        self.gain_reg = 0.1
+        self.gain_max = 2.0
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
