@@ -571,6 +571,21 @@ int unires_voxel_sums(const float *x, const float *ay, const float *g, const int
 int unires_gain_sums(const float *x, const float *ay, const float *g, const float *u, const int32_t dim[3],
                      int32_t dim_thick, double *out_dev, void *stream);
 
+/* Terms of the rigid Gauss-Newton step of a repeat with per-slice gains e (S = dim[axis] floats, > 0), g a volume or
+ * NULL (1), u S floats or NULL (1), all on the device (no counterpart in the reference).  p = fl32(e[s] ay) is formed in
+ * registers and never stored.
+ *   sums_dev[s]     = sum_{v in s, x != 0} [g] (x - p)^2    unires_slice_sums' terms (g NULL) / unires_voxel_sums' (g)
+ *   sums_dev[S + s] = the count / effective count, as those two write it
+ *   out (NULL: not written) = t[s] (p - x), masked where x == 0 or p == 0 (+0 there), t[s] = fl32(fl64(u[s]) fl64(e[s]))
+ *                  (u NULL: t = e): unires_rigid_resid's / unires_rigid_resid_g's roundings with u := t, ay := p
+ * Bit for bit what unires_slice_apply(ay, e) -> P, unires_slice_sums(x, P) / unires_voxel_sums(x, P, g) and
+ * unires_rigid_resid(x, P, u := t) / unires_rigid_resid_g(x, P, g, u := t) give, in one pass over x, ay [and g]; no
+ * atomics: the same bits every run.  out == NULL is a line-search evaluation (nothing but 2 S doubles is written).
+ * out == ay is allowed; x, g, u, e are only read (out == x or out == g: UNIRES_ERR_ARG).  Errors as for
+ * unires_slice_sums.  sums_dev: 2 S doubles on the device. */
+int unires_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e,
+                         const int32_t dim[3], int32_t axis, double *sums_dev, float *out, void *stream);
+
 /* dst[v] = fl32(u[s(v)] src[v]) over a z-fastest volume `dim`, s(v) = v's index along `axis`, u dim[axis] floats on the
  * device: the pass of a slice-weighted repeat on its own, without mask and without a `done` word (no counterpart in the
  * reference).  dst == src: in place; dst != src: src is only read.  With the gains of a repeat as u it makes e . (A y),

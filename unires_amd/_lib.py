@@ -142,6 +142,8 @@ SIGNATURES = {
     'unires_voxel_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p, C.c_void_p]),
     'unires_gain_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
+    'unires_rigid_terms_e': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     'unires_slice_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p]),
     'unires_voxel_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),

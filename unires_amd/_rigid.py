@@ -24,7 +24,7 @@ from ._host import light_host
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
 from ._project import _apply_scaling, _proj_info, _slice_axis, _taps, _thick_axis
-from ._update import _gn_weight, _slice_ll
+from ._update import _check_gain, _gn_gain, _gn_weight, _slice_ll
 from .spatial import _m12
 
 _F64 = torch.float64
@@ -104,7 +104,7 @@ def _grid_matrix(po, rigid, method):
 
 
 @on_device
-def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None, weight=None):
+def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None, weight=None, gain=None):
     """ll and, if ``diff``, the raw ingredients of the derivatives: gr3 (dim,3) = grid_grad,
     dg (dim) = residual in grid space.
 
@@ -118,7 +118,15 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     ``dat_x`` is), or None; ``axis`` is then the repeat's slice axis whether or not it has slice weights.  The terms are
     those of 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - A y)^2: ll = 1/2 tau sum_s u_s SSE_s with SSE_s from
     ``unires_voxel_sums``, which carries g - the statement ``_compute_nll`` takes a voxel-weighted repeat's term from -
-    and the residual g u[s(v)] (A y - x), masked, in one pass (``unires_rigid_resid_g``)."""
+    and the residual g u[s(v)] (A y - x), masked, in one pass (``unires_rigid_resid_g``).
+
+    ``gain``: the repeat's slice gains along ``axis`` (float32, on the device, one per slice of ``dat_x`` - already
+    decimated where ``dat_x`` is), or None.  The terms are those of 1/2 tau sum_v g(v) u[s(v)] [x != 0] (x - e[s(v)] A y)^2
+    (g, u = 1 where None) on the gained prediction p = fl32(e A y), which is formed in registers and never stored: one
+    pass (``unires_rigid_terms_e``) gives the slice sums of x - p - ll = 1/2 tau sum_s u_s SSE_s by ``_slice_ll``, to the
+    bit ``_compute_nll``'s term of the repeat - and, with ``diff``, the residual g u e (p - x), masked where x or p is 0:
+    the factor e is the chain rule through diag(e).  The ridge 1/2 kappa sum (e - 1)^2 of ``sett.slice_gain`` does not
+    depend on the rigid parameters and is left out of ll."""
     method = sett.method
     lib = _lib.load()
     mat, dim = _grid_matrix(po, rigid, method)
@@ -128,7 +136,24 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
         scl = float(po.scl)
         dat_yx = _ops.conv_down(dat_yx, _taps(po), po.ratio, scl, po.dim_thick)
     dat_yx = dat_yx.reshape(tuple(dat_x.shape))
-    if weight is not None:
+    if gain is not None:
+        dat_x, dat_yx = dat_x.contiguous(), dat_yx.contiguous()
+        _check_gain(gain, dat_x.shape[axis])
+        if weight is not None:
+            weight = weight.contiguous()
+            if weight.dtype != torch.float32 or tuple(weight.shape) != tuple(dat_x.shape):
+                raise ValueError('weight: one float32 weight per voxel of dat_x')
+        if slice_w is not None:
+            slice_w = slice_w.contiguous()
+            if slice_w.dtype != torch.float32 or slice_w.numel() != dat_x.shape[axis]:
+                raise ValueError('slice_w: one float32 weight per slice of dat_x along axis %d' % axis)
+        sums = torch.empty(2 * int(dat_x.shape[axis]), dtype=_F64, device=dat_x.device)
+        # (with diff the residual goes over A y in place: A y is not needed again)
+        check(lib.unires_rigid_terms_e(_ptr(dat_x), _ptr(dat_yx), None if weight is None else _ptr(weight),
+                                       None if slice_w is None else _ptr(slice_w), _ptr(gain), i3(dat_x.shape), axis,
+                                       _ptr(sums), _ptr(dat_yx) if diff else None, _stream()))
+        ll = _slice_ll(tau, slice_w, sums)
+    elif weight is not None:
         dat_x, dat_yx, weight = dat_x.contiguous(), dat_yx.contiguous(), weight.contiguous()
         if weight.dtype != torch.float32 or tuple(weight.shape) != tuple(dat_x.shape):
             raise ValueError('weight: one float32 weight per voxel of dat_x')
@@ -154,7 +179,9 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     if not diff:
         return ll, None, None
     gr3 = _ops.pull_grad_affine(dat_y, M, dim).reshape(dim + (3,))
-    if weight is not None:
+    if gain is not None:
+        d = dat_yx  # (written above, with the sums)
+    elif weight is not None:
         d = dat_yx  # (in place: A y is not needed again)
         check(lib.unires_rigid_resid_g(_ptr(dat_x), _ptr(dat_yx), _ptr(weight), i3(dat_x.shape), axis,
                                        None if slice_w is None else _ptr(slice_w), _ptr(d), _stream()))
@@ -171,14 +198,16 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
 
 
 @on_device
-def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None, weight=None):
+def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None, weight=None,
+                 gain=None):
     """Rigid matching term with the reference's return shapes (unires/_update.py:448-538):
     ll, gr (dim, 3) = grid_grad * residual, Hes (dim, 6) = outer(grid_grad) [* CtC].
     ``slice_w``: the observation's slice weights along ``po.dim_thick`` (``_rigid_terms``); ``weight``: its voxel
-    weights, the shape of ``dat_x``; the Hessian's weight is the caller's ``CtC`` (``_ctc`` with the same weights)."""
-    weighted = slice_w is not None or weight is not None
+    weights, the shape of ``dat_x``; ``gain``: its slice gains along ``po.dim_thick``; the Hessian's weight is the
+    caller's ``CtC`` (``_ctc`` with the same weights and gains)."""
+    weighted = slice_w is not None or weight is not None or gain is not None
     ll, gr3, d = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=diff, slice_w=slice_w,
-                              axis=_thick_axis(po) if weighted else None, weight=weight)
+                              axis=_thick_axis(po) if weighted else None, weight=weight, gain=gain)
     if not diff:
         return ll, None, None
     Hes = torch.stack([gr3[..., 0] * gr3[..., 0], gr3[..., 1] * gr3[..., 1], gr3[..., 2] * gr3[..., 2],
@@ -204,11 +233,23 @@ def _voxel_times(src, weight, slice_w, axis):
     return src
 
 
-def _ctc(po, dim, device, slice_w=None, axis=None, weight=None):
+def _gain_w_mat(slice_w, gain):
+    """The Hessian's slice factor of a gained repeat: w_mat[s] = fl32(fl64(fl64(u e) e)), the table the plan's A^T A
+    applies between its halves (``k_gain_compose``'s roundings: u e is exact in float64, u e e rounded there once, then
+    once more to float32); u = 1 where ``slice_w`` is None."""
+    ev = gain.double()
+    ue = ev if slice_w is None else slice_w.double() * ev
+    return (ue * ev).float().contiguous()
+
+
+def _ctc(po, dim, device, slice_w=None, axis=None, weight=None, gain=None):
     """conv_transpose(conv(1)) (unires/_update.py:603-607); with slice weights conv_transpose(u . conv(1)): the
     weights applied in x space between the two halves (times 1 is exact: u = 1 gives the unweighted bits).  With voxel
     weights ``weight`` (contiguous float32, the decimated observation's shape) conv_transpose(W . conv(1)), W = g or
-    g u[s(v)]: one pass and one rounding (``_voxel_times``; g = 1 gives the bits of the form above)."""
+    g u[s(v)]: one pass and one rounding (``_voxel_times``; g = 1 gives the bits of the form above).  With slice
+    gains ``gain`` the slice factor is w_mat = u e^2 in the place of u (``_gain_w_mat``): W e^2 per voxel."""
+    if gain is not None:
+        slice_w = _gain_w_mat(slice_w, gain)
     ones = torch.ones(dim, dtype=torch.float32, device=device)
     low = _ops.conv_down(ones, _taps(po), po.ratio)
     if weight is not None:
@@ -234,7 +275,16 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
     [x != 0] (x - A y)^2 in the same way: the map is decimated as the data are (``g[::sk[0], ::sk[1], ::sk[2]]``, cut
     to ``dim_x``), the Hessian's weight is conv_transpose(W . conv(1)) with W = g or g u[s(v)] - the volume W in the
     denoising regime - and a map that is all zero leaves the repeat alone.  Without ``sett.voxel_gn`` the map is
-    ignored, as it was before the update could carry it."""
+    ignored, as it was before the update could carry it.
+
+    With ``sett.gain_gn`` a repeat with slice gains (``xn.slice_gain``) takes its step on 1/2 tau sum_v W [x != 0]
+    (x - e[s(v)] A y)^2, W = g u (1 where the repeat has none, g only with ``sett.voxel_gn``): the gains are decimated
+    with the observation as u is (``e[::sk[a]][:dim_x[a]]``); objective and residual W e (e A y - x) come from one
+    pass on the gained prediction (``unires_rigid_terms_e``), and the Hessian's weight is W e^2 - the forms above with
+    w_mat = fl32(fl64(fl64(u e) e)) in the place of u, built once per repeat and call.  ll and sll are the data term
+    alone: the ridge of ``sett.slice_gain`` does not depend on the rigid parameters.  The all-weights-zero rule
+    applies unchanged.  Without ``sett.gain_gn`` the gains are ignored, as they were before the update could carry
+    them."""
     lib = _lib.load()
     dev = yc.dat.device
     method = sett.method
@@ -263,26 +313,32 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
         u = getattr(xn, 'slice_w', None)
         g = _gn_weight(xn, sett)
         a = _slice_axis(xn)
+        e = _gn_gain(xn, sett)
         if u is not None:
             u = u[::sk[a]][:po.dim_x[a]].contiguous()
+        uh = u  # (the Hessian's slice factor: u, or w_mat = u e^2 for a gained repeat, once per repeat and call)
+        if e is not None:
+            e = e[::sk[a]][:po.dim_x[a]].contiguous()
+            uh = _gain_w_mat(u, e)
         if g is not None:
             # (the map decimated as the data are; the Hessian's weight W = g [u] once per repeat and call)
             g = g[::sk[0], ::sk[1], ::sk[2]][:po.dim_x[0], :po.dim_x[1], :po.dim_x[2]].contiguous()
             if method == 'super-resolution':
-                CtC = _ctc(po, dim, dev, u, a, weight=g)
+                CtC = _ctc(po, dim, dev, uh, a, weight=g)
             else:
-                CtC = g if u is None else _voxel_times(torch.ones_like(g), g, u, a)
-        elif u is None:
+                CtC = g if uh is None else _voxel_times(torch.ones_like(g), g, uh, a)
+        elif uh is None:
             CtC = _ctc(po, dim, dev) if method == 'super-resolution' else None
         else:
-            CtC = _ctc(po, dim, dev, u, a) if method == 'super-resolution' else _spread(u, dat_x.shape, a).contiguous()
+            CtC = _ctc(po, dim, dev, uh, a) if method == 'super-resolution' else _spread(uh, dat_x.shape, a).contiguous()
         empty = False
         ll = torch.zeros((), dtype=_F64, device=dev)
         rigid = _expm(q, basis)
         for _gn in range(max_niter_gn):
             rigid, d_rigid = _expm(q, basis, grad_X=True)
             D = torch.stack([torch.linalg.solve(po.mat_y, d_rigid[i].mm(mat)) for i in range(num_q)])
-            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a, weight=g)
+            ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a, weight=g,
+                                       gain=e)
             d72 = (C.c_float * 72)(*D[:, :3, :].reshape(-1).float().tolist())
             check(lib.unires_rigid_sums(_ptr(gr3), _ptr(dg), _ptr(CtC) if CtC is not None else None,
                                         i3(dim), d72, _ptr(sums), _stream()))
@@ -290,7 +346,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
             Hes = np.zeros((num_q, num_q))
             Hes[iu] = s[num_q:]
             Hes = Hes + np.triu(Hes, 1).T
-            if (u is not None or g is not None) and not Hes.any():  # (all weights zero: no data term, no step - nothing to solve)
+            if (u is not None or g is not None or e is not None) and not Hes.any():  # (all weights zero: no data term, no step - nothing to solve)
                 empty = True
                 break
             Update = torch.from_numpy(np.linalg.solve(Hes, s[:num_q]))
@@ -302,7 +358,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
                 for n_ls in range(num_linesearch):
                     q = old_q - armijo * Update
                     rigid = _expm(q, basis)
-                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a, weight=g)[0]
+                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a, weight=g, gain=e)[0]
                     if bool(ll < old_ll):
                         armijo = min(1.25 * armijo, 1.0)
                         if verbose >= 1:

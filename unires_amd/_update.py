@@ -247,16 +247,31 @@ def _slice_gain(sett):
     return bool(getattr(sett, 'slice_gain', False))
 
 
+def _check_gain(e, S):
+    if not torch.is_tensor(e) or not e.is_cuda or e.dtype != torch.float32 or not e.is_contiguous() \
+            or e.numel() != int(S):
+        raise ValueError('unires_amd: xn.slice_gain must be a contiguous float32 device tensor with one gain per slice, '
+                         'as fit() leaves it')
+    return e
+
+
+def _gn_gain(xn, sett):
+    """The slice gains the rigid Gauss-Newton update carries for repeat ``xn``: ``xn.slice_gain`` with ``sett.gain_gn``
+    (checked as ``_gained`` checks it), else None - the switch is off by default, and the update then ignores the gains
+    as it did before."""
+    e = getattr(xn, 'slice_gain', None)
+    if e is None or not getattr(sett, 'gain_gn', False):
+        return None
+    return _check_gain(e, xn.dat.shape[_slice_axis(xn)])
+
+
 def _gained(Ay, xn, out=None):
     """e . (A y): the prediction of a repeat with gains ``xn.slice_gain`` along ``po.dim_thick`` (``unires_slice_apply``,
     one float32 product per voxel; out of place unless ``out`` is ``Ay``).  ``Ay`` itself where the repeat has none."""
     e = getattr(xn, 'slice_gain', None)
     if e is None:
         return Ay
-    if not torch.is_tensor(e) or not e.is_cuda or e.dtype != torch.float32 or not e.is_contiguous() \
-            or e.numel() != int(Ay.shape[_slice_axis(xn)]):
-        raise ValueError('unires_amd: xn.slice_gain must be a contiguous float32 device tensor with one gain per slice, '
-                         'as fit() leaves it')
+    _check_gain(e, Ay.shape[_slice_axis(xn)])
     out = torch.empty_like(Ay) if out is None else out
     check(_lib.load().unires_slice_apply(_ptr(Ay), _ptr(out), _ptr(e), i3(Ay.shape), _slice_axis(xn), _stream()))
     return out

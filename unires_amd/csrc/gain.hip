@@ -6,6 +6,8 @@
 //   k_gain_compose: the two per-slice tables of a gained repeat, u e^2 for the pass between the halves of A^T A and u e
 //     for the right-hand side; the passes themselves are slice.hip's and voxel.hip's, which take either table where they
 //     took u.
+//   k_rigid_terms_e_rows / k_rigid_terms_e_z + k_gain_finish: the rigid Gauss-Newton step of a gained repeat in one pass
+//     (sett.gain_gn) - the slice sums of x - e . A y and the residual t[s] (e . A y - x), e . A y never stored.
 #include <algorithm>
 
 #include "gain.hpp"
@@ -119,7 +121,119 @@ __global__ void __launch_bounds__(kBlock) k_gain_compose(const float *__restrict
   }
 }
 
+// One voxel of the rigid Gauss-Newton step of a gained repeat: p = fl32(e ay) (k_slice_apply's product) stays in a
+// register.  Its term of the slice's sums is slice_term's on p - voxel_term's with G, and the count as a double, which
+// holds the integers slice_term counts exactly - and, with OUT, its residual is resid_term's / resid_term_g<true>'s on p
+// with the slice's factor tv = fl32(u e) for u.  The two differences are taken separately: x - p and p - x differ in
+// the sign of a zero.  The store goes to the offset just read: out may be ay.
+template <bool G, bool OUT>
+__device__ __forceinline__ void terms_e_term(const float *__restrict__ x, const float *ay, const float *__restrict__ g,
+                                             float *out, size_t o, float ev, float tv, double &acc, double &cnt) {
+#pragma clang fp contract(off)
+  // (the product and the differences it feeds are written out under the pragma: __fmul_rn and __fsub_rn are plain
+  // operators in a header compiled with contraction on, and a product that feeds a difference would fuse through them)
+  const float xv = x[o], p = ay[o] * ev;
+  const float gv = G ? g[o] : 1.f;
+  if (xv != 0.f) {
+    const float r = xv - p, rr = __fmul_rn(r, r);
+    acc += (double)(G ? __fmul_rn(gv, rr) : rr);
+    cnt += G ? (double)gv : 1.0;
+  }
+  if (OUT) {
+    float v = 0.f;
+    if (xv != 0.f && p != 0.f) {
+      const float d = p - xv;
+      v = G ? (float)__dmul_rn(__dmul_rn((double)gv, (double)tv), (double)d) : __fmul_rn(tv, d);
+    }
+    out[o] = v;
+  }
+}
+
+// t[s] = fl32(fl64(u[s]) fl64(e[s])), exact in float64 and rounded once: k_gain_compose's w_rhs[s]
+__device__ __forceinline__ float terms_e_factor(const float *__restrict__ u, float ev, size_t s) {
+#pragma clang fp contract(off)
+  return u ? (float)__dmul_rn((double)u[s], (double)ev) : ev;
+}
+
+// k_slice_sums_rows' / k_voxel_sums_rows' walk, grid and shares (axes 0 and 1), with the gain and the residual in the
+// same pass: e[s] and t[s] are uniform over the workgroup.  Every voxel is visited by exactly one thread, once.
+template <bool G, bool OUT>
+__global__ void __launch_bounds__(kBlock) k_rigid_terms_e_rows(const float *__restrict__ x, const float *ay,
+                                                               const float *__restrict__ g, const float *__restrict__ u,
+                                                               const float *__restrict__ e, float *out, Dim3i d, int axis,
+                                                               double *__restrict__ part) {
+  const size_t s = blockIdx.x, b = blockIdx.y, B = gridDim.y;
+  const size_t S = axis == 0 ? d.x : d.y;
+  const float ev = e[s], tv = terms_e_factor(u, ev, s);
+  double acc = 0.0, cnt = 0.0;
+  if (axis == 0) {
+    const size_t P = (size_t)d.y * d.z, base = s * P;
+    for (size_t i = b * kBlock + threadIdx.x; i < P; i += B * kBlock)
+      terms_e_term<G, OUT>(x, ay, g, out, base + i, ev, tv, acc, cnt);
+  } else {
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    for (size_t i = b * (kBlock / kWave) + wave; i < (size_t)d.x; i += B * (kBlock / kWave)) {
+      const size_t base = (i * d.y + s) * d.z;
+      for (int k = lane; k < d.z; k += kWave) terms_e_term<G, OUT>(x, ay, g, out, base + k, ev, tv, acc, cnt);
+    }
+  }
+  const double ts = block_sum(acc), tc = block_sum(cnt);
+  if (threadIdx.x == 0) part[s * B + b] = ts, part[(S + s) * B + b] = tc;
+}
+
+// k_slice_sums_z's / k_voxel_sums_z's walk, grid and shares (axis 2): a lane keeps its z, and so its e and t.
+template <bool G, bool OUT>
+__global__ void __launch_bounds__(kBlock) k_rigid_terms_e_z(const float *__restrict__ x, const float *ay,
+                                                            const float *__restrict__ g, const float *__restrict__ u,
+                                                            const float *__restrict__ e, float *out, Dim3i d,
+                                                            double *__restrict__ part) {
+  __shared__ double s_acc[kBlock / kWave][kWave];
+  __shared__ double s_cnt[kBlock / kWave][kWave];
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const size_t z = (size_t)blockIdx.x * kWave + lane, b = blockIdx.y, B = gridDim.y;
+  const size_t R = (size_t)d.x * d.y, S = d.z;
+  double acc = 0.0, cnt = 0.0;
+  if (z < S) {
+    const float ev = e[z], tv = terms_e_factor(u, ev, z);
+    for (size_t r = b * (kBlock / kWave) + wave; r < R; r += B * (kBlock / kWave))
+      terms_e_term<G, OUT>(x, ay, g, out, r * S + z, ev, tv, acc, cnt);
+  }
+  s_acc[wave][lane] = acc, s_cnt[wave][lane] = cnt;
+  __syncthreads();
+  if (wave == 0 && z < S) {
+    double t = s_acc[0][lane], c = s_cnt[0][lane];
+    for (int w = 1; w < kBlock / kWave; ++w) t += s_acc[w][lane], c += s_cnt[w][lane];
+    part[z * B + b] = t, part[(S + z) * B + b] = c;
+  }
+}
+
 }  // namespace
+
+void launch_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e, Dim3i d,
+                          int axis, double *part, double *sums, float *out, hipStream_t st) {
+  const int B = slice_sums_parts(d, axis);
+  const size_t S = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
+  const dim3 grid(axis == 2 ? (unsigned)((S + kWave - 1) / kWave) : (unsigned)S, B);
+#define UNIRES_TERMS_E(G, OUT)                                                                                         \
+  do {                                                                                                                 \
+    if (axis == 2)                                                                                                     \
+      hipLaunchKernelGGL((k_rigid_terms_e_z<G, OUT>), grid, dim3(kBlock), 0, st, x, ay, g, u, e, out, d, part);        \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_rigid_terms_e_rows<G, OUT>), grid, dim3(kBlock), 0, st, x, ay, g, u, e, out, d, axis,      \
+                         part);                                                                                        \
+  } while (0)
+  if (g && out)
+    UNIRES_TERMS_E(true, true);
+  else if (g)
+    UNIRES_TERMS_E(true, false);
+  else if (out)
+    UNIRES_TERMS_E(false, true);
+  else
+    UNIRES_TERMS_E(false, false);
+#undef UNIRES_TERMS_E
+  const size_t blocks = std::min<size_t>((2 * S + kBlock / kWave - 1) / (kBlock / kWave), 4096);
+  hipLaunchKernelGGL(k_gain_finish, dim3((unsigned)blocks), dim3(kBlock), 0, st, part, B, 2 * S, sums);
+}
 
 void launch_gain_sums(const float *x, const float *ay, const float *g, const float *u, Dim3i d, int axis, double *part,
                       double *out, hipStream_t st) {

@@ -17,4 +17,13 @@ void launch_gain_sums(const float *x, const float *ay, const float *g, const flo
 // workgroup.  u e is exact in float64; u e e is rounded there once, then once more to float32.
 void launch_gain_compose(const float *u, const float *e, int S, float *w_mat, float *w_rhs, hipStream_t st);
 
+// The terms of the rigid Gauss-Newton step of a gained repeat in one pass, on p = fl32(e[s(v)] ay(v)) held in registers
+// (launch_slice_apply's product, never stored); g a volume or nullptr (1), u S floats or nullptr (1), e S floats.
+//   sums[s], sums[S + s]: launch_slice_sums' bits on (x, p) - launch_voxel_sums' with g - by their walk, grid, shares
+//     and finish order;  part: 2 * S * slice_sums_parts(d, axis) doubles of scratch.
+//   out (nullptr: not written): launch_rigid_resid's bits on (x, p) with t[s] = fl32(fl64(u[s]) fl64(e[s])) (u nullptr:
+//     e[s]) for u - launch_rigid_resid_g's with g.  out may be ay: a voxel is read and stored by one thread, once.
+void launch_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e, Dim3i d,
+                          int axis, double *part, double *sums, float *out, hipStream_t st);
+
 }  // namespace unires

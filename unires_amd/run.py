@@ -83,8 +83,10 @@ def _init_slice_gains(x, sett, dev):
     per slice along ``po.dim_thick``, real, finite, > 0 - the one read-back) and moved to the device as float32; with
     ``sett.slice_gain`` every non-CT repeat starts from its own, or from ones where it has none, so that the plans'
     kernels do not change mid-fit, and the precision kappa of its gains' prior is fixed here (``gain_kappa``), so that
-    the objective is one function for the whole fit.  The even / odd scaling is a special case of the gains and the
-    rigid update's residual does not carry them: both settings are refused by name."""
+    the objective is one function for the whole fit.  The even / odd scaling is a special case of the gains:
+    ``sett.scaling`` is refused by name (ValueError).  The rigid update carries the gains only with ``sett.gain_gn``:
+    without it ``sett.unified_rigid`` is refused by name (NotImplementedError) rather than left to minimise another
+    data term."""
     from ._project import _slice_axis
     from ._update import gain_kappa
     on = bool(getattr(sett, 'slice_gain', False))
@@ -96,9 +98,10 @@ def _init_slice_gains(x, sett, dev):
     if getattr(sett, 'scaling', False):
         raise ValueError('sett.scaling with slice gains (_input.slice_gain, sett.slice_gain): the even / odd slice '
                          'scaling is a special case of the per-slice gains - use one of the two')
-    if getattr(sett, 'unified_rigid', False):
+    if getattr(sett, 'unified_rigid', False) and not getattr(sett, 'gain_gn', False):
         raise NotImplementedError('sett.unified_rigid with slice gains (_input.slice_gain, sett.slice_gain): the '
-                                  'rigid Gauss-Newton update\'s residual does not carry per-slice gains yet')
+                                  'rigid Gauss-Newton update carries per-slice gains only where asked to - set '
+                                  'sett.gain_gn')
     if on and not float(getattr(sett, 'gain_reg', 0.1)) >= 0:
         raise ValueError('sett.gain_reg must be >= 0')
     if on and not float(getattr(sett, 'gain_max', 2.0)) > 1:
@@ -195,7 +198,11 @@ def fit(x, y, sett):
     Slice gains model an observation as e[s(v)] (A y)(v) (banding).  Under ``sett.slice_gain`` they are re-estimated
     after every ADMM iteration's z / w update, before the slice and voxel rules write their weights, against a ridge
     towards 1 whose precision is fixed here for the whole fit; the objective carries that ridge.  ``sett.scaling``
-    (ValueError) and ``sett.unified_rigid`` (NotImplementedError) are refused with gains, by name.
+    is refused with gains, by name (ValueError).  With ``sett.gain_gn`` the rigid Gauss-Newton update of a gained
+    repeat (``sett.unified_rigid``) takes its step on the same data term - objective, residual and Hessian weight
+    carry the gains (``_update_rigid``), and it sees the gains ``_update_admm`` has just re-estimated; the ridge does
+    not depend on the rigid parameters and is no part of that step.  Without ``sett.gain_gn`` (the default)
+    ``sett.unified_rigid`` is refused with gains, by name (NotImplementedError).
 
     Slice weights define a repeat's data term, and every update minimises it: with ``sett.scaling`` or
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,

@@ -37,7 +37,8 @@ class _input:
         # its neighbours (banding) keeps its information.  Set before fit() where the gains are known (used as given
         # with sett.slice_gain off; fit() validates them once and moves them to the device); with sett.slice_gain
         # fit() starts from them, or from ones where None, and re-estimates them every ADMM iteration.  They enter the
-        # y-update and the objective; sett.scaling and sett.unified_rigid are refused with them
+        # y-update and the objective, and with sett.gain_gn the rigid Gauss-Newton update; sett.scaling is refused with
+        # them, and so is sett.unified_rigid without sett.gain_gn
         self.slice_gain = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
@@ -132,13 +133,20 @@ class settings:
         # of 1/2 tau sum_v W (x - e_s A y)^2 + 1/2 kappa (e_s - 1)^2 over [1 / gain_max, gain_max], W the repeat's
         # weights and mask.  kappa = gain_reg tau (sum_{x != 0} x^2) / (slices with data), fixed for a whole fit().  The
         # reference's sett.scaling (one exp(+-s) for even / odd slices) is a special case and is refused with it, and so
-        # is sett.unified_rigid, whose residual does not carry gains.  A factor common to all gains of a repeat trades
+        # is sett.unified_rigid unless sett.gain_gn lets its step carry the gains.  A factor common to all gains of a repeat trades
         # against y; the ridge towards 1 bounds it and does not remove it.  gain_reg = 0.1 and
         # gain_max = 2 are UNTUNED modelling defaults: nobody has chosen them on real data.  Off: every slice has gain 1
         # unless the user set _input.slice_gain
         self.slice_gain = False
         self.gain_reg = 0.1
         self.gain_max = 2.0
+        # the rigid Gauss-Newton update (sett.unified_rigid) carries the gains of every repeat that has some: objective,
+        # residual (times e, the chain rule through diag(e)) and Hessian weight W e^2 are those of
+        # 1/2 tau sum_v W (x - e_s A y)^2 (_rigid._update_rigid).  Off: fit() refuses sett.unified_rigid
+        # with gains, and the update ignores xn.slice_gain, as it did before it could carry them.  A switch only because
+        # that refusal is pinned by a test; not a modelling choice - with gains and sett.unified_rigid, turn it on.
+        # sett.scaling stays refused with gains either way
+        self.gain_gn = False
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
