@@ -586,6 +586,25 @@ int unires_gain_sums(const float *x, const float *ay, const float *g, const floa
 int unires_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e,
                          const int32_t dim[3], int32_t axis, double *sums_dev, float *out, void *stream);
 
+/* Terms of the Rician data term of a magnitude observation (no counterpart in the reference; sett.noise_model =
+ * 'rician'): x, ay x-space volumes `dim`, g a volume of weights or NULL (1), e S = dim[axis] per-slice gains or NULL
+ * (1), all on the device; tau the observation's precision 1 / sigma^2.  Per voxel, in registers,
+ * p = fl32(e[s] ay) (unires_slice_apply's product; ay itself without e) and z = fl32(fl32(tau x) p).
+ *   xt (NULL: not written) = fl32(x R(z)), R = I1 / I0: the effective observation of the quadratic majoriser - the
+ *                  y-update's right-hand side takes it where it took x.  R odd, |R| <= 1, R(+-inf) = +-1; +0 where
+ *                  x == 0.  xt == ay is allowed; x, g, e are only read (xt == x or xt == g: UNIRES_ERR_ARG).
+ *   sums_dev[s] (NULL: not written) = sum_{v in slice s} g(v) c(z(v)),  c(z) = (z - |z|) - log i0e(|z|): what the
+ *                  voxel's negative log-likelihood holds beside 1/2 tau (x - p)^2 (the term -log(tau x), which does
+ *                  not depend on y, is dropped).  float32 terms, widened; fl64(g c) rounded on its own; float64 sums in
+ *                  unires_rigid_terms_e's fixed order (no atomics: the same bits every run); every one of the S
+ *                  entries is written.  Slice weights are the caller's: sum_s u_s sums_dev[s].
+ * R and c are float32 evaluations of fixed-degree forms (Abramowitz & Stegun 9.8.1 - 9.8.4 as ratios: |z| <= 3.75
+ * polynomials in z^2, beyond polynomials in 1 / |z|; one select, no loops, no exp, no overflow): R to 2e-6 relative,
+ * c to 1e-6 (1 + |c|).  One pass over x, ay [and g].  Errors as for unires_slice_sums; xt and sums_dev both NULL:
+ * UNIRES_ERR_ARG.  sums_dev: S doubles on the device. */
+int unires_rician_terms(const float *x, const float *ay, const float *g, const float *e, const int32_t dim[3],
+                        int32_t axis, float tau, float *xt, double *sums_dev, void *stream);
+
 /* dst[v] = fl32(u[s(v)] src[v]) over a z-fastest volume `dim`, s(v) = v's index along `axis`, u dim[axis] floats on the
  * device: the pass of a slice-weighted repeat on its own, without mask and without a `done` word (no counterpart in the
  * reference).  dst == src: in place; dst != src: src is only read.  With the gains of a repeat as u it makes e . (A y),

@@ -57,6 +57,31 @@ def _slice_robust(sett):
     return bool(getattr(sett, 'slice_robust', False))
 
 
+NOISE_MODELS = ('gaussian', 'rician')
+
+
+def _noise_model(sett):
+    """sett.noise_model ('gaussian' where the settings object has none): the data term's noise model.  Any other name
+    than NOISE_MODELS' is a ValueError."""
+    name = getattr(sett, 'noise_model', 'gaussian')
+    if name not in NOISE_MODELS:
+        raise ValueError("sett.noise_model must be 'gaussian' or 'rician', not %r" % (name,))
+    return name
+
+
+def _is_rician(xn, sett):
+    """Repeat ``xn`` has the Rician data term: sett.noise_model = 'rician' and not CT."""
+    return _noise_model(sett) == 'rician' and not getattr(xn, 'ct', False)
+
+
+def _obs(xn, sett):
+    """What the y-update's right-hand side reads for repeat ``xn``: under the Rician model the effective observation
+    ``xn._rician_dat`` (fit()'s clone of ``xn.dat`` before the first iteration, x R(tau x e . A y) after each), else
+    ``xn.dat``.  Masks, weights and every residual keep reading ``xn.dat``."""
+    xt = getattr(xn, '_rician_dat', None)
+    return xt if xt is not None and _is_rician(xn, sett) else xn.dat
+
+
 class _Precond:
     """Callable x -> x / M like the lambda unires/_update.py:100 returns; carries the plan
     that holds the device copy of M so cg() can run the preconditioned iteration on device."""
@@ -112,9 +137,9 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
             plan.set_concurrency(1)
             lam = float(y[c].lam)
             if getattr(sett, 'cache_atx', True) and not sync:
-                plan.rhs_cached([xn.dat for xn in x[c]], w[c], z[c], rho, lam, out=tmp)
+                plan.rhs_cached([_obs(xn, sett) for xn in x[c]], w[c], z[c], rho, lam, out=tmp)
             else:
-                plan.rhs([xn.dat for xn in x[c]], w[c], z[c], rho, lam, out=tmp)
+                plan.rhs([_obs(xn, sett) for xn in x[c]], w[c], z[c], rho, lam, out=tmp)
             if pre in ('jacobi', 'fft'):
                 plan.precond_build(rho, lam, mode=pre)
             res = plan.cg(tmp, y[c].dat, rho, lam, max_iter=sett.cgs_max_iter,
@@ -139,9 +164,9 @@ def _update_y(x, y, z, w, rho, tmp, sett, info=None):
         with torch.cuda.stream(streams[c]):
             streams[c].wait_event(ready)
             if getattr(sett, 'cache_atx', True):
-                plan.rhs_cached([xn.dat for xn in x[c]], w[c], z[c], rho, lam, out=b)
+                plan.rhs_cached([_obs(xn, sett) for xn in x[c]], w[c], z[c], rho, lam, out=b)
             else:
-                plan.rhs([xn.dat for xn in x[c]], w[c], z[c], rho, lam, out=b)
+                plan.rhs([_obs(xn, sett) for xn in x[c]], w[c], z[c], rho, lam, out=b)
             if pre in ('jacobi', 'fft'):
                 plan.precond_build(rho, lam, mode=pre)
         plans.append(plan)
@@ -278,7 +303,7 @@ def _gained(Ay, xn, out=None):
 
 
 @on_device
-def _slice_sums(x, y, sett, ays=None, raw=None):
+def _slice_sums(x, y, sett, ays=None, raw=None, proj=None):
     """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights or gains: SSE_s =
     sum_{v in s, x != 0} (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick``
     (``unires_slice_sums``; float32 terms, float64 sums in a fixed order); for a repeat with voxel weights
@@ -287,7 +312,8 @@ def _slice_sums(x, y, sett, ays=None, raw=None):
     (``_update_slice_weights``; ``_update_voxel_weights`` takes the A y itself from ``ays``, a dict filled here with
     (c, n): A y of the voxel-weighted repeats).  For a repeat with gains ``xn.slice_gain`` the prediction is
     e . (A y) throughout (``_gained``), and ``raw``, a dict, receives (c, n): its A y WITHOUT gains, which
-    ``_update_slice_gains`` estimates from.  Nothing is read back."""
+    ``_update_slice_gains`` estimates from.  ``proj``: {(c, n): A y without gains} already computed for this y (the
+    Rician repeats', ``_rician_terms``), only read.  Nothing is read back."""
     lib = _lib.load()
     out = {}
     for c in range(len(x)):
@@ -295,7 +321,9 @@ def _slice_sums(x, y, sett, ays=None, raw=None):
             g = getattr(xn, 'weight', None)
             if getattr(xn, 'slice_w', None) is None and g is None and getattr(xn, 'slice_gain', None) is None:
                 continue
-            Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            Ay = None if proj is None else proj.get((c, n))
+            if Ay is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             if getattr(xn, 'slice_gain', None) is not None:
                 if raw is not None:
                     raw[(c, n)] = Ay
@@ -477,21 +505,78 @@ def _slice_ll(tau, w, sums):
 
 
 @on_device
-def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
+def _rician_ll(w, L):
+    """sum_s u_s L_s of one Rician repeat: ``L`` its (S,) float64 sums of g c(z) per slice (``unires_rician_terms``),
+    ``w`` its (S,) slice weights or None (u = 1) - what the repeat's data term holds beside ``_slice_ll``'s (or the
+    masked SSE's) Gaussian part, NOT multiplied by tau.  A float64 dot product on the device, no read-back."""
+    return L.sum() if w is None else (w.double() * L).sum()
+
+
+@on_device
+def _rician_terms(x, y, sett, proj=None, sums=True, write=True):
+    """One ``unires_rician_terms`` pass per Rician repeat (``_is_rician``) on the current y: with ``write`` the
+    effective observation x R(tau x e . A y) goes in place into ``xn._rician_dat`` (made here where fit() has not),
+    whose version counter is bumped - it tells the cached sum tau At (W e . x~) of the next y-update; with ``sums``
+    returns {(c, n): (S,) float64 device tensor L_s = sum_{v in s} g c(z)}, else {} and nothing but x~ is written.
+    ``proj``, a dict, holds (c, n): A y WITHOUT gains where already computed and receives it where computed here.  A
+    user's fixed gains enter through mu = e . A y inside the kernel.  No read-back."""
+    lib = _lib.load()
+    out = {}
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            if not _is_rician(xn, sett):
+                continue
+            Ay = None if proj is None else proj.get((c, n))
+            if Ay is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+                if proj is not None:
+                    proj[(c, n)] = Ay
+            xd = xn.dat.contiguous()
+            a = _slice_axis(xn)
+            g, e = getattr(xn, 'weight', None), getattr(xn, 'slice_gain', None)
+            if e is not None:
+                _check_gain(e, xd.shape[a])
+            xt = None
+            if write:
+                if getattr(xn, '_rician_dat', None) is None:
+                    xn._rician_dat = torch.empty_like(xd)
+                xt = xn._rician_dat
+            L = torch.empty(int(xd.shape[a]), dtype=torch.float64, device=xd.device) if sums else None
+            check(lib.unires_rician_terms(_ptr(xd), _ptr(Ay.contiguous()),
+                                          None if g is None or not sums else _ptr(g.contiguous()),
+                                          None if e is None else _ptr(e), i3(xd.shape), a, float(xn.tau),
+                                          None if xt is None else _ptr(xt), None if L is None else _ptr(L), _stream()))
+            if write:
+                torch.autograd.graph.increment_version(xt)
+            if sums:
+                out[(c, n)] = L
+    return out
+
+
+@on_device
+def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None, proj=None, rician=None):
     """Negative model log-likelihood (unires/_update.py:396-427); returns 0-d float64
     device tensors (nll_yx, nll_xy, nll_y) without synchronising.  A repeat with slice or voxel weights contributes
     1/2 tau sum_s u_s SSE_s (``slice_sums``: ``_slice_sums``' result for this y, computed here when None; SSE_s
     carries g for a voxel-weighted repeat, and is taken on e . A y for a repeat with gains).  Under ``sett.slice_gain``
-    the gains' prior 1/2 kappa sum_s (e_s - 1)^2 of every estimated repeat is part of the data term's value."""
+    the gains' prior 1/2 kappa sum_s (e_s - 1)^2 of every estimated repeat is part of the data term's value.  Under
+    ``sett.noise_model = 'rician'`` a non-CT repeat adds sum_s u_s L_s (``_rician_ll``; ``rician``: ``_rician_terms``'
+    sums for this y, computed here - without touching the effective observations - when None; ``proj``: the A y
+    without gains it computed); the term -log(tau x), which does not depend on y, is left out."""
     dev = y[0].dat.device
+    if rician is None and _noise_model(sett) == 'rician':
+        proj = {} if proj is None else proj
+        rician = _rician_terms(x, y, sett, proj, write=False)
     if slice_sums is None:
-        slice_sums = _slice_sums(x, y, sett)
+        slice_sums = _slice_sums(x, y, sett, proj=proj)
     lib = _lib.load()
     vx = [float(v) for v in voxel_size(y[0].mat).tolist()]
     nll_xy = torch.zeros((), dtype=torch.float64, device=dev)
     sse = torch.zeros((), dtype=torch.float64, device=dev)
     for c in range(len(x)):
         for n in range(len(x[c])):
+            if rician and (c, n) in rician:
+                nll_xy = nll_xy + _rician_ll(getattr(x[c][n], 'slice_w', None), rician[(c, n)])
             if (c, n) in slice_sums:
                 nll_xy = nll_xy + _slice_ll(x[c][n].tau, getattr(x[c][n], 'slice_w', None), slice_sums[(c, n)])
                 e = getattr(x[c][n], 'slice_gain', None)
@@ -500,7 +585,9 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None):
                         x[c][n]._gain_kappa = gain_kappa(x[c][n], getattr(sett, 'gain_reg', 0.1))
                     nll_xy = nll_xy + 0.5 * x[c][n]._gain_kappa * ((e.double() - 1.0) ** 2).sum()
                 continue
-            Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            Ay = None if proj is None else proj.get((c, n))
+            if Ay is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             xd = x[c][n].dat.contiguous()
             check(lib.unires_masked_sse(_ptr(xd), _ptr(Ay), xd.numel(), _ptr(sse), _stream()))
             nll_xy = nll_xy + 0.5 * float(x[c][n].tau) * sse
@@ -607,9 +694,14 @@ def _update_admm(x, y, z, w, rho, tmp, obj, n_iter, sett, info=None):
     # voxel-weighted repeats is kept for the Huber rule)
     ays = {} if _voxel_robust(sett) else None
     raw = {} if _slice_gain(sett) else None  # (A y without gains of the gained repeats, for the gain rule)
-    sums = _slice_sums(x, y, sett, ays, raw) if want_obj or _slice_robust(sett) or _slice_gain(sett) else None
+    # (the Rician repeats: A y once - it serves the sums below, the objective's correction and the effective
+    # observation of the next y-update, written here; without an objective nothing but that is written)
+    proj = {} if _noise_model(sett) == 'rician' else None
+    rician = _rician_terms(x, y, sett, proj, sums=want_obj) if proj is not None else None
+    sums = _slice_sums(x, y, sett, ays, raw, proj) if want_obj or _slice_robust(sett) or _slice_gain(sett) else None
     if want_obj:
-        obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums)
+        obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums, proj=proj,
+                                                                     rician=rician)
     z, w, tmp = _update_zw(y, z, w, rho, tmp, sett)
     if _slice_gain(sett):  # (before the rules below write their weights: it reads the W this iteration's y-update used;
         _update_slice_gains(x, y, sett, raw)  # sums and ays keep the prediction e . A y of that y-update's gains)

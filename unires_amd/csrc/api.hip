@@ -19,6 +19,7 @@
 #include "coreg.hpp"
 #include "noise.hpp"
 #include "pull.hpp"
+#include "rician.hpp"
 #include "stencil.hpp"
 
 using namespace unires;
@@ -665,6 +666,22 @@ extern "C" int unires_rigid_terms_e(const float *x, const float *ay, const float
   const size_t cols = 2 * (size_t)dim[axis];
   if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), axis), &part)) return rc;
   launch_rigid_terms_e(x, ay, g, u, e, mk(dim), axis, part, sums_dev, out, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_rician_terms(const float *x, const float *ay, const float *g, const float *e, const int32_t dim[3],
+                                   int32_t axis, float tau, float *xt, double *sums_dev, void *stream) {
+  if (!x || !ay || !dim) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
+  if (!xt && !sums_dev) return fail(UNIRES_ERR_ARG, "nothing to write: xt and sums are both null");
+  if (xt && (xt == x || xt == g)) return fail(UNIRES_ERR_ARG, "xt must not be x or g: they are only read");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  if (sums_dev)
+    if (int rc = reduce_scratch(st, (size_t)dim[axis] * (size_t)slice_sums_parts(mk(dim), axis), &part)) return rc;
+  launch_rician_terms(x, ay, g, e, mk(dim), axis, tau, xt, part, sums_dev, st);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

@@ -209,6 +209,11 @@ __global__ void __launch_bounds__(kBlock) k_rigid_terms_e_z(const float *__restr
 
 }  // namespace
 
+void launch_gain_finish(const double *part, int B, size_t ncols, double *out, hipStream_t st) {
+  const size_t blocks = std::min<size_t>((ncols + kBlock / kWave - 1) / (kBlock / kWave), 4096);
+  hipLaunchKernelGGL(k_gain_finish, dim3((unsigned)blocks), dim3(kBlock), 0, st, part, B, ncols, out);
+}
+
 void launch_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e, Dim3i d,
                           int axis, double *part, double *sums, float *out, hipStream_t st) {
   const int B = slice_sums_parts(d, axis);
@@ -231,8 +236,7 @@ void launch_rigid_terms_e(const float *x, const float *ay, const float *g, const
   else
     UNIRES_TERMS_E(false, false);
 #undef UNIRES_TERMS_E
-  const size_t blocks = std::min<size_t>((2 * S + kBlock / kWave - 1) / (kBlock / kWave), 4096);
-  hipLaunchKernelGGL(k_gain_finish, dim3((unsigned)blocks), dim3(kBlock), 0, st, part, B, 2 * S, sums);
+  launch_gain_finish(part, B, 2 * S, sums, st);
 }
 
 void launch_gain_sums(const float *x, const float *ay, const float *g, const float *u, Dim3i d, int axis, double *part,
@@ -252,8 +256,7 @@ void launch_gain_sums(const float *x, const float *ay, const float *g, const flo
     else
       hipLaunchKernelGGL(k_gain_sums_rows<false>, grid, dim3(kBlock), 0, st, x, ay, g, u, d, axis, part);
   }
-  const size_t blocks = std::min<size_t>((3 * S + kBlock / kWave - 1) / (kBlock / kWave), 4096);
-  hipLaunchKernelGGL(k_gain_finish, dim3((unsigned)blocks), dim3(kBlock), 0, st, part, B, 3 * S, out);
+  launch_gain_finish(part, B, 3 * S, out, st);
 }
 
 void launch_gain_compose(const float *u, const float *e, int S, float *w_mat, float *w_rhs, hipStream_t st) {

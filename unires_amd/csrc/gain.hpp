@@ -26,4 +26,8 @@ void launch_gain_compose(const float *u, const float *e, int S, float *w_mat, fl
 void launch_rigid_terms_e(const float *x, const float *ay, const float *g, const float *u, const float *e, Dim3i d,
                           int axis, double *part, double *sums, float *out, hipStream_t st);
 
+// out[c] = sum_b part[c * B + b] for c < ncols: the finish of every per-slice sum above (and of rician.hip's) - a wave
+// per entry, lane l adds the shares l, l + 64, ... in index order, a fixed tree adds the lanes.  Plain stores.
+void launch_gain_finish(const double *part, int B, size_t ncols, double *out, hipStream_t st);
+
 }  // namespace unires

@@ -14,7 +14,7 @@ from ._host import wait_blocking
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
 from ._rigid import _update_rigid
-from ._update import _admm_aux, _step_size, _update_admm, _update_scaling, _voxel_scale
+from ._update import _admm_aux, _noise_model, _step_size, _update_admm, _update_scaling, _voxel_scale
 from .stats import MAD_TO_SD, median_work
 from .optim import get_gain
 from .spatial import _m12
@@ -131,6 +131,38 @@ def _init_slice_gains(x, sett, dev):
                 xn._gain_kappa = gain_kappa(xn, getattr(sett, 'gain_reg', 0.1))
 
 
+def _init_rician(x, sett):
+    """sett.noise_model as the iterations take it.  'gaussian' (the default): nothing but forgetting an earlier fit()'s
+    effective observations.  'rician': ``sett.scaling``, ``sett.unified_rigid`` and ``sett.slice_gain`` are refused by
+    name (NotImplementedError) - those updates minimise the Gaussian term, and carrying the majoriser through them is not
+    built; every non-CT observation must be finite and >= 0 (ValueError naming channel and repeat; one reduction per
+    repeat on the device, one read-back for all), and gets ``xn._rician_dat``, a float32 clone of ``xn.dat``: the
+    effective observation of the FIRST y-update, which is therefore the Gaussian one (mu = 0 is a stationary point of
+    the Rician likelihood: an effective observation x R(tau x A y0) of an all-zero first guess would stay 0).  Any
+    other name: ValueError."""
+    if _noise_model(sett) == 'gaussian':
+        for xc in x:
+            for xn in xc:
+                if getattr(xn, '_rician_dat', None) is not None:
+                    xn._rician_dat = None
+        return x
+    for name in ('scaling', 'unified_rigid', 'slice_gain'):
+        if getattr(sett, name, False):
+            raise NotImplementedError("sett.%s with sett.noise_model = 'rician': that update minimises the Gaussian data "
+                                      "term; carrying the Rician majoriser through it is not built" % name)
+    who = [(c, n) for c, xc in enumerate(x) for n, xn in enumerate(xc) if not xn.ct]
+    if who:
+        bad = torch.stack([~(torch.isfinite(x[c][n].dat).all() & (x[c][n].dat >= 0).all()) for c, n in who]).tolist()
+        for (c, n), b in zip(who, bad):
+            if b:
+                raise ValueError("x[%d][%d].dat holds a negative or non-finite value: sett.noise_model = 'rician' takes "
+                                 "magnitude data" % (c, n))
+    for xc in x:
+        for xn in xc:
+            xn._rician_dat = None if xn.ct else xn.dat.float().contiguous().clone()
+    return x
+
+
 def _init_voxel_weights(x, sett, dev):
     """The observations' voxel weights as the iterations take them: a user's ``_input.weight`` validated (the
     observation's shape, real, finite, >= 0 - the one read-back) and moved to the device as contiguous float32.  With
@@ -208,6 +240,14 @@ def fit(x, y, sett):
     ``sett.unified_rigid`` the Gauss-Newton updates of a weighted repeat take the weights too (``_update_scaling``,
     ``_update_rigid``).  Under ``sett.slice_robust`` they see the weights ``_update_admm`` has just re-estimated.
 
+    ``sett.noise_model = 'rician'`` gives every non-CT repeat the Rician data term W [1/2 tau (x - mu)^2 + c(tau x mu)],
+    mu = e . A y, minimised by majorisation: every ADMM iteration's y-update is the Gaussian one on the effective
+    observation ``xn._rician_dat`` = x I1/I0(tau x mu) of the previous iteration's y (a clone of ``xn.dat`` for the
+    first: one more observation-sized buffer per repeat), and ``obj`` carries the term c.  Observations must be finite
+    and >= 0 (ValueError); ``sett.scaling``, ``sett.unified_rigid`` and ``sett.slice_gain`` are refused with it, by name
+    (NotImplementedError); a user's fixed ``_input.slice_gain``, both robust rules, ``sett.mask_zeros`` and channel
+    streams work with it unchanged.  The default 'gaussian' runs what ran before the knob existed.
+
     Voxel weights define it likewise.  With ``sett.voxel_gn`` the two Gauss-Newton updates of a repeat that has voxel
     weights take them too - beside its slice weights, where it has both - and under ``sett.voxel_robust`` they see the
     weights ``_update_admm`` has just re-estimated.  Without ``sett.voxel_gn`` (the default) ``sett.scaling`` and
@@ -216,6 +256,7 @@ def fit(x, y, sett):
         raise ValueError('one output per channel')
     with torch.no_grad():
         dev = y[0].dat.device
+        _init_rician(x, sett)
         _init_slice_weights(x, sett, dev)
         _init_voxel_weights(x, sett, dev)
         _init_slice_gains(x, sett, dev)

@@ -147,6 +147,17 @@ class settings:
         # that refusal is pinned by a test; not a modelling choice - with gains and sett.unified_rigid, turn it on.
         # sett.scaling stays refused with gains either way
         self.gain_gn = False
+        # build-side knob: the noise model of the data term.  'gaussian': 1/2 tau sum_v W (x - mu)^2, mu = e . A y - the
+        # reference's, and what ran before the knob existed, bit for bit.  'rician': every non-CT observation is a
+        # magnitude image with Rice noise of sigma = 1 / sqrt(tau) (what init() estimates): a voxel's term becomes
+        # W [1/2 tau (x - mu)^2 + c(tau x mu)], c(z) = (z - |z|) - log i0e(|z|), which does not pull dark tissue, CSF
+        # and air towards the Rician mean.  Minimised by majorisation: each ADMM iteration's y-update is the Gaussian
+        # one on the effective observation x I1/I0(tau x mu) of the previous iteration's y (the first on x itself); one
+        # A y and one streaming pass per repeat and iteration, and one more observation-sized buffer per repeat
+        # (DESIGN 8.14).  CT repeats keep the Gaussian term.  Observations must be finite and >= 0.  sett.scaling,
+        # sett.unified_rigid and sett.slice_gain minimise the Gaussian term and are refused with it, by name.  Any
+        # other name: ValueError in fit()
+        self.noise_model = 'gaussian'
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
