@@ -605,6 +605,25 @@ int unires_rigid_terms_e(const float *x, const float *ay, const float *g, const 
 int unires_rician_terms(const float *x, const float *ay, const float *g, const float *e, const int32_t dim[3],
                         int32_t axis, float tau, float *xt, double *sums_dev, void *stream);
 
+/* Terms of the rigid Gauss-Newton step of a repeat with the Rician data term (no counterpart in the reference;
+ * sett.rician_gn): x, ay x-space volumes `dim`, g a volume of weights or NULL (1), u S = dim[axis] slice weights or
+ * NULL (1), e S per-slice gains or NULL (1), all on the device; tau the observation's precision.  One pass over x, ay
+ * [and g]; per voxel, in registers, p = fl32(e[s] ay) (ay itself with e NULL) and z = fl32(fl32(tau x) p).
+ *   sums_dev[s], sums_dev[S + s]  = the SSE and the count of slice s: exactly unires_rigid_terms_e's - with e NULL
+ *                  unires_slice_sums' (g NULL) or unires_voxel_sums' (g) on ay
+ *   sums_dev[2 S + s] = sum_{v in s} g c(z): exactly unires_rician_terms' sums_dev
+ *   out (NULL: not written; a line-search evaluation) = t[s] [g] (p - x~), x~ = fl32(x R(z)) unires_rician_terms'
+ *                  effective observation, never stored; +0 where x == 0 or p == 0 - the mask reads the true x, not
+ *                  x~, which can underflow to 0 where x is not; t[s] = fl32(fl64(u[s]) fl64(e[s])), 1 where a table
+ *                  is NULL; unires_rigid_resid's / unires_rigid_resid_g's roundings with u := t, ay := p, x := x~
+ *                  (both tables NULL: theirs with u NULL).  tau times out is the exact derivative of the repeat's
+ *                  Rician term W [1/2 tau (x - p)^2 + c(z)] in A y.
+ * No atomics: the same bits every run; every one of the 3 S entries is written with a plain store.  out == ay is
+ * allowed; x, g, u, e are only read (out == x or out == g: UNIRES_ERR_ARG).  Errors as for unires_slice_sums; nothing
+ * is launched on a bad argument.  sums_dev: 3 S doubles on the device. */
+int unires_rigid_terms_r(const float *x, const float *ay, const float *g, const float *u, const float *e,
+                         const int32_t dim[3], int32_t axis, float tau, double *sums_dev, float *out, void *stream);
+
 /* dst[v] = fl32(u[s(v)] src[v]) over a z-fastest volume `dim`, s(v) = v's index along `axis`, u dim[axis] floats on the
  * device: the pass of a slice-weighted repeat on its own, without mask and without a `done` word (no counterpart in the
  * reference).  dst == src: in place; dst != src: src is only read.  With the gains of a repeat as u it makes e . (A y),

@@ -24,7 +24,7 @@ from ._host import light_host
 from ._lib import check, i3
 from ._ops import _ptr, _stream, on_device
 from ._project import _apply_scaling, _proj_info, _slice_axis, _taps, _thick_axis
-from ._update import _check_gain, _gn_gain, _gn_weight, _slice_ll
+from ._update import _check_gain, _gn_gain, _gn_weight, _is_rician, _rician_ll, _slice_ll
 from .spatial import _m12
 
 _F64 = torch.float64
@@ -104,7 +104,8 @@ def _grid_matrix(po, rigid, method):
 
 
 @on_device
-def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None, weight=None, gain=None):
+def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, axis=None, weight=None, gain=None,
+                 rician=False):
     """ll and, if ``diff``, the raw ingredients of the derivatives: gr3 (dim,3) = grid_grad,
     dg (dim) = residual in grid space.
 
@@ -126,7 +127,15 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     pass (``unires_rigid_terms_e``) gives the slice sums of x - p - ll = 1/2 tau sum_s u_s SSE_s by ``_slice_ll``, to the
     bit ``_compute_nll``'s term of the repeat - and, with ``diff``, the residual g u e (p - x), masked where x or p is 0:
     the factor e is the chain rule through diag(e).  The ridge 1/2 kappa sum (e - 1)^2 of ``sett.slice_gain`` does not
-    depend on the rigid parameters and is left out of ll."""
+    depend on the rigid parameters and is left out of ll.
+
+    ``rician``: the repeat has the Rician data term (``sett.noise_model = 'rician'`` with ``sett.rician_gn``; ``axis`` is
+    then its slice axis whatever else it has, ``dat_x`` the TRUE observation, never the effective one).  The terms are
+    those of sum_v W [1/2 tau (x - p)^2 + c(tau x p)], W = g u [x != 0 for the square], p = fl32(e A y), from one pass
+    (``unires_rigid_terms_r``; g, u, e each optional): ll = ``_slice_ll`` of its first 2 S sums plus ``_rician_ll`` of
+    its last S - ``_compute_nll``'s statement for the repeat, to the bit where the repeat has weights or gains - and,
+    with ``diff``, the residual W e (p - x R(tau x p)), masked where x or p is 0: tau times it is the exact derivative
+    of the Rician term in A y, the Gaussian residual on the effective observation taken at the current prediction."""
     method = sett.method
     lib = _lib.load()
     mat, dim = _grid_matrix(po, rigid, method)
@@ -136,7 +145,28 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
         scl = float(po.scl)
         dat_yx = _ops.conv_down(dat_yx, _taps(po), po.ratio, scl, po.dim_thick)
     dat_yx = dat_yx.reshape(tuple(dat_x.shape))
-    if gain is not None:
+    if rician:
+        dat_x, dat_yx = dat_x.contiguous(), dat_yx.contiguous()
+        S = int(dat_x.shape[axis])
+        if gain is not None:
+            _check_gain(gain, S)
+        if weight is not None:
+            weight = weight.contiguous()
+            if weight.dtype != torch.float32 or tuple(weight.shape) != tuple(dat_x.shape):
+                raise ValueError('weight: one float32 weight per voxel of dat_x')
+        if slice_w is not None:
+            slice_w = slice_w.contiguous()
+            if slice_w.dtype != torch.float32 or slice_w.numel() != S:
+                raise ValueError('slice_w: one float32 weight per slice of dat_x along axis %d' % axis)
+        sums = torch.empty(3 * S, dtype=_F64, device=dat_x.device)
+        # (with diff the residual goes over A y in place: A y is not needed again)
+        check(lib.unires_rigid_terms_r(_ptr(dat_x), _ptr(dat_yx), None if weight is None else _ptr(weight),
+                                       None if slice_w is None else _ptr(slice_w), None if gain is None else _ptr(gain),
+                                       i3(dat_x.shape), axis, float(tau), _ptr(sums), _ptr(dat_yx) if diff else None,
+                                       _stream()))
+        # (L_s in a tensor of its own, as _compute_nll holds it: the same reduction, whatever the offset of a view)
+        ll = _slice_ll(tau, slice_w, sums[:2 * S]) + _rician_ll(slice_w, sums[2 * S:].clone())
+    elif gain is not None:
         dat_x, dat_yx = dat_x.contiguous(), dat_yx.contiguous()
         _check_gain(gain, dat_x.shape[axis])
         if weight is not None:
@@ -179,7 +209,7 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
     if not diff:
         return ll, None, None
     gr3 = _ops.pull_grad_affine(dat_y, M, dim).reshape(dim + (3,))
-    if gain is not None:
+    if rician or gain is not None:
         d = dat_yx  # (written above, with the sums)
     elif weight is not None:
         d = dat_yx  # (in place: A y is not needed again)
@@ -199,15 +229,17 @@ def _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=False, slice_w=None, a
 
 @on_device
 def _rigid_match(dat_x, dat_y, po, tau, rigid, sett, CtC=None, diff=False, verbose=0, slice_w=None, weight=None,
-                 gain=None):
+                 gain=None, rician=False):
     """Rigid matching term with the reference's return shapes (unires/_update.py:448-538):
     ll, gr (dim, 3) = grid_grad * residual, Hes (dim, 6) = outer(grid_grad) [* CtC].
     ``slice_w``: the observation's slice weights along ``po.dim_thick`` (``_rigid_terms``); ``weight``: its voxel
     weights, the shape of ``dat_x``; ``gain``: its slice gains along ``po.dim_thick``; the Hessian's weight is the
-    caller's ``CtC`` (``_ctc`` with the same weights and gains)."""
+    caller's ``CtC`` (``_ctc`` with the same weights and gains).  ``rician``: ll and the residual are the Rician term's
+    (``_rigid_terms``); the Hessian is what it is without - the majoriser's curvature."""
     weighted = slice_w is not None or weight is not None or gain is not None
     ll, gr3, d = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=diff, slice_w=slice_w,
-                              axis=_thick_axis(po) if weighted else None, weight=weight, gain=gain)
+                              axis=_thick_axis(po) if weighted or rician else None, weight=weight, gain=gain,
+                              rician=rician)
     if not diff:
         return ll, None, None
     Hes = torch.stack([gr3[..., 0] * gr3[..., 0], gr3[..., 1] * gr3[..., 1], gr3[..., 2] * gr3[..., 2],
@@ -284,7 +316,17 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
     w_mat = fl32(fl64(fl64(u e) e)) in the place of u, built once per repeat and call.  ll and sll are the data term
     alone: the ridge of ``sett.slice_gain`` does not depend on the rigid parameters.  The all-weights-zero rule
     applies unchanged.  Without ``sett.gain_gn`` the gains are ignored, as they were before the update could carry
-    them."""
+    them.
+
+    With ``sett.rician_gn`` a repeat with the Rician data term (``sett.noise_model = 'rician'``, not CT) takes its step
+    on sum_v W [1/2 tau (x - e A y)^2 + c(tau x e A y)], with W and e as above: the objective of the step and of every
+    line-search evaluation is that term, exactly - ``_compute_nll``'s statement for the repeat - and the residual is
+    W e (e A y - x R(z)), tau times which is its exact derivative; both come from one pass over the TRUE observation
+    ``xn.dat`` (``unires_rigid_terms_r``; ``xn._rician_dat`` is the y-update's and is never read here).  The Hessian's
+    weight ``CtC`` is exactly what the repeat would get without the Rician model, W e^2: the curvature of the quadratic
+    majoriser, which bounds the term's own second derivative tau [1 - tau x^2 R'(z)] from above, so the step is a
+    Gauss-Newton step on the majoriser at the current parameters, guarded by the line search on the exact term.  The
+    all-weights-zero rule is unchanged.  CT repeats, the Gaussian model and the switch off run what they ran."""
     lib = _lib.load()
     dev = yc.dat.device
     method = sett.method
@@ -314,6 +356,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
         g = _gn_weight(xn, sett)
         a = _slice_axis(xn)
         e = _gn_gain(xn, sett)
+        rc = bool(getattr(sett, 'rician_gn', False)) and _is_rician(xn, sett)  # (the Rician term: objective and residual)
         if u is not None:
             u = u[::sk[a]][:po.dim_x[a]].contiguous()
         uh = u  # (the Hessian's slice factor: u, or w_mat = u e^2 for a gained repeat, once per repeat and call)
@@ -338,7 +381,7 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
             rigid, d_rigid = _expm(q, basis, grad_X=True)
             D = torch.stack([torch.linalg.solve(po.mat_y, d_rigid[i].mm(mat)) for i in range(num_q)])
             ll, gr3, dg = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, diff=True, slice_w=u, axis=a, weight=g,
-                                       gain=e)
+                                       gain=e, rician=rc)
             d72 = (C.c_float * 72)(*D[:, :3, :].reshape(-1).float().tolist())
             check(lib.unires_rigid_sums(_ptr(gr3), _ptr(dg), _ptr(CtC) if CtC is not None else None,
                                         i3(dim), d72, _ptr(sums), _stream()))
@@ -358,7 +401,8 @@ def _update_rigid_channel(xc, yc, sett, max_niter_gn=1, num_linesearch=4, verbos
                 for n_ls in range(num_linesearch):
                     q = old_q - armijo * Update
                     rigid = _expm(q, basis)
-                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a, weight=g, gain=e)[0]
+                    ll = _rigid_terms(dat_x, dat_y, po, tau, rigid, sett, slice_w=u, axis=a, weight=g, gain=e,
+                                      rician=rc)[0]
                     if bool(ll < old_ll):
                         armijo = min(1.25 * armijo, 1.0)
                         if verbose >= 1:

@@ -446,10 +446,11 @@ def gain_rule(sums, tau, kappa, gain_max):
 
 
 @on_device
-def _gain_sums(xn, Ay):
+def _gain_sums(xn, Ay, obs=None):
     """``unires_gain_sums`` of one repeat: (3 S,) float64 on the device, W = xn.weight . xn.slice_w (1 where None),
-    ``Ay`` its A y WITHOUT gains."""
-    xd = xn.dat.contiguous()
+    ``Ay`` its A y WITHOUT gains.  ``obs``: what stands for the observation (None: ``xn.dat``) - the effective
+    observation of a Rician repeat under ``sett.rician_gn`` (``_update_slice_gains``)."""
+    xd = (xn.dat if obs is None else obs).contiguous()
     a = _slice_axis(xn)
     g, u = getattr(xn, 'weight', None), getattr(xn, 'slice_w', None)
     sums = torch.empty(3 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
@@ -476,8 +477,17 @@ def _update_slice_gains(x, y, sett, raw=None):
     repeat's current weights (``raw``: what ``_slice_sums`` kept of A y WITHOUT gains for this y, computed here where
     missing).  kappa is ``xn._gain_kappa``, which ``fit()`` fixes before the first iteration (computed here for a
     direct call).  The gain tensors are updated in place: their version counters tell the plans
-    (``sync_slice_gains``, at the next y-update's plan fetch) and the cached sum tau At (w e . x).  No read-back."""
+    (``sync_slice_gains``, at the next y-update's plan fetch) and the cached sum tau At (w e . x).  No read-back.
+
+    With ``sett.rician_gn`` a Rician repeat's sums are taken on its effective observation ``xn._rician_dat`` = x R(z),
+    which ``_update_admm`` has just written at the current (y, e): ``gain_rule`` on it is
+    the exact minimiser of the quadratic majoriser plus the ridge, so the gain step and the next y-update minimise one
+    surrogate in turn, and neither increases the Rician objective.  The rule's x != 0 mask is then read on x R(z),
+    which is 0 exactly where x is, apart from float32 underflow of the product.  kappa keeps reading ``xn.dat``.  A direct
+    call reads the buffer as it finds it - a caller who has moved y or e since it was written calls ``_rician_terms``
+    first, as ``_update_admm`` does; only where the repeat has none yet is it made here, at the current (y, e)."""
     reg, gmax = float(getattr(sett, 'gain_reg', 0.1)), float(getattr(sett, 'gain_max', 2.0))
+    rician = bool(getattr(sett, 'rician_gn', False))
     for c in range(len(x)):
         for n, xn in enumerate(x[c]):
             e = getattr(xn, 'slice_gain', None)
@@ -488,7 +498,12 @@ def _update_slice_gains(x, y, sett, raw=None):
                 Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
             if getattr(xn, '_gain_kappa', None) is None:
                 xn._gain_kappa = gain_kappa(xn, reg)
-            xn._gain_sums = _gain_sums(xn, Ay)  # (kept: what the last estimate was taken from)
+            obs = None
+            if rician and _is_rician(xn, sett):
+                if getattr(xn, '_rician_dat', None) is None:
+                    _rician_terms([[xn]], [y[c]], sett, {(0, 0): Ay}, sums=False)
+                obs = xn._rician_dat
+            xn._gain_sums = _gain_sums(xn, Ay, obs)  # (kept: what the last estimate was taken from)
             e.copy_(gain_rule(xn._gain_sums, xn.tau, xn._gain_kappa, gmax))
     return x
 

@@ -686,6 +686,22 @@ extern "C" int unires_rician_terms(const float *x, const float *ay, const float 
   return UNIRES_OK;
 }
 
+extern "C" int unires_rigid_terms_r(const float *x, const float *ay, const float *g, const float *u, const float *e,
+                                    const int32_t dim[3], int32_t axis, float tau, double *sums_dev, float *out,
+                                    void *stream) {
+  if (!x || !ay || !dim || !sums_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
+  if (out && (out == x || out == g)) return fail(UNIRES_ERR_ARG, "out must not be x or g: they are only read");
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  const size_t cols = 3 * (size_t)dim[axis];
+  if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), axis), &part)) return rc;
+  launch_rigid_terms_r(x, ay, g, u, e, mk(dim), axis, tau, part, sums_dev, out, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
 extern "C" int unires_slice_apply(const float *src, float *dst, const float *u, const int32_t dim[3], int32_t axis,
                                   void *stream) {
   if (!src || !dst || !u || !dim) return fail(UNIRES_ERR_NULL, "null argument");

@@ -21,4 +21,16 @@ namespace unires {
 void launch_rician_terms(const float *x, const float *ay, const float *g, const float *e, Dim3i d, int axis, float tau,
                          float *xt, double *part, double *sums, hipStream_t st);
 
+// The terms of the rigid Gauss-Newton step of a Rician repeat in one pass over x, ay [and g] (sett.rician_gn): p and z
+// as above, in registers; g a volume or nullptr (1), u and e S floats each or nullptr (1).
+//   sums[s], sums[S + s]: launch_rigid_terms_e's bits - without e launch_slice_sums' / launch_voxel_sums' on (x, ay);
+//   sums[2 S + s]: launch_rician_terms' sums;  part: 3 * S * slice_sums_parts(d, axis) doubles of scratch.
+//   out (nullptr: not written): launch_rigid_resid's / launch_rigid_resid_g's bits on (x~, p), x~ = fl32(x R(z)) the
+//     effective observation above, with t[s] = fl32(fl64(u[s]) fl64(e[s])) (1 for a missing table; neither: no factor)
+//     for u; +0 where x == 0 or p == 0 - the mask reads the true x.  out may be ay: a voxel is read and stored by one
+//     thread, once.
+// launch_rigid_terms_e's walk, grid, shares and finish order: no atomics, the same bits every run.
+void launch_rigid_terms_r(const float *x, const float *ay, const float *g, const float *u, const float *e, Dim3i d,
+                          int axis, float tau, double *part, double *sums, float *out, hipStream_t st);
+
 }  // namespace unires

@@ -134,8 +134,9 @@ def _init_slice_gains(x, sett, dev):
 def _init_rician(x, sett):
     """sett.noise_model as the iterations take it.  'gaussian' (the default): nothing but forgetting an earlier fit()'s
     effective observations.  'rician': ``sett.scaling``, ``sett.unified_rigid`` and ``sett.slice_gain`` are refused by
-    name (NotImplementedError) - those updates minimise the Gaussian term, and carrying the majoriser through them is not
-    built; every non-CT observation must be finite and >= 0 (ValueError naming channel and repeat; one reduction per
+    name (NotImplementedError) - those updates minimise the Gaussian term - unless ``sett.rician_gn`` carries the Rician
+    term through the rigid update and the gain estimate (``sett.scaling`` stays refused; ``sett.unified_rigid`` with
+    gains still needs ``sett.gain_gn``, ``_init_slice_gains``); every non-CT observation must be finite and >= 0 (ValueError naming channel and repeat; one reduction per
     repeat on the device, one read-back for all), and gets ``xn._rician_dat``, a float32 clone of ``xn.dat``: the
     effective observation of the FIRST y-update, which is therefore the Gaussian one (mu = 0 is a stationary point of
     the Rician likelihood: an effective observation x R(tau x A y0) of an all-zero first guess would stay 0).  Any
@@ -146,7 +147,7 @@ def _init_rician(x, sett):
                 if getattr(xn, '_rician_dat', None) is not None:
                     xn._rician_dat = None
         return x
-    for name in ('scaling', 'unified_rigid', 'slice_gain'):
+    for name in ('scaling',) if getattr(sett, 'rician_gn', False) else ('scaling', 'unified_rigid', 'slice_gain'):
         if getattr(sett, name, False):
             raise NotImplementedError("sett.%s with sett.noise_model = 'rician': that update minimises the Gaussian data "
                                       "term; carrying the Rician majoriser through it is not built" % name)
@@ -246,7 +247,11 @@ def fit(x, y, sett):
     first: one more observation-sized buffer per repeat), and ``obj`` carries the term c.  Observations must be finite
     and >= 0 (ValueError); ``sett.scaling``, ``sett.unified_rigid`` and ``sett.slice_gain`` are refused with it, by name
     (NotImplementedError); a user's fixed ``_input.slice_gain``, both robust rules, ``sett.mask_zeros`` and channel
-    streams work with it unchanged.  The default 'gaussian' runs what ran before the knob existed.
+    streams work with it unchanged.  The default 'gaussian' runs what ran before the knob existed.  With
+    ``sett.rician_gn`` the last two are allowed: the rigid update of a Rician repeat takes its step on the Rician term
+    (exact objective, exact gradient, the majoriser's curvature: ``_update_rigid``), and the gain rule is taken on the
+    effective observation the iteration has just written, so that it and the next y-update minimise one surrogate
+    (``_update_slice_gains``); ``sett.scaling`` stays refused.
 
     Voxel weights define it likewise.  With ``sett.voxel_gn`` the two Gauss-Newton updates of a repeat that has voxel
     weights take them too - beside its slice weights, where it has both - and under ``sett.voxel_robust`` they see the

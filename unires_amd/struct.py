@@ -155,9 +155,17 @@ class settings:
         # one on the effective observation x I1/I0(tau x mu) of the previous iteration's y (the first on x itself); one
         # A y and one streaming pass per repeat and iteration, and one more observation-sized buffer per repeat
         # (DESIGN 8.14).  CT repeats keep the Gaussian term.  Observations must be finite and >= 0.  sett.scaling,
-        # sett.unified_rigid and sett.slice_gain minimise the Gaussian term and are refused with it, by name.  Any
-        # other name: ValueError in fit()
+        # sett.unified_rigid and sett.slice_gain minimise the Gaussian term and are refused with it, by name, unless
+        # sett.rician_gn is set.  Any other name: ValueError in fit()
         self.noise_model = 'gaussian'
+        # the rigid Gauss-Newton update (sett.unified_rigid) and the gain estimate (sett.slice_gain) carry the Rician
+        # term of every repeat that has it: the rigid step's objective is the exact Rician term, its residual
+        # W e (e A y - x I1/I0(z)) the exact gradient, its Hessian weight W e^2 the majoriser's curvature - the one the
+        # step builds without the model (_rigid._update_rigid); the gain rule reads the effective observation
+        # (_update._update_slice_gains).  Off: fit() refuses both with 'rician', and the two updates run
+        # what they ran.  A switch only because those refusals are pinned by a test; not a modelling choice.
+        # sett.scaling stays refused with 'rician' either way, and sett.unified_rigid with gains still needs sett.gain_gn
+        self.rician_gn = False
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
