@@ -624,6 +624,38 @@ int unires_rician_terms(const float *x, const float *ay, const float *g, const f
 int unires_rigid_terms_r(const float *x, const float *ay, const float *g, const float *u, const float *e,
                          const int32_t dim[3], int32_t axis, float tau, double *sums_dev, float *out, void *stream);
 
+/* A smooth multiplicative bias field b = exp(beta) of an observation (no counterpart in the reference; sett.bias,
+ * _input.bias_coef): beta(i, j, z) = sum_{a < k0, b < k1, c < k2} coef[(a k1 + b) k2 + c] tx[a n0 + i] ty[b n1 + j]
+ * tz[c n2 + z], k = order (1 .. 8 along every axis), n = dim.  coef and the three tables are float64 on the device; a
+ * table holds at least k rows of n entries, row m the caller's phi_m (the unnormalised DCT-II function
+ * cos(pi m (2 i + 1) / (2 n)), phi_0 = 1).  beta is evaluated in float64 - folded over a, then b, then c, each in index
+ * order, one product and one addition per term - and clamped to +- beta_max (> 0).
+ *   b                     = fl32(exp(beta))
+ *   gb2 (NULL: not written) = fl32(fl64(fl64(g b) b)), g an x-space volume of weights or NULL (1): g b is exact in
+ *                  float64, the chain is rounded there once and once more to float32 - the voxel map the plan takes for
+ *                  a repeat with a field (unires_plan_set_voxel_weights)
+ *   xb  (NULL: not written) = fl32(x / b), +0 where x == 0: the effective observation the right-hand side reads
+ * One streaming pass: the coefficients are folded over the two outer axes once per plane and row; a voxel costs k2
+ * multiply-adds and one exp.  b, gb2, xb are buffers of their own (UNIRES_ERR_ARG); x and g are only read. */
+int unires_bias_field(const double *coef, const double *tx, const double *ty, const double *tz, const int32_t order[3],
+                      const int32_t dim[3], double beta_max, const float *g, const float *x, float *b, float *gb2,
+                      float *xb, void *stream);
+
+/* What the Gauss-Newton step of a bias field is assembled from, in one pass over x, mu, b [and g] (no counterpart in the
+ * reference): mu the prediction e . A y without the field, g a volume of weights or NULL (1), u dim[axis] slice weights
+ * or NULL (1), all on the device.  Per voxel m = fl32(b mu), r = fl64(m) - fl64(x), W = g u [x != 0]; everything after m
+ * in float64, each product rounded on its own.  With k = order, q = 2 k - 1 and the tables of unires_bias_field (at
+ * least q rows each):
+ *   out_dev[0]                                   = sum_v W r^2
+ *   out_dev[1 + (a k1 + b) k2 + c]               = sum_v W m r  phi_a(i) phi_b(j) phi_c(z),   a < k0, b < k1, c < k2
+ *   out_dev[1 + k0 k1 k2 + (a q1 + b) q2 + c]    = sum_v W m^2 phi_a(i) phi_b(j) phi_c(z),   a < q0, b < q1, c < q2
+ * order = (0, 0, 0): out_dev[0] alone, and the tables are not read - a line-search evaluation.  float64 sums in a fixed
+ * order (no atomics: the same bits every run); every entry is written with a plain store.  Errors as for
+ * unires_slice_sums; orders outside 1 .. 8 (and not all 0): UNIRES_ERR_ARG. */
+int unires_bias_terms(const float *x, const float *mu, const float *b, const float *g, const float *u, int32_t axis,
+                      const double *tx, const double *ty, const double *tz, const int32_t order[3], const int32_t dim[3],
+                      double *out_dev, void *stream);
+
 /* dst[v] = fl32(u[s(v)] src[v]) over a z-fastest volume `dim`, s(v) = v's index along `axis`, u dim[axis] floats on the
  * device: the pass of a slice-weighted repeat on its own, without mask and without a `done` word (no counterpart in the
  * reference).  dst == src: in place; dst != src: src is only read.  With the gains of a repeat as u it makes e . (A y),

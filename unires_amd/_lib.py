@@ -148,6 +148,10 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     'unires_rigid_terms_r': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32,
                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_bias_field': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, c_i32x3, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'unires_bias_terms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, c_i32x3, c_i32x3, C.c_void_p, C.c_void_p]),
     'unires_slice_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_void_p]),
     'unires_voxel_apply': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32x3, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),

@@ -211,8 +211,11 @@ def _slice_weights(x):
 
 def _voxel_weights(x):
     """Per repeat the voxel weights ``xn.weight`` or None, as ``ChannelPlan.sync_voxel_weights`` takes them; None when
-    no repeat of the channel has some."""
-    gs = [getattr(xn, 'weight', None) for xn in x]
+    no repeat of the channel has some.  For a repeat with a bias field the plan's map is ``xn._bias_weight`` = g b^2
+    (``_update._bias_compose``; g = 1 without weights): W b^2 in the matrix and, with the effective observation x / b,
+    W b x on the right.  Everything else that reads ``xn.weight`` - the sums, the Huber rule, its prior - keeps the
+    true g."""
+    gs = [getattr(xn, 'weight', None) if getattr(xn, '_bias_weight', None) is None else xn._bias_weight for xn in x]
     return gs if any(g is not None for g in gs) else None
 
 

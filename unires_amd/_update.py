@@ -77,7 +77,12 @@ def _is_rician(xn, sett):
 def _obs(xn, sett):
     """What the y-update's right-hand side reads for repeat ``xn``: under the Rician model the effective observation
     ``xn._rician_dat`` (fit()'s clone of ``xn.dat`` before the first iteration, x R(tau x e . A y) after each), else
-    ``xn.dat``.  Masks, weights and every residual keep reading ``xn.dat``."""
+    ``xn.dat``.  For a repeat with a bias field it is ``xn._bias_dat`` = x / b (``_bias_compose``): with the plan's
+    voxel map g b^2 the term reads A^T (W b x) (fit() refuses a field under the Rician model).  Masks, weights and every
+    residual keep reading ``xn.dat``."""
+    xb = getattr(xn, '_bias_dat', None)
+    if xb is not None:
+        return xb
     xt = getattr(xn, '_rician_dat', None)
     return xt if xt is not None and _is_rician(xn, sett) else xn.dat
 
@@ -302,8 +307,264 @@ def _gained(Ay, xn, out=None):
     return out
 
 
+def _bias(sett):
+    """sett.bias (False where the settings object has none): every non-CT observation without a user's
+    ``_input.bias_coef`` gets a smooth multiplicative bias field whose coefficients take one Gauss-Newton step after
+    each ADMM iteration (``_update_bias``)."""
+    return bool(getattr(sett, 'bias', False))
+
+
+BIAS_MAX_ORDER = 8
+BIAS_STEPS = tuple(2.0 ** -p for p in range(6))  # the line search's step lengths: 1, 1/2, ..., 2^-5
+
+
+def _has_field(xn):
+    """Repeat ``xn`` has a bias field: ``fit()`` (``_init_bias``) has made its buffers."""
+    return getattr(xn, '_bias_b', None) is not None
+
+
+def bias_orders_of(shape, vx, cutoff):
+    """k_d = clamp(ceil(2 n_d vx_d / cutoff), 1, min(8, n_d)) per axis: the cosines whose half-period n_d vx_d / m is
+    no shorter than ``cutoff`` / 2 ... mm, at least the constant, at most 8 and at most the complete basis."""
+    import math
+    return tuple(int(min(max(math.ceil(2.0 * int(n) * float(v) / float(cutoff)), 1), min(BIAS_MAX_ORDER, int(n))))
+                 for n, v in zip(shape, vx))
+
+
+def bias_orders(xn, sett):
+    """The orders (kx, ky, kz) of the bias field of repeat ``xn`` on its own voxel grid, in the caller's layout
+    (``bias_orders_of`` on ``xn.dat.shape``, the voxel sizes of ``xn.mat`` and ``sett.bias_cutoff``)."""
+    return bias_orders_of(tuple(xn.dat.shape), voxel_size(xn.mat).tolist(), getattr(sett, 'bias_cutoff', 60.0))
+
+
+def bias_tables(shape, orders):
+    """The three cosine tables of a field of ``orders`` on a grid ``shape``, float64 numpy (2 k_d - 1, n_d): row m is
+    the unnormalised DCT-II function phi_m(i) = cos(pi m (2 i + 1) / (2 n)), phi_0 = 1.  The first k_d rows synthesise
+    the field; all 2 k_d - 1 are what the projection of W m^2 is taken on (``bias_hessian``).  Built on the host and
+    handed to the kernels as they are: the float64 restatement under tests/ reads the same bits."""
+    import numpy as np
+    out = []
+    for n, k in zip(shape, orders):
+        m = np.arange(2 * int(k) - 1, dtype=np.float64)[:, None]
+        i = np.arange(int(n), dtype=np.float64)[None, :]
+        out.append(np.ascontiguousarray(np.cos(np.pi * m * (2.0 * i + 1.0) / (2.0 * int(n)))))
+    return tuple(out)
+
+
+def bias_lambda(shape, vx, orders, kappa, sett):
+    """The diagonal of the coefficients' prior, float64 numpy (kx, ky, kz): Lambda = kappa bias_reg (1 + sum_d
+    (bias_cutoff m_d / (2 n_d vx_d))^2) - a ridge that grows with the square of a term's spatial frequency in units of
+    the cut-off, and is kappa bias_reg on the constant term."""
+    import numpy as np
+    cut, reg = float(getattr(sett, 'bias_cutoff', 60.0)), float(getattr(sett, 'bias_reg', 0.01))
+    f = [(cut * np.arange(int(k), dtype=np.float64) / (2.0 * int(n) * float(v))) ** 2
+         for n, v, k in zip(shape, vx, orders)]
+    return float(kappa) * reg * (1.0 + f[0][:, None, None] + f[1][None, :, None] + f[2][None, None, :])
+
+
+def bias_kappa(xn):
+    """kappa = tau sum_{x != 0} x^2 of one observation: the curvature the constant term has at b = 1 on a prediction as
+    large as the data.  A float64 sum on the device; a 0-d float64 device tensor, not read back here."""
+    xd = xn.dat.double()
+    return float(xn.tau) * (xd * xd).sum()
+
+
+def bias_hessian(P, orders):
+    """sum_v f(v) Phi_k(v) Phi_l(v) for all pairs of basis functions, (K, K) float64 numpy, K = kx ky kz, from ``P``, the
+    projection of f onto the orders < 2 k_d - 1 ((2 kx - 1, 2 ky - 1, 2 kz - 1)): since phi_m phi_m' =
+    (phi_|m - m'| + phi_(m + m')) / 2 along every axis, an entry is 1/8 of the sum of eight entries of ``P``."""
+    import numpy as np
+    P = np.asarray(P, dtype=np.float64)
+    kx, ky, kz = (int(k) for k in orders)
+
+    def pair(k):
+        m = np.arange(k)
+        return np.abs(m[:, None] - m[None, :]), m[:, None] + m[None, :]
+
+    H = np.zeros((kx, ky, kz, kx, ky, kz), dtype=np.float64)
+    for sa in pair(kx):
+        for sb in pair(ky):
+            for sc in pair(kz):
+                H += P[sa[:, None, None, :, None, None], sb[None, :, None, None, :, None],
+                       sc[None, None, :, None, None, :]]
+    return H.reshape(kx * ky * kz, kx * ky * kz) / 8.0
+
+
+def bias_energy(S, c, lam, tau):
+    """E(c) = 1/2 tau S + 1/2 c^T Lambda c: ``S`` = sum W r^2 at the field of ``c``, ``lam`` the diagonal of Lambda."""
+    import numpy as np
+    c = np.asarray(c, dtype=np.float64)
+    return 0.5 * float(tau) * float(S) + 0.5 * float((np.asarray(lam, dtype=np.float64) * c * c).sum())
+
+
+def bias_step(c, G, P, lam, tau):
+    """The float64 host rule of one Gauss-Newton step on the coefficients ``c`` ((kx, ky, kz) numpy): ``G`` the
+    projection of W m r onto the orders < k, ``P`` that of W m^2 onto the orders < 2 k - 1 (``unires_bias_terms``),
+    ``lam`` the diagonal of Lambda.  gradient = tau G + Lambda c; H = tau ``bias_hessian(P)`` + Lambda, the Gauss-Newton
+    curvature (positive semi-definite: the exact one, which adds W m r to W m^2, can be negative); Delta = -H^-1 gradient.
+    Returns (candidates, gradient, H): the candidates c + s Delta for s = 1, 1/2, ..., 2^-5 in the order the line search
+    tries them - an empty list where H is singular or Delta is not finite (no data and no prior: c stays)."""
+    import numpy as np
+    c = np.asarray(c, dtype=np.float64)
+    lam = np.asarray(lam, dtype=np.float64)
+    grad = float(tau) * np.asarray(G, dtype=np.float64).reshape(c.shape) + lam * c
+    H = float(tau) * bias_hessian(P, c.shape) + np.diag(lam.reshape(-1))
+    try:
+        delta = -np.linalg.solve(H, grad.reshape(-1)).reshape(c.shape)
+    except np.linalg.LinAlgError:
+        return [], grad, H
+    if not np.isfinite(delta).all():
+        return [], grad, H
+    return [c + s * delta for s in BIAS_STEPS], grad, H
+
+
+def _bias_dev_tables(shape, orders, dev):
+    return tuple(torch.from_numpy(t).to(dev) for t in bias_tables(shape, orders))
+
+
 @on_device
-def _slice_sums(x, y, sett, ays=None, raw=None, proj=None):
+def _bias_field_call(coef, tabs, shape, beta_max, b, g=None, x=None, gb2=None, xb=None):
+    """``unires_bias_field``: ``coef`` (kx, ky, kz) float64 (any device; moved to ``b``'s), ``tabs`` the device tables."""
+    coef = torch.as_tensor(coef, dtype=torch.float64)
+    cd = coef.to(b.device).contiguous()
+    check(_lib.load().unires_bias_field(_ptr(cd), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), i3(coef.shape), i3(shape),
+                                        float(beta_max), None if g is None else _ptr(g), None if x is None else _ptr(x),
+                                        _ptr(b), None if gb2 is None else _ptr(gb2), None if xb is None else _ptr(xb),
+                                        _stream()))
+    return b
+
+
+def bias_field(coef, shape, device='cuda', bias_max=4.0):
+    """The bias field b = exp(beta) of the coefficients ``coef`` ((kx, ky, kz), k_d <= min(8, shape[d]); what
+    ``fit()`` returns in ``info['bias']``) on a voxel grid ``shape``, synthesised on the device: a float32 tensor of
+    that shape.  log b is clamped to +- log(``bias_max``), as ``fit()`` clamps it (``sett.bias_max``)."""
+    import math
+    coef = torch.as_tensor(coef, dtype=torch.float64).detach().cpu()
+    shape = tuple(int(n) for n in shape)
+    if coef.dim() != 3 or len(shape) != 3 or any(not 1 <= int(k) <= min(BIAS_MAX_ORDER, n)
+                                                   for k, n in zip(coef.shape, shape)):
+        raise ValueError('bias_field: coef must be (kx, ky, kz) with 1 <= k_d <= min(8, shape[d]), got %s on %s'
+                         % (tuple(coef.shape), shape))
+    if not bool(torch.isfinite(coef).all()):
+        raise ValueError('bias_field: coef must be finite')
+    if not float(bias_max) > 1:
+        raise ValueError('bias_field: bias_max must be > 1')
+    dev = torch.device(device)
+    b = torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(b.device):
+        return _bias_field_call(coef, _bias_dev_tables(shape, tuple(coef.shape), b.device), shape,
+                                math.log(float(bias_max)), b)
+
+
+@on_device
+def _bias_terms(xn, mu, b, full=True):
+    """``unires_bias_terms`` of one repeat on the prediction ``mu`` = e . A y and the field ``b``: a float64 device
+    tensor, (1 + K + Q,) with ``full`` (sum W r^2, the projection of W m r, the projection of W m^2), else (1,)."""
+    xd = xn.dat.contiguous()
+    k = tuple(xn._bias_coef.shape) if full else (0, 0, 0)
+    q = tuple(2 * v - 1 for v in k) if full else (0, 0, 0)
+    out = torch.empty(1 + k[0] * k[1] * k[2] + q[0] * q[1] * q[2], dtype=torch.float64, device=xd.device)
+    g, u = getattr(xn, 'weight', None), getattr(xn, 'slice_w', None)
+    t = xn._bias_tab
+    check(_lib.load().unires_bias_terms(_ptr(xd), _ptr(mu.contiguous()), _ptr(b), None if g is None else _ptr(g.contiguous()),
+                                        None if u is None else _ptr(u.contiguous()), _slice_axis(xn), _ptr(t[0]),
+                                        _ptr(t[1]), _ptr(t[2]), i3(k), i3(xd.shape), _ptr(out), _stream()))
+    return out
+
+
+def _fielded(mu, xn, out=None):
+    """b . mu: the prediction of a repeat with a bias field (``unires_voxel_apply``, one float32 product per voxel; out
+    of place unless ``out`` is ``mu``).  ``mu`` itself where the repeat has none."""
+    if not _has_field(xn):
+        return mu
+    out = torch.empty_like(mu) if out is None else out
+    check(_lib.load().unires_voxel_apply(_ptr(mu), _ptr(out), _ptr(xn._bias_b), None, None, i3(mu.shape), 0, 0, None,
+                                         _stream()))
+    return out
+
+
+def _predicted(Ay, xn, out=None):
+    """b . e . (A y): the prediction of repeat ``xn`` - the gains first (``_gained``), then the field (``_fielded``);
+    out of place unless ``out`` is ``Ay``.  ``Ay`` itself where the repeat has neither."""
+    mu = _gained(Ay, xn, out)
+    return _fielded(mu, xn, out=mu if (mu is not Ay or out is Ay) else None)
+
+
+@on_device
+def _bias_compose(x, sett, force=False):
+    """The two volumes the plan reads for every repeat with a field, recomposed where its coefficients or its voxel
+    weights changed since they were last written (``force``: regardless): ``xn._bias_weight`` = g b^2 (what
+    ``_project._voxel_weights`` hands the plan for ``xn.weight``) and ``xn._bias_dat`` = x / b (what ``_obs`` hands the
+    right-hand side), with ``xn._bias_b`` itself, in one ``unires_bias_field`` pass.  Their version counters are bumped:
+    they tell the plan's copy of the map (``sync_voxel_weights``) and the cached sum tau At (W b . x)."""
+    import math
+    beta_max = math.log(float(getattr(sett, 'bias_max', 4.0)))
+    for xc in x:
+        for xn in xc:
+            if not _has_field(xn):
+                continue
+            g = getattr(xn, 'weight', None)
+            key = (xn._bias_rev, None if g is None else (id(g), g._version))
+            if not force and key == getattr(xn, '_bias_key', None):
+                continue
+            _bias_field_call(xn._bias_coef, xn._bias_tab, xn.dat.shape, beta_max, xn._bias_b,
+                             g=None if g is None else g.contiguous(), x=xn.dat.contiguous(), gb2=xn._bias_weight,
+                             xb=xn._bias_dat)
+            torch.autograd.graph.increment_version(xn._bias_weight)
+            torch.autograd.graph.increment_version(xn._bias_dat)
+            xn._bias_key = key
+    return x
+
+
+@on_device
+def _update_bias(x, y, sett, raw=None):
+    """One Gauss-Newton step on the bias coefficients of every repeat ``fit()`` estimates a field for
+    (``xn._bias_est``), at the current y and the repeat's current weights (``raw``: what ``_slice_sums`` kept of the
+    prediction e . A y WITHOUT the field for this y, computed here where missing).  One ``unires_bias_terms`` pass gives
+    sum W r^2, the projection of W m r and the projection of W m^2; they are read back - one read-back per repeat and
+    iteration - and the K x K algebra of the step (``bias_step``: Hessian assembly, solve, candidates) is numpy on the
+    host in float64, as ``_update_rigid`` does its 6 x 6 algebra.  The line search then tries s = 1, 1/2, ..., 2^-5: the
+    candidate's field is synthesised (``unires_bias_field``), its objective taken by the same kernel called for the
+    objective alone (one 8-byte read-back each), and the first s with E(c + s Delta) <= E(c) is accepted; otherwise c
+    stays.  ``xn._bias_coef`` and ``xn._bias_b`` are updated; the plan's volumes follow in ``_bias_compose``.
+    ``xn._bias_E`` keeps (E before, E after, s) of the last step (s = 0: kept).  A user's fixed ``_input.bias_coef``
+    is never touched."""
+    import math
+    import numpy as np
+    beta_max = math.log(float(getattr(sett, 'bias_max', 4.0)))
+    for c in range(len(x)):
+        for n, xn in enumerate(x[c]):
+            if not _has_field(xn) or not getattr(xn, '_bias_est', False):
+                continue
+            mu = None if raw is None else raw.get((c, n))
+            if mu is None:
+                Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+                mu = _gained(Ay, xn, out=Ay)
+            tau, lam = float(xn.tau), xn._bias_lam
+            c0 = xn._bias_coef.numpy().copy()
+            k = c0.shape
+            K = c0.size
+            v = _bias_terms(xn, mu, xn._bias_b).cpu().numpy()  # the one read-back of the step
+            E0 = bias_energy(v[0], c0, lam, tau)
+            cands, _, _ = bias_step(c0, v[1:1 + K].reshape(k), v[1 + K:].reshape(tuple(2 * d - 1 for d in k)), lam, tau)
+            xn._bias_E = (E0, E0, 0.0)
+            if not np.isfinite(E0):
+                continue
+            bc = torch.empty_like(xn._bias_b)
+            for s, cand in zip(BIAS_STEPS, cands):
+                _bias_field_call(cand, xn._bias_tab, xn.dat.shape, beta_max, bc)
+                E1 = bias_energy(float(_bias_terms(xn, mu, bc, full=False).cpu()[0]), cand, lam, tau)
+                if E1 <= E0:
+                    xn._bias_coef = torch.from_numpy(np.ascontiguousarray(cand))
+                    xn._bias_b, bc = bc, xn._bias_b
+                    xn._bias_rev += 1
+                    xn._bias_E = (E0, E1, s)
+                    break
+    return x
+
+
+@on_device
+def _slice_sums(x, y, sett, ays=None, raw=None, proj=None, mus=None):
     """{(c, n): (2 S,) float64 device tensor} for every repeat that has slice or voxel weights or gains: SSE_s =
     sum_{v in s, x != 0} (x - A y)^2 and N_s = #{v in s : x != 0} per slice along ``po.dim_thick``
     (``unires_slice_sums``; float32 terms, float64 sums in a fixed order); for a repeat with voxel weights
@@ -313,7 +574,9 @@ def _slice_sums(x, y, sett, ays=None, raw=None, proj=None):
     (c, n): A y of the voxel-weighted repeats).  For a repeat with gains ``xn.slice_gain`` the prediction is
     e . (A y) throughout (``_gained``), and ``raw``, a dict, receives (c, n): its A y WITHOUT gains, which
     ``_update_slice_gains`` estimates from.  ``proj``: {(c, n): A y without gains} already computed for this y (the
-    Rician repeats', ``_rician_terms``), only read.  Nothing is read back."""
+    Rician repeats', ``_rician_terms``), only read.  For a repeat with a bias field the prediction is b . e . (A y)
+    (``_fielded``), and ``mus``, a dict, receives (c, n): its e . A y WITHOUT the field, which ``_update_bias`` steps
+    from.  Nothing is read back."""
     lib = _lib.load()
     out = {}
     for c in range(len(x)):
@@ -328,6 +591,10 @@ def _slice_sums(x, y, sett, ays=None, raw=None, proj=None):
                 if raw is not None:
                     raw[(c, n)] = Ay
                 Ay = _gained(Ay, xn)
+            if _has_field(xn):  # (the field after the gains: the prediction is b . e . A y, out of place)
+                if mus is not None:
+                    mus[(c, n)] = Ay
+                Ay = _fielded(Ay, xn)
             xd = xn.dat.contiguous()
             a = _slice_axis(xn)
             sums = torch.empty(2 * int(xd.shape[a]), dtype=torch.float64, device=xd.device)
@@ -378,7 +645,7 @@ def _update_voxel_weights(x, y, sett, ays=None):
             Ay = None if ays is None else ays.get((c, n))
             if Ay is None:
                 Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
-                Ay = _gained(Ay, xn, out=Ay)  # (a repeat with gains: the residual is x - e . A y)
+                Ay = _predicted(Ay, xn, out=Ay)  # (a repeat with gains or a field: the residual is x - b . e . A y)
             xd = xn.dat.contiguous()
             prior = getattr(xn, '_weight_prior', None)
             if mad:
@@ -577,7 +844,9 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None, proj
     the gains' prior 1/2 kappa sum_s (e_s - 1)^2 of every estimated repeat is part of the data term's value.  Under
     ``sett.noise_model = 'rician'`` a non-CT repeat adds sum_s u_s L_s (``_rician_ll``; ``rician``: ``_rician_terms``'
     sums for this y, computed here - without touching the effective observations - when None; ``proj``: the A y
-    without gains it computed); the term -log(tau x), which does not depend on y, is left out."""
+    without gains it computed); the term -log(tau x), which does not depend on y, is left out.  A repeat with a bias
+    field is predicted by b . e . A y (``_predicted``), and under ``sett.bias`` the prior 1/2 c^T Lambda c of every
+    estimated field is part of the data term's value."""
     dev = y[0].dat.device
     if rician is None and _noise_model(sett) == 'rician':
         proj = {} if proj is None else proj
@@ -590,6 +859,8 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None, proj
     sse = torch.zeros((), dtype=torch.float64, device=dev)
     for c in range(len(x)):
         for n in range(len(x[c])):
+            if _has_field(x[c][n]) and getattr(x[c][n], '_bias_est', False):  # (the estimated fields' prior)
+                nll_xy = nll_xy + bias_energy(0.0, x[c][n]._bias_coef.numpy(), x[c][n]._bias_lam, 0.0)
             if rician and (c, n) in rician:
                 nll_xy = nll_xy + _rician_ll(getattr(x[c][n], 'slice_w', None), rician[(c, n)])
             if (c, n) in slice_sums:
@@ -603,6 +874,7 @@ def _compute_nll(x, y, sett, rho, sum_dtype=torch.float64, slice_sums=None, proj
             Ay = None if proj is None else proj.get((c, n))
             if Ay is None:
                 Ay = _proj('A', y[c].dat, x[c], y[c], n=n, method=sett.method, do=sett.do_proj)
+            Ay = _predicted(Ay, x[c][n])  # (a repeat with a field and no weights: b . A y, out of place)
             xd = x[c][n].dat.contiguous()
             check(lib.unires_masked_sse(_ptr(xd), _ptr(Ay), xd.numel(), _ptr(sse), _stream()))
             nll_xy = nll_xy + 0.5 * float(x[c][n].tau) * sse
@@ -713,17 +985,22 @@ def _update_admm(x, y, z, w, rho, tmp, obj, n_iter, sett, info=None):
     # observation of the next y-update, written here; without an objective nothing but that is written)
     proj = {} if _noise_model(sett) == 'rician' else None
     rician = _rician_terms(x, y, sett, proj, sums=want_obj) if proj is not None else None
-    sums = _slice_sums(x, y, sett, ays, raw, proj) if want_obj or _slice_robust(sett) or _slice_gain(sett) else None
+    mus = {} if _bias(sett) else None  # (e . A y without the field of the repeats with one, for the bias step)
+    sums = _slice_sums(x, y, sett, ays, raw, proj, mus) if want_obj or _slice_robust(sett) or _slice_gain(sett) else None
     if want_obj:
         obj[n_iter, 0], obj[n_iter, 1], obj[n_iter, 2] = _compute_nll(x, y, sett, rho, slice_sums=sums, proj=proj,
                                                                      rician=rician)
     z, w, tmp = _update_zw(y, z, w, rho, tmp, sett)
     if _slice_gain(sett):  # (before the rules below write their weights: it reads the W this iteration's y-update used;
         _update_slice_gains(x, y, sett, raw)  # sums and ays keep the prediction e . A y of that y-update's gains)
+    if _bias(sett):  # (in the same place, for the same reason; fit() refuses the two together)
+        _update_bias(x, y, sett, mus)
     if _slice_robust(sett):  # (after the objective: each iteration's is taken with the weights its y-update used)
         _update_slice_weights(x, y, sett, sums)
     if _voxel_robust(sett):  # (likewise; A y is computed there where the sums above were not wanted)
         _update_voxel_weights(x, y, sett, ays)
+    if any(_has_field(xn) for xc in x for xn in xc):  # (after the rules: g b^2 and x / b follow the new c and g)
+        _bias_compose(x, sett)
     # An iteration is enqueue-only (no read-back): a host loop would run ahead until the hardware queue is
     # full and then spin inside every launch call.  The pacer parks the thread - sleeping between looks at a
     # stream mark (_host.StreamMark) - until the device is at most `host_pace` iterations behind (settings.host_pace; 0: off).

@@ -15,6 +15,7 @@
 
 #include "admm.hpp"
 #include "api_internal.hpp"
+#include "bias.hpp"
 #include "conv.hpp"
 #include "coreg.hpp"
 #include "noise.hpp"
@@ -698,6 +699,43 @@ extern "C" int unires_rigid_terms_r(const float *x, const float *ay, const float
   const size_t cols = 3 * (size_t)dim[axis];
   if (int rc = reduce_scratch(st, cols * (size_t)slice_sums_parts(mk(dim), axis), &part)) return rc;
   launch_rigid_terms_r(x, ay, g, u, e, mk(dim), axis, tau, part, sums_dev, out, st);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_bias_field(const double *coef, const double *tx, const double *ty, const double *tz,
+                                 const int32_t order[3], const int32_t dim[3], double beta_max, const float *g,
+                                 const float *x, float *b, float *gb2, float *xb, void *stream) {
+  if (!coef || !tx || !ty || !tz || !order || !dim || !b) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  for (int a = 0; a < 3; ++a)
+    if (order[a] < 1 || order[a] > kBiasMaxOrder) return fail(UNIRES_ERR_ARG, "bias orders: 1 .. 8 along every axis");
+  if (!(beta_max > 0.0)) return fail(UNIRES_ERR_ARG, "the bound on log b must be positive");
+  if (xb && !x) return fail(UNIRES_ERR_NULL, "x / b needs x");
+  if (b == x || b == g || (gb2 && (gb2 == x || gb2 == g || gb2 == b)) || (xb && (xb == x || xb == g || xb == b || xb == gb2)))
+    return fail(UNIRES_ERR_ARG, "b, gb2 and xb must be buffers of their own: x and g are only read");
+  launch_bias_field(coef, tx, ty, tz, mk(order), mk(dim), beta_max, g, x, b, gb2, xb, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return UNIRES_OK;
+}
+
+extern "C" int unires_bias_terms(const float *x, const float *mu, const float *b, const float *g, const float *u,
+                                 int32_t axis, const double *tx, const double *ty, const double *tz,
+                                 const int32_t order[3], const int32_t dim[3], double *out_dev, void *stream) {
+  if (!x || !mu || !b || !order || !dim || !out_dev) return fail(UNIRES_ERR_NULL, "null argument");
+  if (!dims_ok(dim)) return fail(UNIRES_ERR_DIM, "bad dims");
+  if (axis < 0 || axis > 2) return fail(UNIRES_ERR_ARG, "bad axis");
+  const bool none = order[0] == 0 && order[1] == 0 && order[2] == 0;
+  if (!none) {
+    for (int a = 0; a < 3; ++a)
+      if (order[a] < 1 || order[a] > kBiasMaxOrder)
+        return fail(UNIRES_ERR_ARG, "bias orders: 1 .. 8 along every axis, or all 0 for the objective alone");
+    if (!tx || !ty || !tz) return fail(UNIRES_ERR_NULL, "null argument");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = nullptr;
+  if (int rc = reduce_scratch(st, bias_terms_scratch(mk(dim), mk(order)), &part)) return rc;
+  launch_bias_terms(x, mu, b, g, u, axis, tx, ty, tz, mk(order), mk(dim), part, out_dev, st);
   CHECK_LAUNCH();
   return UNIRES_OK;
 }

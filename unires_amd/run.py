@@ -164,6 +164,84 @@ def _init_rician(x, sett):
     return x
 
 
+BIAS_STATE = ('_bias_coef', '_bias_est', '_bias_tab', '_bias_lam', '_bias_kappa', '_bias_b', '_bias_weight', '_bias_dat',
+              '_bias_key', '_bias_E')
+
+
+def _init_bias(x, sett, dev):
+    """The observations' bias fields as the iterations take them.  A user's ``_input.bias_coef`` is
+    validated - (kx, ky, kz) with 1 <= k_d <= min(8, n_d), real, finite; ValueError naming channel and repeat - and used
+    as given, with ``sett.bias`` on or off: it is never re-estimated.  With ``sett.bias`` every other non-CT repeat
+    starts from zeros of ``bias_orders``' shape (b = 1), and kappa = tau sum_{x != 0} x^2 (a float64 device sum, read
+    back once, here) fixes its prior Lambda for the whole fit, so that the objective is one function.  Every repeat with
+    a field gets three observation-sized float32 buffers - b, the plan's voxel map g b^2 and the effective observation
+    x / b: 12 bytes per voxel of the observation - and its cosine tables on the device, composed here once.  The field
+    is carried by the y-update and the objective alone: ``sett.noise_model = 'rician'``, ``sett.scaling``,
+    ``sett.unified_rigid`` and ``sett.slice_gain`` (a per-slice constant would be left unidentified between the two)
+    are refused with it, by name (NotImplementedError).  Without ``sett.bias`` and without coefficients: nothing but
+    forgetting an earlier fit()'s fields."""
+    import numpy as np
+    from ._update import (BIAS_MAX_ORDER, _bias, _bias_compose, _bias_dev_tables, bias_kappa, bias_lambda, bias_orders)
+    from .spatial import voxel_size
+    on = _bias(sett)
+    for xc in x:
+        for xn in xc:
+            for name in BIAS_STATE:
+                setattr(xn, name, None)
+            xn._bias_rev = 0
+    if not on and all(getattr(xn, 'bias_coef', None) is None for xc in x for xn in xc):
+        return x
+    what = 'a bias field (sett.bias, _input.bias_coef)'
+    if _noise_model(sett) == 'rician':
+        raise NotImplementedError("%s with sett.noise_model = 'rician': the field under the Rician majoriser is not "
+                                  "built" % what)
+    for name, why in (('scaling', 'the even / odd scaling update does not carry the field'),
+                      ('unified_rigid', 'the rigid Gauss-Newton update does not carry the field'),
+                      ('slice_gain', 'estimating both would leave a per-slice constant unidentified')):
+        if getattr(sett, name, False):
+            raise NotImplementedError('%s with sett.%s: %s' % (what, name, why))
+    if on and not float(getattr(sett, 'bias_cutoff', 60.0)) > 0:
+        raise ValueError('sett.bias_cutoff must be positive')
+    if on and not float(getattr(sett, 'bias_reg', 0.01)) >= 0:
+        raise ValueError('sett.bias_reg must be >= 0')
+    if not float(getattr(sett, 'bias_max', 4.0)) > 1:
+        raise ValueError('sett.bias_max must be > 1')
+    todo = []
+    for c, xc in enumerate(x):
+        for n, xn in enumerate(xc):
+            given = getattr(xn, 'bias_coef', None)
+            est = on and given is None and not getattr(xn, 'ct', False)
+            if given is None and not est:
+                continue
+            shape = tuple(int(d) for d in xn.dat.shape)
+            if given is None:
+                coef = torch.zeros(bias_orders(xn, sett), dtype=torch.float64)
+            else:
+                coef = torch.as_tensor(given)
+                if coef.dim() != 3 or any(not 1 <= int(k) <= min(BIAS_MAX_ORDER, d) for k, d in zip(coef.shape, shape)):
+                    raise ValueError('x[%d][%d].bias_coef has shape %s, expected (kx, ky, kz) with 1 <= k_d <= min(8, n_d) '
+                                     'on an observation of shape %s' % (c, n, tuple(coef.shape), shape))
+                if coef.is_complex() or coef.dtype == torch.bool:
+                    raise ValueError('x[%d][%d].bias_coef must be real numbers' % (c, n))
+                coef = coef.detach().to(device='cpu', dtype=torch.float64).contiguous().clone()
+                if not bool(torch.isfinite(coef).all()):
+                    raise ValueError('x[%d][%d].bias_coef must be finite' % (c, n))
+            todo.append((xn, coef, est, shape))
+    for xn, coef, est, shape in todo:
+        xn._bias_coef, xn._bias_est = coef, est
+        xn._bias_tab = _bias_dev_tables(shape, tuple(coef.shape), dev)
+        xn._bias_b = torch.empty(shape, dtype=torch.float32, device=dev)
+        xn._bias_weight = torch.empty(shape, dtype=torch.float32, device=dev)
+        xn._bias_dat = torch.empty(shape, dtype=torch.float32, device=dev)
+        if est:
+            xn._bias_kappa = float(bias_kappa(xn))
+            xn._bias_lam = bias_lambda(shape, voxel_size(xn.mat).tolist(), tuple(coef.shape), xn._bias_kappa, sett)
+        else:
+            xn._bias_lam = np.zeros(tuple(coef.shape))
+    _bias_compose(x, sett, force=True)
+    return x
+
+
 def _init_voxel_weights(x, sett, dev):
     """The observations' voxel weights as the iterations take them: a user's ``_input.weight`` validated (the
     observation's shape, real, finite, >= 0 - the one read-back) and moved to the device as contiguous float32.  With
@@ -226,7 +304,20 @@ def fit(x, y, sett):
     ``sett.voxel_robust``) as the DEVICE float32 tensor the iterations used, or None, and ``voxel_scale``: likewise each
     repeat's last robust residual scale 1.4826 median|x - A y| (a float32 CPU scalar) under ``sett.voxel_robust`` with
     ``sett.voxel_scale = 'mad'``, else None, and ``slice_gain``: likewise each repeat's final per-slice intensity gains
-    (``_input.slice_gain``, ``sett.slice_gain``; a CPU float32 tensor, one per slice along ``po.dim_thick``) or None.
+    (``_input.slice_gain``, ``sett.slice_gain``; a CPU float32 tensor, one per slice along ``po.dim_thick``) or None,
+    and ``bias``: likewise each repeat's final bias coefficients (``_input.bias_coef``, ``sett.bias``; a CPU float64
+    tensor (kx, ky, kz); ``unires_amd.bias_field`` synthesises the field from them) or None.
+
+    A bias field models an observation as b . e . (A y), b = exp(beta) > 0 smooth (receive-coil shading): a separable
+    cosine series on the observation's own grid, cut off at ``sett.bias_cutoff`` mm.  Under ``sett.bias`` the
+    coefficients of every non-CT repeat without a user's ``_input.bias_coef`` take one Gauss-Newton step after every
+    ADMM iteration's z / w update, before the slice and voxel rules write their weights (``_update_bias``), against a
+    ridge whose precision is fixed here for the whole fit; the objective carries that ridge.  The plan reads g b^2 for
+    the repeat's voxel map and x / b for its observation, recomposed once per iteration, so no solve kernel changes; that
+    is three more observation-sized buffers per repeat with a field.  A user's coefficients are used as given and never
+    re-estimated.  ``sett.noise_model = 'rician'``, ``sett.scaling``, ``sett.unified_rigid`` and ``sett.slice_gain`` are
+    refused with a field, by name (NotImplementedError); a fixed ``_input.slice_gain``, slice and voxel weights with
+    both rules and both scales, ``sett.mask_zeros``, ``sett.diff`` and channel streams work with it.
 
     Slice gains model an observation as e[s(v)] (A y)(v) (banding).  Under ``sett.slice_gain`` they are re-estimated
     after every ADMM iteration's z / w update, before the slice and voxel rules write their weights, against a ridge
@@ -265,6 +356,7 @@ def fit(x, y, sett):
         _init_slice_weights(x, sett, dev)
         _init_voxel_weights(x, sett, dev)
         _init_slice_gains(x, sett, dev)
+        _init_bias(x, sett, dev)
         N = sum(len(xc) for xc in x)
         sett = _get_sched(N, sett)
         cnt_scl = 0
@@ -324,8 +416,9 @@ def fit(x, y, sett):
                         else torch.tensor(MAD_TO_SD, dtype=torch.float32) * next(meds) for xn in xc] for xc in x]
         slice_gain = [[None if getattr(xn, 'slice_gain', None) is None else xn.slice_gain.detach().cpu() for xn in xc]
                       for xc in x]
+        bias = [[None if getattr(xn, '_bias_coef', None) is None else xn._bias_coef.clone() for xn in xc] for xc in x]
         info = dict(obj=obj[:n_done].cpu(), n_iter=n_done, reg_scl=sett.reg_scl.clone(), slice_w=slice_w,
-                    voxel_w=voxel_w, voxel_scale=voxel_scale, slice_gain=slice_gain)
+                    voxel_w=voxel_w, voxel_scale=voxel_scale, slice_gain=slice_gain, bias=bias)
         return dat_y, y[0].mat, R, info
 
 

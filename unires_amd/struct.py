@@ -40,6 +40,14 @@ class _input:
         # y-update and the objective, and with sett.gain_gn the rigid Gauss-Newton update; sett.scaling is refused with
         # them, and so is sett.unified_rigid without sett.gain_gn
         self.slice_gain = None
+        # coefficients of a smooth multiplicative bias field b = exp(beta) of the observation (receive-coil shading),
+        # float64 (kx, ky, kz), kd <= min(8, dim[d]): None - no field.  beta(i, j, k) = sum_abc c_abc phi_a(i) phi_b(j)
+        # phi_c(k) on the observation's own voxel grid, phi_m(i) = cos(pi m (2 i + 1) / (2 n)) (unnormalised DCT-II).
+        # The observation is modelled as b . e . (A y).  Set before fit() where the field is known: used as given and
+        # never re-estimated, with sett.bias on or off (fit() validates it once); with sett.bias every other non-CT
+        # observation starts from zeros and takes one Gauss-Newton step after every ADMM iteration.  Refused with the
+        # Rician model, sett.scaling, sett.unified_rigid and sett.slice_gain
+        self.bias_coef = None
         # where the observation was read from (_core._read_data; None for in-memory data)
         self.file = None    # the header the file was read with
         self.fname = None
@@ -166,6 +174,22 @@ class settings:
         # what they ran.  A switch only because those refusals are pinned by a test; not a modelling choice.
         # sett.scaling stays refused with 'rician' either way, and sett.unified_rigid with gains still needs sett.gain_gn
         self.rician_gn = False
+        # build-side knobs: a smooth multiplicative bias field per observation (receive-coil shading).  bias: every
+        # non-CT observation without a user's _input.bias_coef gets a field b = exp(beta), beta a separable cosine
+        # series of order kd = clamp(ceil(2 n_d vx_d / bias_cutoff), 1, min(8, n_d)) along axis d - half-periods no
+        # shorter than bias_cutoff mm; its coefficients take one Gauss-Newton step with a backtracking line search
+        # after every ADMM iteration (_update._update_bias).  The data term becomes 1/2 tau sum_v W (x - b mu)^2 +
+        # 1/2 c^T Lambda c, Lambda = kappa bias_reg diag(1 + sum_d (bias_cutoff m_d / (2 n_d vx_d))^2), kappa =
+        # tau sum_{x != 0} x^2 fixed for a whole fit(); the ridge on the constant term is what fixes the scale between b
+        # and y.  log b is clamped to +- log(bias_max).  The plan reads g b^2 for its voxel map and x / b for its
+        # observation: no solve kernel changes, three more observation-sized buffers per repeat.  bias_cutoff = 60 mm,
+        # bias_reg = 0.01 and bias_max = 4 are UNTUNED modelling defaults: nobody has chosen them on real data.
+        # Refused, by name, with noise_model = 'rician', scaling, unified_rigid and slice_gain.  Off:
+        # no observation has a field unless the user set _input.bias_coef
+        self.bias = False
+        self.bias_cutoff = 60.0
+        self.bias_reg = 0.01
+        self.bias_max = 4.0
         # per-voxel weight maps for init() / preproc(): a nested list shaped like the data (channels, then repeats),
         # each entry a NIfTI path, a tensor / array of the observation's shape, or None (_core._read_weights)
         self.weight = None
